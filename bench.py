@@ -6,6 +6,7 @@ launched under torch.distributed.run (one rank per GPU over RCCL), or on its own
 which case it re-launches itself that way (127.0.0.1 rendezvous, free port).  W untimed
 warm-up steps, then exactly K training steps bracketed by barrier +
 synchronize; the max over ranks is the job time; rank 0 prints ONE JSON line.
+``--dump-outputs DIR`` writes what the last timed step computed to DIR/*.npy (see dump_outputs).
 
 A step = ``ForecasterModule.training_step``-equivalent on one pre-resident
 synthetic batch per GPU: standardised inputs -> AR rollout
@@ -332,6 +333,36 @@ def oracle_loss_step0(cfg, device=None):
     return float(loss)
 
 
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(out_dir, trainer, loss):
+    """--dump-outputs: what the last timed step computed, as a caller of the training step holds it afterwards -- the loss,
+    the parameters after the optimizer update and the gradients of that step -- written as float32 .npy files, so that two
+    builds run with the same arguments (same seeded graph, weights and batch) can be compared output for output.  Parameters
+    and gradients are concatenated in the module's registration order (``module.parameters()``), without the flat buffer's
+    alignment padding.  When both would exceed DUMP_BYTES_MAX together, the same fixed, seeded sample of positions is kept
+    from each and its positions are written to params_sample_index.npy (float64, exact below 2**53)."""
+    import numpy as np
+
+    fp = trainer.fp
+    views = [(fp.offsets[i], p.numel()) for i, p in enumerate(fp.params)]
+    params = torch.cat([fp.flat[o : o + n] for o, n in views]).float().cpu()
+    grads = torch.cat([fp.grad[o : o + n] for o, n in views]).float().cpu()
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    n = params.numel()
+    keep = (DUMP_BYTES_MAX - 4096) // (4 + 4 + 8)
+    if 8 * n > DUMP_BYTES_MAX - 4096:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        params, grads = params[idx], grads[idx]
+        arrays["params_sample_index"] = idx.numpy().astype(np.float64)
+    arrays["params"] = params.numpy()
+    arrays["grads"] = grads.numpy()
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def kernel_rooflines(recs, meta, step_ms, traffic):
     """Per-launch roofline records from the instrumented eager pass (HIP events on the launch stream).
 
@@ -437,7 +468,12 @@ def main():
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python instead of replaying a HIP graph")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
                     help="bf16 = run the step inside torch.autocast(bfloat16), as Lightning --precision bf16-mixed does (cfg5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated parameters, their gradients) "
+                         "as DIR/<name>.npy, e.g. --dump-outputs bench_outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[args.config]
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -496,11 +532,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_regions(tr, b, steps):
+    def timed_regions(tr, b, steps, max_regions=5):
         """Regions of EXACTLY `steps` training steps, each bracketed by barrier + synchronize, a region's time = the max over
         ranks.  One region is the contract; when it lasts under 0.5 s (20 steps of cfg2 are 35 ms: one scheduling hiccup is
-        3 %) four more follow and the MEDIAN region is reported, all of them listed.  Every rank takes the same decision:
-        it is made on the all-reduced time."""
+        3 %) more follow, up to `max_regions`, and the MEDIAN region is reported, all of them listed.  Every rank takes the
+        same decision: it is made on the all-reduced time.  The headline measurement passes max_regions=1, so that
+        --steps is the number of timed steps."""
         regions, last = [], None
         while True:
             sync()
@@ -514,15 +551,17 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 el = float(t)
             regions.append(el)
-            if (len(regions) == 1 and el >= 0.5) or len(regions) >= 5:
+            if (len(regions) == 1 and el >= 0.5) or len(regions) >= max_regions:
                 return regions, last
 
     for _ in range(args.warmup):
         trainer.step(*batch)
-    regions, loss = timed_regions(trainer, batch, args.steps)
-    elapsed = sorted(regions)[len(regions) // 2]
+    regions, loss = timed_regions(trainer, batch, args.steps, max_regions=1)
+    elapsed = regions[0]
     ms_per_step = elapsed / args.steps * 1e3
     value = world * cfg["B"] * cfg["T"] * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), trainer, loss)
 
     # N > 1: BASELINE configs[2] (GraphLAM d = 256, 8 layers, ar_steps 4, one sample per GPU) is the configuration the
     # 0.9-efficiency target is written for; it is timed as well (same contract, fewer steps) and reported under "also".
@@ -717,7 +756,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
-            "timed_regions_ms": [x * 1e3 for x in regions],   # each = exactly `steps` steps; value / ms_per_step = the median region
+            "timed_regions_ms": [x * 1e3 for x in regions],   # one region of exactly `steps` steps: value / ms_per_step come from it
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
