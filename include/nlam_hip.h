@@ -40,6 +40,10 @@
  *   nlam_wmse_fwd / nlam_wmse_bwd
  *       metrics.wmse + mask_and_reduce_metric (metrics.py:37-137) with the batch / step means of
  *       models/module.py:463-510.
+ *   nlam_loss_fwd / nlam_loss_bwd, nlam_step_tail_loss_fwd / nlam_step_tail_loss_bwd
+ *       the other losses of --loss (train_model.py:271-276): metrics.mse / mae / wmae / nll / crps_gauss
+ *       (and wmse), per-variable or per-entry (predicted) std, the same reduction; the step-tail pair fuses
+ *       them into the AR step's state update as nlam_step_tail_* does for wmse.
  *   nlam_reduce_partials
  *       deterministic second stage of the per-workgroup partial sums.
  *   nlam_adamw_step
@@ -530,6 +534,60 @@ int32_t nlam_step_tail_fwd(const float* delta, const float* prev, const float* t
 int32_t nlam_step_tail_bwd(const float* g_pred, const float* gloss, const float* pred, const float* target, const float* dstd,
                            const float* bmask, const float* inv_var, const float* row_weight, float scale, float* d_delta,
                            float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream);
+
+/* The training losses the reference selects with --loss (train_model.py:271-276, metrics.DEFINED_METRICS, metrics.py:87-386).
+ * With d = pred - target, s the std and z = (target - pred) / s, the entry of each kind is
+ *   NLAM_LOSS_MSE         d^2                     (s ignored: the reference replaces it with ones)
+ *   NLAM_LOSS_MAE         |d|                     (s ignored)
+ *   NLAM_LOSS_WMSE        d^2 / s^2
+ *   NLAM_LOSS_WMAE        |d| / s
+ *   NLAM_LOSS_NLL         d^2 / (2 s^2) + log s + log(2 pi) / 2
+ *   NLAM_LOSS_CRPS_GAUSS  s * (z * (2 Phi(z) - 1) + 2 phi(z) - pi^-1/2)
+ * and the reduction is that of nlam_wmse_fwd:  loss = scale * sum_{row, v} row_weight[row % nodes] * entry.  sign(0) = 0 in the
+ * gradients of the absolute errors (torch.l1_loss).  The std is not validated on the device (s > 0 is the caller's contract). */
+#define NLAM_LOSS_MSE        1
+#define NLAM_LOSS_MAE        2
+#define NLAM_LOSS_WMSE       3
+#define NLAM_LOSS_WMAE       4
+#define NLAM_LOSS_NLL        5
+#define NLAM_LOSS_CRPS_GAUSS 6
+#define NLAM_LOSS_MAX_VARS   4096   /* nvars of a per-variable std (its constants live in LDS); NLAM_EUNSUP above */
+/* One masked loss pass over (rows, nvars) fp32 rows, rows = batch * ar_steps * nodes.  The std is per entry (`std`, the
+ * rollout's pred_std of an output_std model) or, with std == NULL, per variable (`var_std`, module.py:157-178); mse / mae read
+ * neither.  nlam_loss_fwd writes one partial per block into partials[0 .. nparts) (finish with nlam_reduce_partials, fixed
+ * order: bit-identical run to run); nlam_loss_bwd takes the upstream scalar gradient from gscalar (device memory: capturable)
+ * and writes dpred and, when dstd != NULL (per-entry std only), dstd; both are 0 on rows of weight 0.  NLAM_EINVAL for an
+ * unknown kind, null pointers or sizes that do not fit together (rows % nodes != 0), before anything is launched. */
+typedef struct {
+    const float* pred;         /* (rows, nvars) */
+    const float* target;       /* (rows, nvars) */
+    const float* std;          /* (rows, nvars) per-entry std, or NULL */
+    const float* var_std;      /* (nvars) per-variable std, read when std == NULL */
+    const float* row_weight;   /* (nodes) interior mask / #interior nodes */
+    const float* gscalar;      /* backward: the scalar gradient of the loss (device) */
+    float* partials;           /* forward: (nparts) */
+    float* dpred;              /* backward: (rows, nvars) */
+    float* dstd;               /* backward: (rows, nvars) or NULL */
+    int64_t rows;
+    int32_t nodes;
+    int32_t nvars;
+    int32_t kind;              /* NLAM_LOSS_* */
+    int32_t nparts;
+    float scale;               /* 1 / (batch * ar_steps) */
+    int32_t _pad;
+} nlam_loss_t;
+int32_t nlam_loss_fwd(const nlam_loss_t* p, void* hip_stream);
+int32_t nlam_loss_bwd(const nlam_loss_t* p, void* hip_stream);
+/* nlam_step_tail_fwd / _bwd with the loss term of any NLAM_LOSS_* kind for a per-variable std (`var_std`, may be NULL for mse /
+ * mae) instead of inv_var:  loss += scale * row_weight[n] * entry(pred - target, var_std[f]),
+ *   G = g_pred + scale * gloss * row_weight[n] * d entry / d pred.  Still one pass each way per AR step. */
+int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* prev, const float* truth, const float* target,
+                                const float* dstd, const float* dmean, const float* bmask, const float* var_std,
+                                const float* row_weight, float scale, float* pred, float* partials, int32_t nparts, int64_t rows,
+                                int32_t nodes, int32_t width, void* hip_stream);
+int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target,
+                                const float* dstd, const float* bmask, const float* var_std, const float* row_weight, float scale,
+                                float* d_delta, float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream);
 
 /* Row-wise concatenation of up to NLAM_MAX_CAT sources into out (rows, sum of widths): the torch.cat of the grid input
  * features (prev_state, prev_prev_state, forcing, static features; step_predictors/graph/base.py:275-283).  A source

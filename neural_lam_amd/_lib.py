@@ -36,6 +36,10 @@ TUNE_WBF_EDGE = 11
 TUNE_WGRAD_MAX_WGS = 12
 TUNE_CHAIN_CUS = 13
 TILE_SPLIT = 1 << 30
+# training-loss kinds (NLAM_LOSS_*), keyed by the reference's metric names (metrics.DEFINED_METRICS)
+LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
+LOSS_MSE, LOSS_MAE, LOSS_WMSE, LOSS_WMAE, LOSS_NLL, LOSS_CRPS_GAUSS = 1, 2, 3, 4, 5, 6
+LOSS_MAX_VARS = 4096
 
 EXPORTS = [
     "nlam_abi_version",
@@ -81,6 +85,10 @@ EXPORTS = [
     "nlam_pre_add_supported",
     "nlam_step_tail_fwd",
     "nlam_step_tail_bwd",
+    "nlam_loss_fwd",
+    "nlam_loss_bwd",
+    "nlam_step_tail_loss_fwd",
+    "nlam_step_tail_loss_bwd",
     "nlam_concat",
     "nlam_window_len",
     "nlam_window_batch",
@@ -269,6 +277,27 @@ class Window(C.Structure):
     ]
 
 
+class Loss(C.Structure):
+    _fields_ = [
+        ("pred", C.c_void_p),
+        ("target", C.c_void_p),
+        ("std", C.c_void_p),
+        ("var_std", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("gscalar", C.c_void_p),
+        ("partials", C.c_void_p),
+        ("dpred", C.c_void_p),
+        ("dstd", C.c_void_p),
+        ("rows", C.c_int64),
+        ("nodes", C.c_int32),
+        ("nvars", C.c_int32),
+        ("kind", C.c_int32),
+        ("nparts", C.c_int32),
+        ("scale", C.c_float),
+        ("_pad", C.c_int32),
+    ]
+
+
 class StdJob(C.Structure):
     _fields_ = [
         ("x", C.c_void_p),
@@ -393,6 +422,14 @@ def load():
     lib.nlam_step_tail_fwd.restype = i32
     lib.nlam_step_tail_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.nlam_step_tail_bwd.restype = i32
+    lib.nlam_loss_fwd.argtypes = [C.POINTER(Loss), vp]
+    lib.nlam_loss_fwd.restype = i32
+    lib.nlam_loss_bwd.argtypes = [C.POINTER(Loss), vp]
+    lib.nlam_loss_bwd.restype = i32
+    lib.nlam_step_tail_loss_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i64, i32, i32, vp]
+    lib.nlam_step_tail_loss_fwd.restype = i32
+    lib.nlam_step_tail_loss_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
+    lib.nlam_step_tail_loss_bwd.restype = i32
     lib.nlam_concat.argtypes = [C.POINTER(Cat), vp]
     lib.nlam_concat.restype = i32
     lib.nlam_window_len.argtypes = [i64, i64, i32, i32, i32]

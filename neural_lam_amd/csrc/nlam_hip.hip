@@ -3402,6 +3402,312 @@ __global__ void step_tail_bwd_kernel(const float* __restrict__ g_pred, const flo
     }
 }
 
+// ---------------------------------------------------------------------------
+// the --loss kinds of metrics.py (nlam_loss_fwd / _bwd, nlam_step_tail_loss_fwd / _bwd; KIND = NLAM_LOSS_*).  The std enters
+// an entry through two constants (loss_consts): per variable they are computed once per workgroup into LDS, per entry (a
+// predicted std) per element.  Accurate expf / erff / logf: the passes are HBM-bound.
+// ---------------------------------------------------------------------------
+constexpr float kInvSqrtPi = 0.564189583547756287f;    // pi^-1/2
+constexpr float kInvSqrt2Pi = 0.398942280401432678f;   // (2 pi)^-1/2
+constexpr float kHalfLog2Pi = 0.918938533204672742f;   // log(2 pi) / 2
+constexpr float kSqrtHalf = 0.707106781186547524f;
+
+__device__ __forceinline__ float std_normal_cdf(float z) { return 0.5f * (1.f + erff(z * kSqrtHalf)); }
+__device__ __forceinline__ float sign0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }   // torch.sign: sign(0) = 0
+
+// c0 = 1 / s^2 (wmse, nll) or 1 / s (wmae, crps_gauss); c1 = log s + log(2 pi) / 2 (nll) or s (crps_gauss)
+template <int KIND>
+__device__ __forceinline__ void loss_consts(float s, float& c0, float& c1) {
+    c0 = 0.f;
+    c1 = 0.f;
+    if constexpr (KIND == NLAM_LOSS_WMSE || KIND == NLAM_LOSS_NLL) c0 = 1.f / (s * s);
+    if constexpr (KIND == NLAM_LOSS_WMAE || KIND == NLAM_LOSS_CRPS_GAUSS) c0 = 1.f / s;
+    if constexpr (KIND == NLAM_LOSS_NLL) c1 = logf(s) + kHalfLog2Pi;
+    if constexpr (KIND == NLAM_LOSS_CRPS_GAUSS) c1 = s;
+}
+
+template <int KIND>
+__device__ __forceinline__ float loss_entry(float d, float c0, float c1) {
+    if constexpr (KIND == NLAM_LOSS_MSE) return d * d;
+    else if constexpr (KIND == NLAM_LOSS_MAE) return fabsf(d);
+    else if constexpr (KIND == NLAM_LOSS_WMSE) return d * d * c0;
+    else if constexpr (KIND == NLAM_LOSS_WMAE) return fabsf(d) * c0;
+    else if constexpr (KIND == NLAM_LOSS_NLL) return 0.5f * d * d * c0 + c1;
+    else {
+        const float z = -d * c0;
+        return c1 * (z * (2.f * std_normal_cdf(z) - 1.f) + 2.f * kInvSqrt2Pi * expf(-0.5f * z * z) - kInvSqrtPi);
+    }
+}
+
+// d entry / d pred
+template <int KIND>
+__device__ __forceinline__ float loss_dpred(float d, float c0) {
+    if constexpr (KIND == NLAM_LOSS_MSE) return 2.f * d;
+    else if constexpr (KIND == NLAM_LOSS_MAE) return sign0(d);
+    else if constexpr (KIND == NLAM_LOSS_WMSE) return 2.f * d * c0;
+    else if constexpr (KIND == NLAM_LOSS_WMAE) return sign0(d) * c0;
+    else if constexpr (KIND == NLAM_LOSS_NLL) return d * c0;
+    else return 1.f - 2.f * std_normal_cdf(-d * c0);
+}
+
+// d entry / d s (a per-entry std); 0 for mse / mae, which do not read it
+template <int KIND>
+__device__ __forceinline__ float loss_dstd(float d, float s) {
+    const float r = 1.f / s;
+    if constexpr (KIND == NLAM_LOSS_WMSE) return -2.f * d * d * r * r * r;
+    else if constexpr (KIND == NLAM_LOSS_WMAE) return -fabsf(d) * r * r;
+    else if constexpr (KIND == NLAM_LOSS_NLL) return r - d * d * r * r * r;
+    else if constexpr (KIND == NLAM_LOSS_CRPS_GAUSS) {
+        const float z = -d * r;
+        return 2.f * kInvSqrt2Pi * expf(-0.5f * z * z) - kInvSqrtPi;
+    } else return 0.f;
+}
+
+// the (c0, c1) pair of every variable into LDS, once per workgroup (var_std may be NULL for mse / mae)
+template <int KIND>
+__device__ __forceinline__ void stage_loss_consts(const float* var_std, int nvars, float2* lc) {
+    for (int v = threadIdx.x; v < nvars; v += blockDim.x) {
+        float c0 = 0.f, c1 = 0.f;
+        if (var_std != nullptr) loss_consts<KIND>(var_std[v], c0, c1);
+        lc[v] = make_float2(c0, c1);
+    }
+    __syncthreads();
+}
+
+// partial[block] = scale * sum row_weight[row % nodes] * entry; 16-byte path with incrementally advanced (variable, node) counters
+// where every operand is aligned and the count is a multiple of 4, the scalar loop otherwise
+template <int KIND, bool PER_ENTRY>
+__global__ __launch_bounds__(256) void loss_fwd_kernel(const nlam_loss_t p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* lc = reinterpret_cast<float2*>(smem);
+    __shared__ float red[4];
+    if constexpr (!PER_ENTRY) stage_loss_consts<KIND>(p.var_std, p.nvars, lc);
+    const int nodes = p.nodes, width = p.nvars;
+    const long total = p.rows * width;
+    const bool small = total < (1L << 31);
+    auto entry = [&](float pv, float tv, float sv, int f) {
+        float c0, c1;
+        if constexpr (PER_ENTRY) {
+            loss_consts<KIND>(sv, c0, c1);
+        } else {
+            const float2 c = lc[f];
+            c0 = c.x;
+            c1 = c.y;
+        }
+        return loss_entry<KIND>(pv - tv, c0, c1);
+    };
+    float s = 0.f;
+    const bool vec = (total & 3) == 0 && small &&
+                     ((reinterpret_cast<uintptr_t>(p.pred) | reinterpret_cast<uintptr_t>(p.target) |
+                       (PER_ENTRY ? reinterpret_cast<uintptr_t>(p.std) : 0)) & 15) == 0;
+    if (vec) {
+        const unsigned nq = (unsigned)(total >> 2), nthr = gridDim.x * blockDim.x;
+        for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += nthr) {
+            const unsigned e = 4 * q;
+            const unsigned r = e / (unsigned)width;
+            int f = (int)(e - r * (unsigned)width);
+            int n = (int)(r % (unsigned)nodes);
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(p.pred + e), tv = *reinterpret_cast<const f32x4*>(p.target + e);
+            f32x4 sv = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (PER_ENTRY) sv = *reinterpret_cast<const f32x4*>(p.std + e);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float w = p.row_weight[n];
+                if (w != 0.f) s += w * entry(pv[c], tv[c], sv[c], f);
+                if (++f == width) {
+                    f = 0;
+                    if (++n == nodes) n = 0;
+                }
+            }
+        }
+    }
+    for (long e0 = vec ? total : (long)blockIdx.x * blockDim.x; e0 < total; e0 += (long)gridDim.x * blockDim.x) {
+        const long e = e0 + threadIdx.x;
+        if (e < total) {
+            long r;
+            int n;
+            row_and_node(e, width, nodes, small, r, n);
+            const int f = (int)(e - r * width);
+            const float w = p.row_weight[n];
+            if (w != 0.f) s += w * entry(p.pred[e], p.target[e], PER_ENTRY ? p.std[e] : 0.f, f);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) p.partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * p.scale;
+}
+
+// dpred = g * row_weight * d entry / d pred, dstd = g * row_weight * d entry / d s (per-entry std), g = scale * gscalar[0]
+template <int KIND, bool PER_ENTRY>
+__global__ __launch_bounds__(256) void loss_bwd_kernel(const nlam_loss_t p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* lc = reinterpret_cast<float2*>(smem);
+    if constexpr (!PER_ENTRY) stage_loss_consts<KIND>(p.var_std, p.nvars, lc);
+    const float g = p.scale * p.gscalar[0];
+    const int nodes = p.nodes, width = p.nvars;
+    const long total = p.rows * width;
+    const bool small = total < (1L << 31);
+    float* const dstd = PER_ENTRY ? p.dstd : nullptr;
+    // (dpred, dstd) of one element
+    auto grads = [&](float pv, float tv, float sv, int f, float w, float& gp, float& gs) {
+        gp = 0.f;
+        gs = 0.f;
+        if (w == 0.f) return;
+        const float d = pv - tv;
+        if constexpr (PER_ENTRY) {
+            float c0, c1;
+            loss_consts<KIND>(sv, c0, c1);
+            gp = g * w * loss_dpred<KIND>(d, c0);
+            gs = g * w * loss_dstd<KIND>(d, sv);
+        } else {
+            gp = g * w * loss_dpred<KIND>(d, lc[f].x);
+        }
+    };
+    const bool vec = (total & 3) == 0 && small &&
+                     ((reinterpret_cast<uintptr_t>(p.pred) | reinterpret_cast<uintptr_t>(p.target) |
+                       reinterpret_cast<uintptr_t>(p.dpred) | (PER_ENTRY ? reinterpret_cast<uintptr_t>(p.std) : 0) |
+                       reinterpret_cast<uintptr_t>(dstd)) & 15) == 0;
+    if (vec) {
+        const unsigned nq = (unsigned)(total >> 2), nthr = gridDim.x * blockDim.x;
+        for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += nthr) {
+            const unsigned e = 4 * q;
+            const unsigned r = e / (unsigned)width;
+            int f = (int)(e - r * (unsigned)width);
+            int n = (int)(r % (unsigned)nodes);
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(p.pred + e), tv = *reinterpret_cast<const f32x4*>(p.target + e);
+            f32x4 sv = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (PER_ENTRY) sv = *reinterpret_cast<const f32x4*>(p.std + e);
+            f32x4 gp4, gs4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float gp, gs;
+                grads(pv[c], tv[c], sv[c], f, p.row_weight[n], gp, gs);
+                gp4[c] = gp;
+                gs4[c] = gs;
+                if (++f == width) {
+                    f = 0;
+                    if (++n == nodes) n = 0;
+                }
+            }
+            *reinterpret_cast<f32x4*>(p.dpred + e) = gp4;
+            if (dstd != nullptr) *reinterpret_cast<f32x4*>(dstd + e) = gs4;
+        }
+        return;
+    }
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        long r;
+        int n;
+        row_and_node(e, width, nodes, small, r, n);
+        const int f = (int)(e - r * width);
+        float gp, gs;
+        grads(p.pred[e], p.target[e], PER_ENTRY ? p.std[e] : 0.f, f, p.row_weight[n], gp, gs);
+        p.dpred[e] = gp;
+        if (dstd != nullptr) dstd[e] = gs;
+    }
+}
+
+// step_tail_fwd_kernel with the loss term of KIND (per-variable std: constants in LDS)
+template <int KIND>
+__global__ __launch_bounds__(256) void step_tail_loss_fwd_kernel(const float* __restrict__ delta, const float* __restrict__ prev,
+                                                                 const float* __restrict__ truth, const float* __restrict__ target,
+                                                                 const float* __restrict__ dstd, const float* __restrict__ dmean,
+                                                                 const float* __restrict__ bmask, const float* __restrict__ var_std,
+                                                                 const float* __restrict__ row_weight, float scale,
+                                                                 float* __restrict__ pred, float* __restrict__ partials, long total,
+                                                                 int nodes, int width) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* lc = reinterpret_cast<float2*>(smem);
+    __shared__ float red[4];
+    stage_loss_consts<KIND>(var_std, width, lc);
+    float s = 0.f;
+    const bool small = total < (1L << 31);
+    const bool vec = (total & 3) == 0 && small &&
+                     ((reinterpret_cast<uintptr_t>(delta) | reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(truth) |
+                       reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(pred)) & 15) == 0;
+    if (vec) {
+        const unsigned nq = (unsigned)(total >> 2), nthr = gridDim.x * blockDim.x;
+        for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += nthr) {
+            const unsigned e = 4 * q;
+            unsigned r = e / (unsigned)width;
+            int f = (int)(e - r * (unsigned)width);
+            int n = (int)(r % (unsigned)nodes);
+            const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + e), pr = *reinterpret_cast<const f32x4*>(prev + e);
+            const f32x4 tr = *reinterpret_cast<const f32x4*>(truth + e), tg = *reinterpret_cast<const f32x4*>(target + e);
+            f32x4 pv4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float nw = pr[c] + (dstd != nullptr ? dl[c] * dstd[f] : dl[c]);
+                if (dmean != nullptr) nw += dmean[f];
+                const float bm = bmask[n];
+                const float pv = bm * tr[c] + (1.f - bm) * nw;
+                pv4[c] = pv;
+                const float w = row_weight[n];
+                if (w != 0.f) {
+                    const float2 k = lc[f];
+                    s += w * loss_entry<KIND>(pv - tg[c], k.x, k.y);
+                }
+                if (++f == width) {
+                    f = 0;
+                    if (++n == nodes) n = 0;
+                }
+            }
+            *reinterpret_cast<f32x4*>(pred + e) = pv4;
+        }
+    }
+    for (long e0 = vec ? total : (long)blockIdx.x * blockDim.x; e0 < total; e0 += (long)gridDim.x * blockDim.x) {
+        const long e = e0 + threadIdx.x;
+        if (e < total) {
+            long r;
+            int n;
+            row_and_node(e, width, nodes, small, r, n);
+            const int f = (int)(e - r * width);
+            float nw = prev[e] + (dstd != nullptr ? delta[e] * dstd[f] : delta[e]);
+            if (dmean != nullptr) nw += dmean[f];
+            const float bm = bmask[n];
+            const float pv = bm * truth[e] + (1.f - bm) * nw;
+            pred[e] = pv;
+            const float w = row_weight[n];
+            if (w != 0.f) {
+                const float2 k = lc[f];
+                s += w * loss_entry<KIND>(pv - target[e], k.x, k.y);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void step_tail_loss_bwd_kernel(const float* __restrict__ g_pred, const float* __restrict__ gloss,
+                                                                 const float* __restrict__ pred, const float* __restrict__ target,
+                                                                 const float* __restrict__ dstd, const float* __restrict__ bmask,
+                                                                 const float* __restrict__ var_std, const float* __restrict__ row_weight,
+                                                                 float scale, float* __restrict__ d_delta, float* __restrict__ d_prev,
+                                                                 long total, int nodes, int width) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* lc = reinterpret_cast<float2*>(smem);
+    stage_loss_consts<KIND>(var_std, width, lc);
+    const float g = scale * gloss[0];
+    const bool small = total < (1L << 31);
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        long r;
+        int n;
+        row_and_node(e, width, nodes, small, r, n);
+        const int f = (int)(e - r * width);
+        const float w = row_weight[n];
+        float G = g_pred != nullptr ? g_pred[e] : 0.f;
+        if (w != 0.f) G += g * w * loss_dpred<KIND>(pred[e] - target[e], lc[f].x);
+        G *= 1.f - bmask[n];
+        if (d_prev != nullptr) d_prev[e] = G;
+        if (d_delta != nullptr) d_delta[e] = dstd != nullptr ? G * dstd[f] : G;
+    }
+}
+
 // row-wise concatenation (nlam_concat): a workgroup owns 64 consecutive rows; every source's 64 x w_k block is one
 // contiguous span in memory (read coalesced into the LDS row image), and so is the 64 x wtot output block
 constexpr int kCatRows = 64;
@@ -6003,6 +6309,74 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
 #endif
 
 #if NLAM_IN_TU(1)
+namespace {
+// nlam_loss_fwd / _bwd and nlam_step_tail_loss_fwd / _bwd: the NLAM_LOSS_* kind as a template argument (arguments validated)
+bool loss_kind_valid(int32_t kind) { return kind >= NLAM_LOSS_MSE && kind <= NLAM_LOSS_CRPS_GAUSS; }
+bool loss_reads_std(int32_t kind) { return kind != NLAM_LOSS_MSE && kind != NLAM_LOSS_MAE; }
+
+long loss_bwd_blocks(long total) {
+    const long blocks = (total + 255) / 256;
+    return blocks > 2048 ? 2048 : blocks;
+}
+
+template <int KIND>
+int32_t loss_launch(const nlam_loss_t& p, bool bwd, hipStream_t stream) {
+    const bool per_entry = p.std != nullptr;
+    const size_t lds = per_entry ? 0 : (size_t)p.nvars * sizeof(float2);
+    if (!bwd) {
+        if (per_entry) hipLaunchKernelGGL((loss_fwd_kernel<KIND, true>), dim3(p.nparts), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((loss_fwd_kernel<KIND, false>), dim3(p.nparts), dim3(256), lds, stream, p);
+    } else {
+        const long blocks = loss_bwd_blocks((long)p.rows * p.nvars);
+        if (per_entry) hipLaunchKernelGGL((loss_bwd_kernel<KIND, true>), dim3((int)blocks), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((loss_bwd_kernel<KIND, false>), dim3((int)blocks), dim3(256), lds, stream, p);
+    }
+    return (int32_t)hipGetLastError();
+}
+
+int32_t loss_dispatch(const nlam_loss_t& p, bool bwd, hipStream_t stream) {
+    switch (p.kind) {
+        case NLAM_LOSS_MSE: return loss_launch<NLAM_LOSS_MSE>(p, bwd, stream);
+        case NLAM_LOSS_MAE: return loss_launch<NLAM_LOSS_MAE>(p, bwd, stream);
+        case NLAM_LOSS_WMSE: return loss_launch<NLAM_LOSS_WMSE>(p, bwd, stream);
+        case NLAM_LOSS_WMAE: return loss_launch<NLAM_LOSS_WMAE>(p, bwd, stream);
+        case NLAM_LOSS_NLL: return loss_launch<NLAM_LOSS_NLL>(p, bwd, stream);
+        case NLAM_LOSS_CRPS_GAUSS: return loss_launch<NLAM_LOSS_CRPS_GAUSS>(p, bwd, stream);
+        default: return NLAM_EINVAL;
+    }
+}
+
+// the checks both directions share: kind, pointers, sizes; NLAM_EUNSUP for a per-variable std wider than the LDS table
+int32_t loss_check(const nlam_loss_t* p) {
+    if (p == nullptr || !loss_kind_valid(p->kind) || p->pred == nullptr || p->target == nullptr || p->row_weight == nullptr)
+        return NLAM_EINVAL;
+    if (p->rows < 1 || p->nodes < 1 || p->nvars < 1 || p->rows % p->nodes != 0) return NLAM_EINVAL;
+    if (loss_reads_std(p->kind) && p->std == nullptr && p->var_std == nullptr) return NLAM_EINVAL;
+    if (p->std == nullptr && p->nvars > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
+    return 0;
+}
+
+template <int KIND>
+void step_tail_loss_fwd_launch(const float* delta, const float* prev, const float* truth, const float* target, const float* dstd,
+                               const float* dmean, const float* bmask, const float* var_std, const float* row_weight, float scale,
+                               float* pred, float* partials, int32_t nparts, long total, int32_t nodes, int32_t width,
+                               hipStream_t stream) {
+    hipLaunchKernelGGL((step_tail_loss_fwd_kernel<KIND>), dim3(nparts), dim3(256), (size_t)width * sizeof(float2), stream, delta,
+                       prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, total, nodes, width);
+}
+
+template <int KIND>
+void step_tail_loss_bwd_launch(const float* g_pred, const float* gloss, const float* pred, const float* target, const float* dstd,
+                               const float* bmask, const float* var_std, const float* row_weight, float scale, float* d_delta,
+                               float* d_prev, long total, int32_t nodes, int32_t width, hipStream_t stream) {
+    hipLaunchKernelGGL((step_tail_loss_bwd_kernel<KIND>), dim3((int)loss_bwd_blocks(total)), dim3(256), (size_t)width * sizeof(float2),
+                       stream, g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, total, nodes,
+                       width);
+}
+}  // namespace
+#endif
+
+#if NLAM_IN_TU(1)
 extern "C" {
 
 // the same segment sum over rows stored as bf16 (the dz1 rows of a layer running with NLAM_F_STORE_BF16: gradient of a
@@ -6293,6 +6667,68 @@ int32_t nlam_adamw_step_resident(float* param, const float* grad, float* exp_avg
                        beta2, eps, weight_decay, 1.f, 1.f, grad_scale, (const float*)bias_corr_dev);
     return (int32_t)hipGetLastError();
 }
+
+
+int32_t nlam_loss_fwd(const nlam_loss_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_loss_fwd");
+    if (const int32_t rc = loss_check(p)) return rc;
+    if (p->partials == nullptr || p->nparts < 1) return NLAM_EINVAL;
+    return loss_dispatch(*p, false, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_loss_bwd(const nlam_loss_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_loss_bwd");
+    if (const int32_t rc = loss_check(p)) return rc;
+    if (p->gscalar == nullptr || p->dpred == nullptr || (p->dstd != nullptr && p->std == nullptr)) return NLAM_EINVAL;
+    return loss_dispatch(*p, true, (hipStream_t)hip_stream);
+}
+
+#define NLAM_LOSS_SWITCH(kind, CALL)                                 \
+    switch (kind) {                                                  \
+        case NLAM_LOSS_MSE: CALL(NLAM_LOSS_MSE); break;               \
+        case NLAM_LOSS_MAE: CALL(NLAM_LOSS_MAE); break;               \
+        case NLAM_LOSS_WMSE: CALL(NLAM_LOSS_WMSE); break;             \
+        case NLAM_LOSS_WMAE: CALL(NLAM_LOSS_WMAE); break;             \
+        case NLAM_LOSS_NLL: CALL(NLAM_LOSS_NLL); break;               \
+        case NLAM_LOSS_CRPS_GAUSS: CALL(NLAM_LOSS_CRPS_GAUSS); break; \
+        default: return NLAM_EINVAL;                                 \
+    }
+
+int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* prev, const float* truth, const float* target,
+                                const float* dstd, const float* dmean, const float* bmask, const float* var_std,
+                                const float* row_weight, float scale, float* pred, float* partials, int32_t nparts, int64_t rows,
+                                int32_t nodes, int32_t width, void* hip_stream) {
+    NLAM_RANGE("nlam_step_tail_loss_fwd");
+    if (!loss_kind_valid(kind) || delta == nullptr || prev == nullptr || truth == nullptr || target == nullptr || bmask == nullptr ||
+        row_weight == nullptr || pred == nullptr || partials == nullptr || (loss_reads_std(kind) && var_std == nullptr))
+        return NLAM_EINVAL;
+    if (rows < 1 || nodes < 1 || width < 1 || nparts < 1 || rows % nodes != 0) return NLAM_EINVAL;
+    if (width > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
+#define NLAM_STL_FWD(K)                                                                                                     \
+    step_tail_loss_fwd_launch<K>(delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, \
+                                 nparts, (long)rows * width, nodes, width, (hipStream_t)hip_stream)
+    NLAM_LOSS_SWITCH(kind, NLAM_STL_FWD)
+#undef NLAM_STL_FWD
+    return (int32_t)hipGetLastError();
+}
+
+int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target,
+                                const float* dstd, const float* bmask, const float* var_std, const float* row_weight, float scale,
+                                float* d_delta, float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream) {
+    NLAM_RANGE("nlam_step_tail_loss_bwd");
+    if (!loss_kind_valid(kind) || gloss == nullptr || pred == nullptr || target == nullptr || bmask == nullptr ||
+        row_weight == nullptr || (loss_reads_std(kind) && var_std == nullptr))
+        return NLAM_EINVAL;
+    if ((d_delta == nullptr && d_prev == nullptr) || rows < 1 || nodes < 1 || width < 1 || rows % nodes != 0) return NLAM_EINVAL;
+    if (width > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
+#define NLAM_STL_BWD(K)                                                                                                    \
+    step_tail_loss_bwd_launch<K>(g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, \
+                                 (long)rows * width, nodes, width, (hipStream_t)hip_stream)
+    NLAM_LOSS_SWITCH(kind, NLAM_STL_BWD)
+#undef NLAM_STL_BWD
+    return (int32_t)hipGetLastError();
+}
+#undef NLAM_LOSS_SWITCH
 
 }  // extern "C"
 #endif

@@ -14,6 +14,7 @@ Reference -> here (same class / argument / attribute / parameter names):
   HiLAMParallel      models/step_predictors/graph/hi_lam_parallel.py:24-218
   ARForecaster       models/forecasters/autoregressive.py:14-149
   wmse               metrics.py:37-137
+  mse .. get_metric  metrics.py:10-34, 140-394 (mse, mae, wmae, nll, crps_gauss: evaluation formulas)
   ForecasterStep     the training_step / loss / AdamW lines of models/module.py:293-304, 326-417, 463-510
 
 Differences that do not change results: the graph may be handed in pre-loaded
@@ -581,7 +582,9 @@ class ARForecaster(nn.Module):
         """``loss_spec = (target_states, inv_var (F,), row_weight (N,), scale)``: also return the training loss
         ``scale * sum_t sum_n,f row_weight * inv_var * (pred - target)^2`` as a third value, with each step's state
         update + boundary overwrite + loss term fused into one pass (ops.StepTailFunction) when the predictor's tail is
-        the plain rescale (no clamping / predicted std)."""
+        the plain rescale (no clamping / predicted std).  ``loss_spec = (target_states, var_std (F,), row_weight (N,), scale,
+        kind)`` with a ``_lib.LOSS_*`` kind: the same for that loss with the per-variable std ``var_std``
+        (ops.StepTailLossFunction); the third value is None where the tail cannot be fused."""
         prev_prev_state, prev_state = init_states[:, 0], init_states[:, 1]
         preds, stds = [], []
         cache = self.predictor.static_cache() if hasattr(self.predictor, "static_cache") else contextlib.nullcontext()
@@ -591,13 +594,19 @@ class ARForecaster(nn.Module):
         with cache:
             for i in range(forcing_features.shape[1]):
                 if fused_tail:
-                    from .ops import StepTailFunction
+                    from .ops import StepTailFunction, StepTailLossFunction
 
-                    target, inv_var, row_weight, scale = loss_spec
                     delta, _ = self.predictor(prev_state, prev_prev_state, forcing_features[:, i], raw_delta=True)
-                    new_state, loss_t = StepTailFunction.apply(
-                        delta.float(), prev_state, boundary_states[:, i], target[:, i], self.predictor.diff_std, self.predictor.diff_mean,
-                        self.boundary_mask.reshape(-1), inv_var, row_weight, scale)
+                    if len(loss_spec) == 4:
+                        target, inv_var, row_weight, scale = loss_spec
+                        new_state, loss_t = StepTailFunction.apply(
+                            delta.float(), prev_state, boundary_states[:, i], target[:, i], self.predictor.diff_std,
+                            self.predictor.diff_mean, self.boundary_mask.reshape(-1), inv_var, row_weight, scale)
+                    else:
+                        target, var_std, row_weight, scale, kind = loss_spec
+                        new_state, loss_t = StepTailLossFunction.apply(
+                            delta.float(), prev_state, boundary_states[:, i], target[:, i], self.predictor.diff_std,
+                            self.predictor.diff_mean, self.boundary_mask.reshape(-1), var_std, row_weight, scale, kind)
                     preds.append(new_state)
                     losses.append(loss_t)
                     prev_prev_state, prev_state = prev_state, new_state
@@ -646,16 +655,71 @@ def wmse(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
     return mask_and_reduce_metric(entry, mask, average_grid, sum_vars)
 
 
+# The other metrics of metrics.DEFINED_METRICS as plain torch formulas, for evaluation code; training runs them on
+# ops.LossFunction / ops.StepTailLossFunction (ForecasterStep(loss=...)).
+def mse(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
+    """metrics.py:140-182: wmse with the std replaced by ones."""
+    return wmse(pred, target, torch.ones_like(pred_std), mask, average_grid, sum_vars)
+
+
+def wmae(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
+    """metrics.py:185-235."""
+    entry = torch.nn.functional.l1_loss(pred, target, reduction="none") / pred_std
+    return mask_and_reduce_metric(entry, mask, average_grid, sum_vars)
+
+
+def mae(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
+    """metrics.py:238-280: wmae with the std replaced by ones."""
+    return wmae(pred, target, torch.ones_like(pred_std), mask, average_grid, sum_vars)
+
+
+def nll(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
+    """metrics.py:283-329: -log N(target; pred, pred_std)."""
+    entry = -torch.distributions.Normal(pred, pred_std).log_prob(target)
+    return mask_and_reduce_metric(entry, mask, average_grid, sum_vars)
+
+
+def crps_gauss(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
+    """metrics.py:332-386: closed-form CRPS of a Gaussian."""
+    std_normal = torch.distributions.Normal(torch.zeros((), device=pred.device), torch.ones((), device=pred.device))
+    z = (target - pred) / pred_std
+    entry = -pred_std * (torch.pi ** (-0.5) - 2 * torch.exp(std_normal.log_prob(z)) - z * (2 * std_normal.cdf(z) - 1))
+    return mask_and_reduce_metric(entry, mask, average_grid, sum_vars)
+
+
+DEFINED_METRICS = {"mse": mse, "mae": mae, "wmse": wmse, "wmae": wmae, "nll": nll, "crps_gauss": crps_gauss}
+
+
+def get_metric(metric_name):
+    """metrics.py:10-34: the metric function of a (case-insensitive) name (ValueError for an unknown one)."""
+    name = metric_name.lower()
+    if name not in DEFINED_METRICS:
+        raise ValueError(f"Unknown metric: {metric_name}")
+    return DEFINED_METRICS[name]
+
+
 class ForecasterStep(nn.Module):
     """The training_step / loss lines of ``ForecasterModule`` (models/module.py)
     without Lightning: on-device standardisation (:326-367), rollout + masked
-    ``wmse`` per step, mean over batch then over steps (:463-510, :412)."""
+    loss per step (``wmse`` unless ``loss`` says otherwise), mean over batch then over steps (:463-510, :412)."""
 
-    def __init__(self, forecaster: ARForecaster, datastore, standardize: bool = False, state_feature_weights=None):
+    def __init__(self, forecaster: ARForecaster, datastore, standardize: bool = False, state_feature_weights=None,
+                 loss: str = "wmse"):
         """``standardize=True`` makes ``forward`` start with ``on_after_batch_transfer`` (the batch arrives
         un-standardised, as ``WeatherDataset`` hands it over).  ``state_feature_weights``: per-variable loss weights
-        (``get_state_feature_weighting``, module.py:162-176 / loss_weighting.py); default = uniform ``1 / n``."""
+        (``get_state_feature_weighting``, module.py:162-176 / loss_weighting.py); default = uniform ``1 / n``.
+        ``loss``: the reference's ``--loss`` (train_model.py:271-276, ``metrics.get_metric``, module.py:226), one of
+        mse, mae, wmse, wmae, nll, crps_gauss (case-insensitive; ValueError otherwise).  The std of a loss is the model's
+        predicted std (output_std) or the per-variable ``diff_std / sqrt(weight)``; mse and mae ignore it, and with it
+        ``state_feature_weights``, because the reference replaces the std with ones."""
         super().__init__()
+        from ._lib import LOSS_KINDS, LOSS_WMSE
+
+        name = str(loss).lower()
+        if name not in LOSS_KINDS:
+            raise ValueError(f"unknown loss {loss!r}: expected one of {', '.join(LOSS_KINDS)}")
+        self.loss_name, self.loss_kind = name, LOSS_KINDS[name]
+        self.default_loss = self.loss_kind == LOSS_WMSE   # wmse keeps its own kernels (StepTailFunction, WmseLossFunction)
         self.forecaster = forecaster
         self.standardize_inputs = bool(standardize)
         bm = torch.tensor(datastore.boundary_mask.values, dtype=torch.float32)
@@ -721,6 +785,8 @@ class ForecasterStep(nn.Module):
             standardize = self.standardize_inputs
         if standardize:
             init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
+        if not self.default_loss:
+            return self._forward_loss(init_states, target_states, forcing)
         if (self.inv_var is not None and init_states.is_cuda and FUSED_STATE_UPDATE and isinstance(self.forecaster, ARForecaster)):
             # rollout with every step's state update + boundary overwrite + loss term in one pass (one more in backward)
             B, T = target_states.shape[0], target_states.shape[1]
@@ -739,3 +805,25 @@ class ForecasterStep(nn.Module):
             pred_std = self.per_var_std
         time_step_loss = torch.mean(wmse(prediction, target_states, pred_std, mask=self.interior_index), dim=0)
         return prediction, torch.mean(time_step_loss)
+
+    def _forward_loss(self, init_states, target_states, forcing):
+        """Every ``loss`` but wmse: the fused step tail (ops.StepTailLossFunction) where the predictor can return its raw delta,
+        the one-pass ops.LossFunction on the rollout otherwise (clamped or predicted-std models)."""
+        from ._lib import LOSS_MAE, LOSS_MSE
+        from .ops import LossFunction
+
+        if self.per_var_std is not None and init_states.is_cuda and FUSED_STATE_UPDATE and isinstance(self.forecaster, ARForecaster):
+            B, T = target_states.shape[0], target_states.shape[1]
+            prediction, pred_std, loss = self.forecaster(
+                init_states, forcing, target_states,
+                loss_spec=(target_states, self.per_var_std, self.interior_weight, 1.0 / (B * T), self.loss_kind))
+            if loss is not None:
+                return prediction, loss
+        else:
+            prediction, pred_std = self.forecaster(init_states, forcing, target_states)
+        if self.loss_kind in (LOSS_MSE, LOSS_MAE):   # the reference's std of ones: neither std is read
+            pred_std = None
+        elif pred_std is not None:
+            pred_std = pred_std.float()
+        return prediction, LossFunction.apply(prediction.float(), target_states.float(), pred_std,
+                                              self.per_var_std if pred_std is None else None, self.interior_weight, self.loss_kind)

@@ -2383,6 +2383,105 @@ class StepTailFunction(torch.autograd.Function):
         return d_delta, d_prev, None, None, None, None, None, None, None, None
 
 
+class LossFunction(torch.autograd.Function):
+    """``mean_t mean_b metrics.<kind>(pred, target, std, interior mask)`` as one pass each way (nlam_loss_fwd / _bwd) for every
+    ``--loss`` kind (``_lib.LOSS_*``).  The std is per entry (``pred_std``, an output_std model's prediction) or, with
+    ``pred_std=None``, per variable (``var_std`` (V,)); mse / mae read neither.
+
+    forward(pred (B, T, N, V), target, pred_std (B, T, N, V) | None, var_std (V) | None, row_weight (N) = interior / #interior,
+    kind) -> scalar.  Gradients: pred, and pred_std when it requires one."""
+
+    NPARTS = 512
+
+    @staticmethod
+    def _args(pred, target, pred_std, var_std, row_weight, kind, scale):
+        B, T, N, V = pred.shape
+        p = L.Loss()
+        p.pred, p.target, p.std = _ptr(pred), _ptr(target), _ptr(pred_std)
+        p.var_std, p.row_weight = _ptr(var_std), _ptr(row_weight)
+        p.rows, p.nodes, p.nvars, p.kind, p.scale = B * T * N, N, V, kind, scale
+        return p
+
+    @staticmethod
+    def forward(ctx, pred, target, pred_std, var_std, row_weight, kind: int):
+        lib = L.load()
+        _require_gpu(*(t for t in (pred, target, pred_std, var_std, row_weight) if t is not None))
+        B, T = pred.shape[0], pred.shape[1]
+        cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
+        pred, target, pred_std = map(cont, (pred, target, pred_std))
+        scale = 1.0 / (B * T)
+        p = LossFunction._args(pred, target, pred_std, var_std, row_weight, kind, scale)
+        partials = torch.empty((LossFunction.NPARTS,), device=pred.device, dtype=torch.float32)
+        p.partials, p.nparts = _ptr(partials), LossFunction.NPARTS
+        L.check(lib.nlam_loss_fwd(C.byref(p), _stream()), "nlam_loss_fwd")
+        out = torch.empty((), device=pred.device, dtype=torch.float32)
+        L.check(lib.nlam_reduce_partials(_ptr(partials), LossFunction.NPARTS, 1, 1, _ptr(out), 0, _stream()), "nlam_reduce_partials")
+        ctx.save_for_backward(pred, target, pred_std, var_std, row_weight)
+        ctx.kind, ctx.scale = kind, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        pred, target, pred_std, var_std, row_weight = ctx.saved_tensors
+        p = LossFunction._args(pred, target, pred_std, var_std, row_weight, ctx.kind, ctx.scale)
+        gc = g.contiguous().to(torch.float32)
+        dpred = torch.empty_like(pred)
+        dstd = torch.empty_like(pred_std) if pred_std is not None and ctx.needs_input_grad[2] else None
+        p.gscalar, p.dpred, p.dstd = _ptr(gc), _ptr(dpred), _ptr(dstd)
+        L.check(lib.nlam_loss_bwd(C.byref(p), _stream()), "nlam_loss_bwd")
+        return dpred, None, dstd, None, None, None
+
+
+class StepTailLossFunction(torch.autograd.Function):
+    """StepTailFunction with the loss term of any ``--loss`` kind (``_lib.LOSS_*``) for a per-variable std
+    (nlam_step_tail_loss_fwd / _bwd): still one pass each way per AR step.
+    forward(delta, prev, truth, target, dstd, dmean, bmask (N,), var_std (F,), row_weight (N,), scale, kind)
+    -> (pred (B, N, F), loss_t scalar)."""
+
+    NPARTS = 512
+
+    @staticmethod
+    def forward(ctx, delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale: float, kind: int):
+        lib = L.load()
+        _require_gpu(*(t for t in (delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight) if t is not None))
+        B, N, F = delta.shape
+        cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
+        delta, prev, truth, target = map(cont, (delta, prev, truth, target))
+        dev = delta.device
+        pred = torch.empty((B, N, F), device=dev, dtype=torch.float32)
+        partials = torch.empty((StepTailLossFunction.NPARTS,), device=dev, dtype=torch.float32)
+        L.check(lib.nlam_step_tail_loss_fwd(kind, _ptr(delta), _ptr(prev), _ptr(truth), _ptr(target), _ptr(dstd), _ptr(dmean),
+                                            _ptr(bmask), _ptr(var_std), _ptr(row_weight), scale, _ptr(pred), _ptr(partials),
+                                            StepTailLossFunction.NPARTS, B * N, N, F, _stream()), "nlam_step_tail_loss_fwd")
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        L.check(lib.nlam_reduce_partials(_ptr(partials), StepTailLossFunction.NPARTS, 1, 1, _ptr(loss), 0, _stream()),
+                "nlam_reduce_partials")
+        ctx.save_for_backward(pred, target, dstd, bmask, var_std, row_weight)
+        ctx.scale, ctx.kind = scale, kind
+        ctx.set_materialize_grads(False)
+        return pred, loss
+
+    @staticmethod
+    def backward(ctx, g_pred, g_loss):
+        lib = L.load()
+        pred, target, dstd, bmask, var_std, row_weight = ctx.saved_tensors
+        B, N, F = pred.shape
+        if g_pred is None and g_loss is None:
+            return (None,) * 11
+        dev = pred.device
+        gl = g_loss.contiguous().to(torch.float32) if g_loss is not None else torch.zeros((), device=dev, dtype=torch.float32)
+        gp = g_pred.contiguous() if g_pred is not None else None
+        d_delta = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        d_prev = torch.empty_like(pred) if ctx.needs_input_grad[1] else None
+        if d_delta is None and d_prev is None:
+            return (None,) * 11
+        L.check(lib.nlam_step_tail_loss_bwd(ctx.kind, _ptr(gp), _ptr(gl), _ptr(pred), _ptr(target), _ptr(dstd), _ptr(bmask),
+                                            _ptr(var_std), _ptr(row_weight), ctx.scale, _ptr(d_delta), _ptr(d_prev), B * N, N, F,
+                                            _stream()), "nlam_step_tail_loss_bwd")
+        return d_delta, d_prev, None, None, None, None, None, None, None, None, None
+
+
 class ConcatFunction(torch.autograd.Function):
     """``torch.cat(sources, dim=-1)`` of (B, N, w_k) rows in one launch (nlam_concat); a stride-0 batch (expand_to_batch)
     is read in place.  Backward: column slices of the incoming gradient (views)."""

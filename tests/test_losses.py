@@ -1,0 +1,365 @@
+"""The --loss choices of the reference (train_model.py:271-276, metrics.DEFINED_METRICS) on ForecasterStep(loss=...):
+construction, the C-ABI of nlam_loss_* / nlam_step_tail_loss_* without a GPU, the metric formulas of models.py against
+the reference golden (tests/golden/losses.pt, tests/golden/make_golden_losses.py), and on the GPU the kernels, the
+model training step per kind, the fused step tail against the unfused route, and HIP-graph capture."""
+import ctypes as C
+import subprocess
+
+import pytest
+import torch
+
+from conftest import ROOT, graph_from_case, load_golden, rel_err
+from neural_lam_amd import _lib as L
+
+KINDS = ["mse", "mae", "wmse", "wmae", "nll", "crps_gauss"]
+NEW_EXPORTS = ["nlam_loss_fwd", "nlam_loss_bwd", "nlam_step_tail_loss_fwd", "nlam_step_tail_loss_bwd"]
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return load_golden("losses")
+
+
+def _cases(groups):
+    """One dict per (input set, kind) out of the golden's groups (inputs once, the kinds' results stacked)."""
+    for grp in groups:
+        for i, kind in enumerate(grp["kinds"]):
+            yield {"kind": kind, "per_entry": grp["per_entry"], "pred": grp["pred"], "target": grp["target"], "std": grp["std"],
+                   "interior": grp["interior"], "ref_loss": grp["ref_loss"][i], "ref_dpred": grp["ref_dpred"][i],
+                   "ref_dstd": grp["ref_dstd"][i] if grp["per_entry"] else None}
+
+
+def _small_step_parts(tmp_path, **kw):
+    from neural_lam_amd import graph as G
+    from neural_lam_amd import models as hm
+    from neural_lam_amd.datastore import SyntheticDatastore
+
+    ds = SyntheticDatastore(30, 27, 5, 2, 1, root_path=tmp_path, boundary="random", seed=1)
+    ext = ds.get_xy_extent("state")
+    graph = G.normalise_graph(G.create_regular_grid_graph(ds.get_xy("state")), max(ext[1] - ext[0], ext[3] - ext[2]))
+    torch.manual_seed(1)
+    return ds, hm.ARForecaster(hm.GraphLAM(ds, graph=graph, **kw), ds)
+
+
+# ---------------------------------------------------------------------------
+# CPU
+# ---------------------------------------------------------------------------
+def test_forecaster_step_accepts_the_reference_loss_names(tmp_path):
+    from neural_lam_amd import models as hm
+
+    ds, fc = _small_step_parts(tmp_path, hidden_dim=8, processor_layers=1)
+    for name in KINDS + ["MSE", "Crps_Gauss", "WMAE", "Nll"]:
+        step = hm.ForecasterStep(fc, ds, loss=name)
+        assert step.loss_name == name.lower() and step.loss_kind == L.LOSS_KINDS[name.lower()]
+        assert step.per_var_std is not None   # the per-variable std is kept for every kind
+    assert hm.ForecasterStep(fc, ds).loss_name == "wmse"
+    with pytest.raises(ValueError, match="mse, mae, wmse, wmae, nll, crps_gauss"):
+        hm.ForecasterStep(fc, ds, loss="huber")
+
+
+def test_loss_entry_points_reject_bad_arguments_without_a_gpu():
+    assert set(NEW_EXPORTS) <= set(L.EXPORTS)
+    lib = L.load()
+    for name in NEW_EXPORTS:
+        assert hasattr(lib, name), name
+    assert [L.LOSS_KINDS[k] for k in KINDS] == [L.LOSS_MSE, L.LOSS_MAE, L.LOSS_WMSE, L.LOSS_WMAE, L.LOSS_NLL, L.LOSS_CRPS_GAUSS]
+    fake = 1 << 20   # never dereferenced: every call below must fail its argument checks before a launch
+
+    def args(**kw):
+        p = L.Loss()
+        p.pred = p.target = p.var_std = p.row_weight = p.partials = p.gscalar = p.dpred = fake
+        p.rows, p.nodes, p.nvars, p.kind, p.nparts, p.scale = 8, 4, 3, L.LOSS_NLL, 1, 1.0
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return C.byref(p)
+
+    for fn in (lib.nlam_loss_fwd, lib.nlam_loss_bwd):
+        assert fn(None, None) == -1
+        for bad in (dict(kind=0), dict(kind=7), dict(kind=-1), dict(rows=7), dict(rows=0), dict(nodes=0), dict(nvars=0),
+                    dict(pred=None), dict(target=None), dict(row_weight=None), dict(var_std=None)):
+            assert fn(args(**bad), None) == -1, (fn, bad)
+        assert fn(args(nvars=L.LOSS_MAX_VARS + 1), None) == -2   # the per-variable constants live in LDS
+    assert lib.nlam_loss_fwd(args(partials=None), None) == -1 and lib.nlam_loss_fwd(args(nparts=0), None) == -1
+    assert lib.nlam_loss_bwd(args(gscalar=None), None) == -1 and lib.nlam_loss_bwd(args(dpred=None), None) == -1
+    assert lib.nlam_loss_bwd(args(dstd=fake), None) == -1   # a std gradient needs a per-entry std
+
+    def fwd(kind, var_std=fake, rows=8, nodes=4, width=3, nparts=1):
+        return lib.nlam_step_tail_loss_fwd(kind, fake, fake, fake, fake, None, None, fake, var_std, fake, 1.0, fake, fake, nparts,
+                                           rows, nodes, width, None)
+
+    def bwd(kind, var_std=fake, rows=8, nodes=4, width=3, d_delta=fake):
+        return lib.nlam_step_tail_loss_bwd(kind, None, fake, fake, fake, None, fake, var_std, fake, 1.0, d_delta, None, rows, nodes,
+                                           width, None)
+
+    for call in (fwd, bwd):
+        assert call(0) == -1 and call(7) == -1
+        assert call(L.LOSS_WMAE, var_std=None) == -1 and call(L.LOSS_CRPS_GAUSS, rows=6) == -1 and call(L.LOSS_NLL, width=0) == -1
+        assert call(L.LOSS_NLL, width=L.LOSS_MAX_VARS + 1, rows=4, nodes=4) == -2
+    assert fwd(L.LOSS_MSE, nparts=0) == -1 and bwd(L.LOSS_MAE, d_delta=None) == -1
+
+
+def test_loss_struct_matches_c_layout(tmp_path):
+    src = tmp_path / "sz.c"
+    src.write_text(
+        '#include <stdio.h>\n#include <stddef.h>\n#include "nlam_hip.h"\n'
+        'int main(){printf("%zu %zu %zu %zu %zu %zu %d %d %d %d %d %d %d\\n", sizeof(nlam_loss_t), offsetof(nlam_loss_t, dstd),'
+        " offsetof(nlam_loss_t, rows), offsetof(nlam_loss_t, kind), offsetof(nlam_loss_t, scale), offsetof(nlam_loss_t, nparts),"
+        " NLAM_LOSS_MSE, NLAM_LOSS_MAE, NLAM_LOSS_WMSE, NLAM_LOSS_WMAE, NLAM_LOSS_NLL, NLAM_LOSS_CRPS_GAUSS, NLAM_LOSS_MAX_VARS);"
+        " return 0;}\n"
+    )
+    exe = tmp_path / "sz"
+    subprocess.run(["gcc", f"-I{ROOT / 'include'}", str(src), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [C.sizeof(L.Loss), L.Loss.dstd.offset, L.Loss.rows.offset, L.Loss.kind.offset, L.Loss.scale.offset,
+                   L.Loss.nparts.offset, *[L.LOSS_KINDS[k] for k in KINDS], L.LOSS_MAX_VARS]
+
+
+def test_model_metric_formulas_match_reference_golden(golden):
+    from neural_lam_amd import models as hm
+
+    assert set(hm.DEFINED_METRICS) == set(KINDS) and hm.get_metric("CRPS_Gauss") is hm.crps_gauss
+    with pytest.raises(ValueError):
+        hm.get_metric("huber")
+    for case in _cases(golden["elementwise"] + golden["ties"]):
+        pred = case["pred"].clone().requires_grad_()
+        std = case["std"].clone().requires_grad_()
+        loss = torch.mean(torch.mean(hm.get_metric(case["kind"])(pred, case["target"], std, mask=case["interior"]), dim=0))
+        loss.backward()
+        what = (case["kind"], case["per_entry"], tuple(pred.shape))
+        assert abs(float(loss.detach()) - float(case["ref_loss"])) <= 1e-6 * abs(float(case["ref_loss"])), what
+        assert rel_err(pred.grad, case["ref_dpred"]) <= 1e-6, what
+        if case["ref_dstd"] is not None:   # mse / mae do not read the std: no gradient, the golden holds zeros
+            assert rel_err(std.grad if std.grad is not None else torch.zeros_like(std), case["ref_dstd"]) <= 1e-6, what
+
+
+# ---------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    L.load()
+    return torch.device("cuda:0")
+
+
+def _misaligned(t):
+    """The same values at a 4-byte offset: a contiguous view whose data pointer is not 16-byte aligned."""
+    buf = torch.empty(t.numel() + 1, device=t.device, dtype=t.dtype)
+    view = buf[1:].view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def _run_loss(case, dev, misalign=False):
+    from neural_lam_amd.ops import LossFunction
+
+    put = (lambda t: _misaligned(t.to(dev))) if misalign else (lambda t: t.to(dev))
+    pred = put(case["pred"]).requires_grad_()
+    target = put(case["target"])
+    interior = case["interior"].to(torch.float32)
+    row_weight = (interior / interior.sum()).to(dev)
+    if case["per_entry"]:
+        std = put(case["std"]).requires_grad_()
+        loss = LossFunction.apply(pred, target, std, None, row_weight, L.LOSS_KINDS[case["kind"]])
+    else:
+        std = None
+        loss = LossFunction.apply(pred, target, None, case["std"].to(dev), row_weight, L.LOSS_KINDS[case["kind"]])
+    loss.backward()
+    return loss, pred.grad, (std.grad if std is not None else None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("misalign", [False, True])
+def test_loss_kernel_matches_reference_golden(dev, golden, misalign):
+    """nlam_loss_fwd / _bwd for every kind x std form: the 16-byte path (total a multiple of 4), the scalar path (not a
+    multiple of 4, or a misaligned slice), rows of weight 0 (boundary nodes)."""
+    for case in _cases(golden["elementwise"]):
+        loss, dpred, dstd = _run_loss(case, dev, misalign)
+        what = (case["kind"], case["per_entry"], tuple(case["pred"].shape), misalign)
+        assert abs(float(loss.detach()) - float(case["ref_loss"])) <= 1e-5 * abs(float(case["ref_loss"])), what
+        assert rel_err(dpred.cpu(), case["ref_dpred"]) <= 1e-5, what
+        boundary = ~case["interior"]
+        assert bool((dpred.cpu()[..., boundary, :] == 0).all()), what
+        if case["per_entry"]:
+            assert rel_err(dstd.cpu(), case["ref_dstd"]) <= 1e-5, what
+        else:
+            assert dstd is None
+
+
+@pytest.mark.gpu
+def test_absolute_error_gradient_is_zero_at_ties(dev, golden):
+    """sign(0) = 0 (torch.l1_loss): an interior entry with pred == target gets no gradient, in both kernels."""
+    from neural_lam_amd.ops import StepTailLossFunction
+
+    for case in _cases(golden["ties"]):
+        loss, dpred, _ = _run_loss(case, dev)
+        tie = (case["pred"] == case["target"]).to(dev)
+        assert int(tie.sum()) > 0
+        assert bool((dpred[tie] == 0).all()) and bool((dpred[~tie & case["interior"].to(dev)[:, None].expand_as(tie)] != 0).all())
+        assert rel_err(dpred.cpu(), case["ref_dpred"]) <= 1e-5
+        assert abs(float(loss.detach()) - float(case["ref_loss"])) <= 1e-5 * abs(float(case["ref_loss"]))
+    # the fused tail: delta = target - prev on every entry -> pred == target on the interior, the gradient is 0 there
+    B, N, F = 2, 40, 4
+    g = torch.Generator().manual_seed(3)
+    prev, target = torch.randn(B, N, F, generator=g).to(dev), torch.randn(B, N, F, generator=g).to(dev)
+    delta = (target - prev).requires_grad_()
+    bmask = (torch.rand(N, generator=g) < 0.3).float().to(dev)
+    rw = ((1 - bmask) / (1 - bmask).sum()).contiguous()
+    for kind in (L.LOSS_MAE, L.LOSS_WMAE):
+        delta.grad = None
+        pred, loss = StepTailLossFunction.apply(delta, prev, torch.zeros_like(prev), target, None, None, bmask,
+                                                torch.rand(F, device=dev) + 0.5, rw, 1.0 / B, kind)
+        ties = (pred == target) & (bmask == 0)[:, None]
+        assert int(ties.sum()) > 0
+        loss.backward()
+        assert bool((delta.grad[ties] == 0).all())
+
+
+def _golden_step(golden, model, kind, dev, tmp_path):
+    """The golden's model ("mean" / "std") on the datastore and graph of graphlam_30x27_variants, with its weights: the mean
+    model's own (flattened in the golden), the std model's = that golden's parameters (it lacks only the clamping)."""
+    from neural_lam_amd import models as hm
+    from neural_lam_amd.datastore import SyntheticDatastore
+
+    base, case = load_golden("graphlam_30x27_variants"), golden["models"][model]
+    ds = SyntheticDatastore(root_path=tmp_path, **base["ds_kwargs"])
+    fc = hm.ARForecaster(hm.GraphLAM(ds, graph=(base["ref_hierarchical"], graph_from_case(base)), **case["model_kwargs"]), ds)
+    names = case["param_names"]
+    assert [k for k, _ in fc.named_parameters()] == names
+    sd = fc.state_dict()
+    if "params" in case:
+        for k, v in zip(names, torch.split(case["params"], case["param_numels"])):
+            sd[k] = v.view_as(sd[k])
+    else:
+        sd.update({k: base["state_dict"][k] for k in names})
+    fc.load_state_dict(sd, strict=True)
+    T = golden["models"]["T"]
+    batch = [base["init"], base["target"][:, :T], base["forcing"][:, :T]]
+    return fc, hm.ForecasterStep(fc, ds, loss=kind).to(dev), [t.contiguous().to(dev) for t in batch]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model,kind", [("mean", k) for k in KINDS] + [("std", k) for k in ("nll", "crps_gauss")])
+def test_model_training_step_per_loss_matches_reference_golden(dev, golden, tmp_path, model, kind):
+    """ForecasterStep(loss=kind) against the reference's ARForecaster + metrics.<kind>: loss, prediction, every parameter
+    gradient (the norms of test_hip_parity.test_model_training_step_matches_reference_golden).  The mean model takes the fused
+    step tail (wmse: its own pair), the output_std model ops.LossFunction with its predicted std."""
+    case = golden["models"][model]
+    ref = case["kinds"][kind]
+    fc, step, batch = _golden_step(golden, model, kind, dev, tmp_path)
+    pred, loss = step(*batch)
+    assert rel_err(pred.cpu(), case["ref_prediction"]) < 1e-4
+    assert abs(float(loss.detach()) - float(ref["ref_loss"])) < 1e-4 * abs(float(ref["ref_loss"]))
+    loss.backward()
+    ref_grads = dict(zip(case["param_names"], torch.split(ref["ref_grads"], case["param_numels"])))
+    for k, p in fc.named_parameters():
+        ref_g = ref_grads[k].view_as(p)
+        got = p.grad if p.grad is not None else torch.zeros_like(p)
+        assert float((got.cpu() - ref_g).abs().max()) < 1e-4 * max(float(ref_g.abs().max()), 1e-3), (kind, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_fused_step_tail_matches_unfused_route(dev, golden, tmp_path, monkeypatch, kind):
+    """T = 3: the fused step tail (ops.StepTailLossFunction, no separate loss launch) against the unfused route
+    (FUSED_STATE_UPDATE off: the state update on its own, then ops.LossFunction over the rollout).  wmse keeps its own pair,
+    ops.StepTailFunction / ops.WmseLossFunction."""
+    from neural_lam_amd import models as hm
+    from neural_lam_amd import ops
+
+    def run(fused):
+        fc, step, (init, _, _) = _golden_step(golden, "mean", kind, dev, tmp_path)
+        N = init.shape[2]
+        g = torch.Generator().manual_seed(5)   # the same T = 3 batch for both routes
+        batch = [init, torch.randn(1, 3, N, 5, generator=g).to(dev), torch.randn(1, 3, N, 6, generator=g).to(dev)]
+        monkeypatch.setattr(hm, "FUSED_STATE_UPDATE", fused)
+        calls = {"loss": 0, "tail": 0}
+        names = ("WmseLossFunction", "StepTailFunction") if kind == "wmse" else ("LossFunction", "StepTailLossFunction")
+        for name, key in zip(names, ("loss", "tail")):
+            orig = getattr(ops, name).apply
+
+            def counted(*a, _orig=orig, _key=key):
+                calls[_key] += 1
+                return _orig(*a)
+
+            monkeypatch.setattr(getattr(ops, name), "apply", counted)
+        pred, loss = step(*batch)
+        loss.backward()
+        monkeypatch.undo()
+        return pred, loss, {k: p.grad.clone() for k, p in fc.named_parameters()}, calls
+
+    p1, l1, g1, c1 = run(True)
+    p0, l0, g0, c0 = run(False)
+    assert c1 == {"loss": 0, "tail": 3} and c0 == {"loss": 1, "tail": 0}
+    assert rel_err(p1.cpu(), p0.cpu()) < 1e-5
+    assert abs(float(l1) - float(l0)) < 1e-5 * abs(float(l0))
+    for k in g0:
+        assert float((g1[k] - g0[k]).abs().max()) < 1e-5 * max(float(g0[k].abs().max()), 1e-3), k
+
+
+@pytest.mark.gpu
+def test_hip_graph_step_equals_eager_step_with_nll(dev, tmp_path):
+    """Trainer(use_graph=True) with loss="nll" (the fused step tail) against the eager Trainer: three AdamW steps, bit for bit."""
+    from neural_lam_amd import models as hm
+    from neural_lam_amd.trainer import Trainer
+
+    def make(use_graph):
+        ds, fc = _small_step_parts(tmp_path, hidden_dim=16, processor_layers=2)
+        return ds, Trainer(hm.ForecasterStep(fc, ds, loss="nll").to(dev), lr=1e-3, use_graph=use_graph)
+
+    ds, t_eager = make(False)
+    _, t_graph = make(True)
+    N = ds.num_grid_points
+    g = torch.Generator().manual_seed(0)
+    for _ in range(3):
+        batch = [torch.randn(1, 2, N, 5, generator=g).to(dev), torch.randn(1, 2, N, 5, generator=g).to(dev),
+                 torch.randn(1, 2, N, 6, generator=g).to(dev)]
+        le, lg = float(t_eager.step(*batch)), float(t_graph.step(*batch))
+        assert le == lg
+        assert torch.equal(t_eager.fp.flat, t_graph.fp.flat) and torch.equal(t_eager.fp.grad, t_graph.fp.grad)
+    assert t_graph._graph is not None
+
+
+@pytest.mark.gpu
+def test_graphed_flat_step_equals_eager_with_crps_gauss_std_model(dev, tmp_path):
+    """graphed_training_step(flat=True) of an output_std model with loss="crps_gauss" (ops.LossFunction with the predicted std)
+    against the eager module: loss, prediction, every gradient and the weights after three AdamW steps, bit for bit."""
+    from neural_lam_amd import models as hm
+    from neural_lam_amd.trainer import graphed_training_step
+
+    kw = dict(hidden_dim=16, processor_layers=1, output_std=True, g2m_gnn_type="PropagationNet", m2g_gnn_type="PropagationNet",
+              mesh_aggr="mean")
+
+    def make():
+        ds, fc = _small_step_parts(tmp_path, **kw)
+        return ds, hm.ForecasterStep(fc, ds, loss="crps_gauss").to(dev)
+
+    ds, s_e = make()
+    _, s_g = make()
+    N = ds.num_grid_points
+    g = torch.Generator().manual_seed(0)
+
+    def batch():
+        return [torch.randn(1, 2, N, 5, generator=g).to(dev), torch.randn(1, 2, N, 5, generator=g).to(dev),
+                torch.randn(1, 2, N, 6, generator=g).to(dev)]
+
+    graphed = graphed_training_step(s_g, *batch(), flat=True)
+    leaf = graphed.flat_parameter
+    o_e = torch.optim.AdamW(s_e.parameters(), lr=1e-3, betas=(0.9, 0.95))
+    o_g = torch.optim.AdamW([leaf], lr=1e-3, betas=(0.9, 0.95))
+    for _ in range(3):
+        b = batch()
+        o_e.zero_grad(set_to_none=True)
+        pred_e, loss_e = s_e(*b)
+        loss_e.backward()
+        o_g.zero_grad(set_to_none=True)
+        pred_g, loss_g = graphed(*b)
+        loss_g.backward()
+        assert float(loss_e) == float(loss_g) and torch.equal(pred_e, pred_g)
+        for p, o in zip(s_e.parameters(), graphed.goffs):
+            assert torch.equal(p.grad.reshape(-1), leaf.grad[o : o + p.numel()])
+        o_e.step()
+        o_g.step()
+        for a, c in zip(s_e.parameters(), s_g.parameters()):
+            assert torch.equal(a, c)
