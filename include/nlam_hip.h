@@ -44,6 +44,9 @@
  *       the other losses of --loss (train_model.py:271-276): metrics.mse / mae / wmae / nll / crps_gauss
  *       (and wmse), per-variable or per-entry (predicted) std, the same reduction; the step-tail pair fuses
  *       them into the AR step's state update as nlam_step_tail_* does for wmse.
+ *   nlam_eval_metrics, nlam_eval_workspace_floats
+ *       the evaluation tensors of validation_step / test_step (models/module.py:546-576, :607-681): per-step loss,
+ *       per-variable masked MSE / MAE / mean std, per-node loss maps; one pass over the rollout + a fixed-order reduction.
  *   nlam_reduce_partials
  *       deterministic second stage of the per-workgroup partial sums.
  *   nlam_adamw_step
@@ -588,6 +591,47 @@ int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* p
 int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target,
                                 const float* dstd, const float* bmask, const float* var_std, const float* row_weight, float scale,
                                 float* d_delta, float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream);
+
+/* The evaluation metrics of validation_step / test_step (models/module.py:491-504, :546-576, :607-681) over a rollout,
+ * pred / target / std (batch * steps * nodes, nvars) fp32, with "masked grid mean" = sum_n row_weight[n] * x (row_weight =
+ * interior / #interior: mask_and_reduce_metric, metrics.py:37-84).  The entry of `kind` is that of nlam_loss_fwd, with the
+ * same std rules (mse / mae read no std; `std` per entry, else `var_std` per variable).  Every output may be NULL:
+ *   step_loss (batch, steps)        masked grid mean of sum_v entry                 (the time_step_loss before its batch mean)
+ *   sq        (batch, steps, nvars) masked grid mean of (pred - target)^2           (metrics.mse, sum_vars=False)
+ *   ab        (batch, steps, nvars) masked grid mean of |pred - target|             (metrics.mae, sum_vars=False)
+ *   std_mean  (batch, steps, nvars) masked grid mean of the per-entry std           (needs `std`)
+ *   maps      (batch, nmaps, nodes) sum_v entry at lead time map_steps[s], NaN where row_weight[n] == 0 (the spatial loss)
+ * Two launches: workgroups own (batch, step, node chunk) and write per-variable partial sums into `workspace` (at least
+ * nlam_eval_workspace_floats(batch, steps, nodes, nvars) floats) and the maps directly; a second kernel adds the chunks in a
+ * fixed order (bit-identical run to run).  No allocation, no host synchronisation.  NLAM_EINVAL (before any launch) for null
+ * required pointers, sizes < 1, an unknown kind, a missing std, map steps outside [0, steps) or a short workspace;
+ * NLAM_EUNSUP for nvars > NLAM_EVAL_MAX_VARS or nmaps > NLAM_EVAL_MAX_MAPS. */
+#define NLAM_EVAL_MAX_MAPS 32
+#define NLAM_EVAL_MAX_VARS 256   /* a workgroup keeps every variable's sums in registers (4 per thread, period 4 * nvars) */
+typedef struct {
+    const float* pred;         /* (batch * steps * nodes, nvars) */
+    const float* target;       /* (batch * steps * nodes, nvars) */
+    const float* std;          /* (batch * steps * nodes, nvars) per-entry std, or NULL */
+    const float* var_std;      /* (nvars) per-variable std, read when std == NULL (may be NULL for mse / mae) */
+    const float* row_weight;   /* (nodes) interior mask / #interior nodes */
+    float* workspace;          /* (workspace_floats) */
+    float* step_loss;          /* (batch, steps) or NULL */
+    float* sq;                 /* (batch, steps, nvars) or NULL */
+    float* ab;                 /* (batch, steps, nvars) or NULL */
+    float* std_mean;           /* (batch, steps, nvars) or NULL */
+    float* maps;               /* (batch, nmaps, nodes), or NULL when nmaps == 0 */
+    int64_t workspace_floats;
+    int32_t batch;
+    int32_t steps;
+    int32_t nodes;
+    int32_t nvars;
+    int32_t kind;              /* NLAM_LOSS_* */
+    int32_t nmaps;
+    int32_t map_steps[NLAM_EVAL_MAX_MAPS];   /* 0-based lead-time indices, [0, nmaps) used */
+} nlam_eval_t;
+int32_t nlam_eval_metrics(const nlam_eval_t* p, void* hip_stream);
+/* floats of nlam_eval_t.workspace for these sizes; -1 (NLAM_EINVAL) for sizes < 1 */
+int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, int32_t nvars);
 
 /* Row-wise concatenation of up to NLAM_MAX_CAT sources into out (rows, sum of widths): the torch.cat of the grid input
  * features (prev_state, prev_prev_state, forcing, static features; step_predictors/graph/base.py:275-283).  A source

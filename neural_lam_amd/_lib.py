@@ -40,6 +40,8 @@ TILE_SPLIT = 1 << 30
 LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
 LOSS_MSE, LOSS_MAE, LOSS_WMSE, LOSS_WMAE, LOSS_NLL, LOSS_CRPS_GAUSS = 1, 2, 3, 4, 5, 6
 LOSS_MAX_VARS = 4096
+EVAL_MAX_MAPS = 32    # NLAM_EVAL_MAX_MAPS: lead times of one nlam_eval_metrics call's loss maps
+EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
 
 EXPORTS = [
     "nlam_abi_version",
@@ -89,6 +91,8 @@ EXPORTS = [
     "nlam_loss_bwd",
     "nlam_step_tail_loss_fwd",
     "nlam_step_tail_loss_bwd",
+    "nlam_eval_metrics",
+    "nlam_eval_workspace_floats",
     "nlam_concat",
     "nlam_window_len",
     "nlam_window_batch",
@@ -298,6 +302,30 @@ class Loss(C.Structure):
     ]
 
 
+class Eval(C.Structure):
+    _fields_ = [
+        ("pred", C.c_void_p),
+        ("target", C.c_void_p),
+        ("std", C.c_void_p),
+        ("var_std", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("step_loss", C.c_void_p),
+        ("sq", C.c_void_p),
+        ("ab", C.c_void_p),
+        ("std_mean", C.c_void_p),
+        ("maps", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("batch", C.c_int32),
+        ("steps", C.c_int32),
+        ("nodes", C.c_int32),
+        ("nvars", C.c_int32),
+        ("kind", C.c_int32),
+        ("nmaps", C.c_int32),
+        ("map_steps", C.c_int32 * EVAL_MAX_MAPS),
+    ]
+
+
 class StdJob(C.Structure):
     _fields_ = [
         ("x", C.c_void_p),
@@ -430,6 +458,10 @@ def load():
     lib.nlam_step_tail_loss_fwd.restype = i32
     lib.nlam_step_tail_loss_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.nlam_step_tail_loss_bwd.restype = i32
+    lib.nlam_eval_metrics.argtypes = [C.POINTER(Eval), vp]
+    lib.nlam_eval_metrics.restype = i32
+    lib.nlam_eval_workspace_floats.argtypes = [i32, i32, i32, i32]
+    lib.nlam_eval_workspace_floats.restype = i64
     lib.nlam_concat.argtypes = [C.POINTER(Cat), vp]
     lib.nlam_concat.restype = i32
     lib.nlam_window_len.argtypes = [i64, i64, i32, i32, i32]

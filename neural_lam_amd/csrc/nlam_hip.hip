@@ -3708,6 +3708,158 @@ __global__ __launch_bounds__(256) void step_tail_loss_bwd_kernel(const float* __
     }
 }
 
+// ---------------------------------------------------------------------------
+// evaluation metrics (nlam_eval_metrics): the per-step loss, per-variable masked MSE / MAE / mean std and the per-node loss
+// maps of validation_step / test_step in one pass over the rollout.  A workgroup owns (batch, step, node chunk); its lanes
+// take 16-byte quads of the chunk with a stride of 4 * lanes elements, lanes a multiple of nvars, so every lane sees the
+// same four variables at every stride: their sums stay in registers and meet in LDS once, in a fixed order.
+// ---------------------------------------------------------------------------
+constexpr int kEvalChunkElems = 8192;   // elements per workgroup (rounded to whole nodes, a multiple of 4 of them)
+
+__host__ __device__ __forceinline__ int eval_chunk_nodes(int nvars) { return ((kEvalChunkElems / nvars + 3) / 4) * 4; }
+
+__host__ __device__ __forceinline__ int eval_lanes(int nvars) { return (256 / nvars) * nvars; }
+
+// workspace[(bt * nchunks + chunk) * (3 * nvars + 1) + j]: j = 0 the weighted loss, then sq[nvars], ab[nvars], std[nvars]
+template <int KIND, bool PER_ENTRY>
+__global__ __launch_bounds__(256) void eval_partials_kernel(const nlam_eval_t p, int nchunks) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int F = p.nvars, N = p.nodes;
+    const int lanes = eval_lanes(F), W = 4 * lanes, rows_per_iter = W / F;
+    float2* lc = reinterpret_cast<float2*>(smem);                  // [F] (c0, c1) of a per-variable std
+    float* acc = smem + ((2 * F + 3) & ~3);                        // [3][W] the lanes' sums; [W] entries of one stride for the maps
+    float* red = acc + 3 * W;                                      // [4]
+    if constexpr (!PER_ENTRY) stage_loss_consts<KIND>(p.var_std, F, lc);
+    const int bt = blockIdx.x / nchunks, chunk = blockIdx.x - bt * nchunks;
+    const int t = bt % p.steps, b = bt / p.steps;
+    const int n0 = chunk * eval_chunk_nodes(F), n1 = min(N, n0 + eval_chunk_nodes(F));
+    const long base = ((long)bt * N + n0) * F;
+    const int cnt = (n1 - n0) * F;
+    const float* pp = p.pred + base;
+    const float* tp = p.target + base;
+    const float* sp = PER_ENTRY ? p.std + base : nullptr;
+    const bool vec = ((reinterpret_cast<uintptr_t>(pp) | reinterpret_cast<uintptr_t>(tp) | reinterpret_cast<uintptr_t>(sp)) & 15) == 0;
+    bool map = false;
+    for (int s = 0; s < p.nmaps; ++s) map |= p.map_steps[s] == t;
+    const int tid = threadIdx.x;
+    const bool active = tid < lanes;
+    float c0[4], c1[4];
+    int row0[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int f = (4 * tid + k) % F;
+        row0[k] = (4 * tid + k) / F;
+        c0[k] = c1[k] = 0.f;
+        if constexpr (!PER_ENTRY) {
+            const float2 c = lc[f];
+            c0[k] = c.x;
+            c1[k] = c.y;
+        }
+    }
+    float lsum = 0.f, sq[4] = {0.f, 0.f, 0.f, 0.f}, ab[4] = {0.f, 0.f, 0.f, 0.f}, sd[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it * W < cnt; ++it) {
+        const int e = it * W + 4 * tid;
+        if (active && e < cnt) {
+            f32x4 pv = {0.f, 0.f, 0.f, 0.f}, tv = {0.f, 0.f, 0.f, 0.f}, sv = {0.f, 0.f, 0.f, 0.f};
+            if (vec && e + 3 < cnt) {
+                pv = *reinterpret_cast<const f32x4*>(pp + e);
+                tv = *reinterpret_cast<const f32x4*>(tp + e);
+                if constexpr (PER_ENTRY) sv = *reinterpret_cast<const f32x4*>(sp + e);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (e + k < cnt) {
+                        pv[k] = pp[e + k];
+                        tv[k] = tp[e + k];
+                        if constexpr (PER_ENTRY) sv[k] = sp[e + k];
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (e + k < cnt) {
+                    const float w = p.row_weight[n0 + row0[k] + it * rows_per_iter];
+                    const float d = pv[k] - tv[k];
+                    float k0 = c0[k], k1 = c1[k];
+                    if constexpr (PER_ENTRY) loss_consts<KIND>(sv[k], k0, k1);
+                    const float ent = loss_entry<KIND>(d, k0, k1);
+                    if (w != 0.f) {
+                        lsum += w * ent;
+                        sq[k] += w * (d * d);
+                        ab[k] += w * fabsf(d);
+                        if constexpr (PER_ENTRY) sd[k] += w * sv[k];
+                    }
+                    if (map) acc[4 * tid + k] = ent;
+                }
+            }
+        }
+        if (map) {   // block-uniform: this lead time is one of the map steps
+            __syncthreads();
+            for (int r = tid; r < rows_per_iter; r += blockDim.x) {
+                const int n = n0 + it * rows_per_iter + r;
+                if (n < n1) {
+                    float v = 0.f;
+                    for (int f = 0; f < F; ++f) v += acc[r * F + f];
+                    if (p.row_weight[n] == 0.f) v = __builtin_nanf("");
+                    for (int s = 0; s < p.nmaps; ++s)
+                        if (p.map_steps[s] == t) p.maps[((long)b * p.nmaps + s) * N + n] = v;
+                }
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = lsum;
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            acc[4 * tid + k] = sq[k];
+            acc[W + 4 * tid + k] = ab[k];
+            acc[2 * W + 4 * tid + k] = sd[k];
+        }
+    }
+    __syncthreads();
+    float* out = p.workspace + (long)blockIdx.x * (3 * F + 1);
+    if (tid == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    for (int j = tid; j < 3 * F; j += blockDim.x) {   // j = q * F + f: the lanes' sums of variable f, in slot order
+        const int q = j / F, f = j - q * F;
+        float v = 0.f;
+        for (int i = f; i < W; i += F) v += acc[q * W + i];
+        out[1 + j] = v;
+    }
+}
+
+// the chunks of one (batch, step) per workgroup into the requested outputs: lane -> column of the partials, the four waves
+// split the chunks (eight loads in flight each), combined in wave order (fixed summation order: deterministic)
+__global__ __launch_bounds__(256) void eval_finish_kernel(const nlam_eval_t p, int nchunks) {
+    __shared__ float red[4][64];
+    const int F = p.nvars, width = 3 * F + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long bt = blockIdx.x;
+    const int per = (nchunks + 3) / 4, c0 = wave * per, c1 = min(nchunks, c0 + per);
+    for (int j0 = 0; j0 < width; j0 += 64) {
+        const int j = j0 + lane;
+        float v = 0.f;
+        if (j < width) {
+            const float* src = p.workspace + bt * nchunks * width + j;
+#pragma unroll 8
+            for (int c = c0; c < c1; ++c) v += src[(long)c * width];
+        }
+        red[wave][lane] = v;
+        __syncthreads();
+        if (wave == 0 && j < width) {
+            float* dst;
+            if (j == 0) dst = p.step_loss != nullptr ? p.step_loss + bt : nullptr;
+            else if (j <= F) dst = p.sq != nullptr ? p.sq + bt * F + (j - 1) : nullptr;
+            else if (j <= 2 * F) dst = p.ab != nullptr ? p.ab + bt * F + (j - 1 - F) : nullptr;
+            else dst = p.std_mean != nullptr ? p.std_mean + bt * F + (j - 1 - 2 * F) : nullptr;
+            if (dst != nullptr) *dst = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+        }
+        __syncthreads();
+    }
+}
+
 // row-wise concatenation (nlam_concat): a workgroup owns 64 consecutive rows; every source's 64 x w_k block is one
 // contiguous span in memory (read coalesced into the LDS row image), and so is the 64 x wtot output block
 constexpr int kCatRows = 64;
@@ -6373,6 +6525,37 @@ void step_tail_loss_bwd_launch(const float* g_pred, const float* gloss, const fl
                        stream, g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, total, nodes,
                        width);
 }
+
+// nlam_eval_metrics: the chunks of a (batch, step) and the argument checks (before any launch)
+long eval_nchunks(int32_t nodes, int32_t nvars) { return (nodes + eval_chunk_nodes(nvars) - 1) / eval_chunk_nodes(nvars); }
+
+int32_t eval_check(const nlam_eval_t* p) {
+    if (p == nullptr) return NLAM_EINVAL;
+    if (p->nvars > NLAM_EVAL_MAX_VARS || p->nmaps > NLAM_EVAL_MAX_MAPS) return NLAM_EUNSUP;
+    if (!loss_kind_valid(p->kind) || p->pred == nullptr || p->target == nullptr || p->row_weight == nullptr ||
+        p->workspace == nullptr)
+        return NLAM_EINVAL;
+    if (p->batch < 1 || p->steps < 1 || p->nodes < 1 || p->nvars < 1 || p->nmaps < 0) return NLAM_EINVAL;
+    if (loss_reads_std(p->kind) && p->std == nullptr && p->var_std == nullptr) return NLAM_EINVAL;
+    if (p->std_mean != nullptr && p->std == nullptr) return NLAM_EINVAL;
+    if (p->nmaps > 0 && p->maps == nullptr) return NLAM_EINVAL;
+    for (int s = 0; s < p->nmaps; ++s)
+        if (p->map_steps[s] < 0 || p->map_steps[s] >= p->steps) return NLAM_EINVAL;
+    const long blocks = (long)p->batch * p->steps * eval_nchunks(p->nodes, p->nvars);
+    if (blocks > 0x7fffffffL || p->workspace_floats < blocks * (3L * p->nvars + 1)) return NLAM_EINVAL;
+    return 0;
+}
+
+template <int KIND>
+int32_t eval_launch(const nlam_eval_t& p, hipStream_t stream) {
+    const int nchunks = (int)eval_nchunks(p.nodes, p.nvars);
+    const long blocks = (long)p.batch * p.steps * nchunks;
+    const size_t lds = (size_t)(((2 * p.nvars + 3) & ~3) + 3 * 4 * eval_lanes(p.nvars) + 4) * sizeof(float);
+    if (p.std != nullptr) hipLaunchKernelGGL((eval_partials_kernel<KIND, true>), dim3((unsigned)blocks), dim3(256), lds, stream, p, nchunks);
+    else hipLaunchKernelGGL((eval_partials_kernel<KIND, false>), dim3((unsigned)blocks), dim3(256), lds, stream, p, nchunks);
+    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)(p.batch * p.steps)), dim3(256), 0, stream, p, nchunks);
+    return (int32_t)hipGetLastError();
+}
 }  // namespace
 #endif
 
@@ -6727,6 +6910,21 @@ int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* 
     NLAM_LOSS_SWITCH(kind, NLAM_STL_BWD)
 #undef NLAM_STL_BWD
     return (int32_t)hipGetLastError();
+}
+
+int32_t nlam_eval_metrics(const nlam_eval_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_eval_metrics");
+    if (const int32_t rc = eval_check(p)) return rc;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+#define NLAM_EVAL(K) return eval_launch<K>(*p, stream)
+    NLAM_LOSS_SWITCH(p->kind, NLAM_EVAL)
+#undef NLAM_EVAL
+    return NLAM_EINVAL;
+}
+
+int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, int32_t nvars) {
+    if (batch < 1 || steps < 1 || nodes < 1 || nvars < 1 || nvars > NLAM_EVAL_MAX_VARS) return NLAM_EINVAL;
+    return (int64_t)batch * steps * eval_nchunks(nodes, nvars) * (3L * nvars + 1);
 }
 #undef NLAM_LOSS_SWITCH
 

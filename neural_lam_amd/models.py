@@ -16,6 +16,7 @@ Reference -> here (same class / argument / attribute / parameter names):
   wmse               metrics.py:37-137
   mse .. get_metric  metrics.py:10-34, 140-394 (mse, mae, wmae, nll, crps_gauss: evaluation formulas)
   ForecasterStep     the training_step / loss / AdamW lines of models/module.py:293-304, 326-417, 463-510
+  ForecasterStep.evaluate  validation_step / test_step, models/module.py:546-576, 607-681 (epoch ends: evaluation.py)
 
 Differences that do not change results: the graph may be handed in pre-loaded
 (``graph=``) instead of being read from ``datastore.root_path``; the
@@ -698,6 +699,26 @@ def get_metric(metric_name):
     return DEFINED_METRICS[name]
 
 
+class EvalResult:
+    """What ``ForecasterStep.evaluate`` returns (device tensors; B = batch, T = rollout, F = state variables, S = map steps):
+    ``prediction`` (B, T, N, F), ``time_step_loss`` (T,), ``mean_loss`` (), ``entry_mse`` (B, T, F), and for phase "test"
+    ``entry_mae`` (B, T, F), ``spatial_loss`` (B, S, N) at the 1-based ``map_steps`` (NaN off the interior) and, for a model
+    that predicts its std, ``output_std`` (B, T, F); None where the phase does not produce it."""
+
+    __slots__ = ("phase", "prediction", "time_step_loss", "mean_loss", "entry_mse", "entry_mae", "spatial_loss", "output_std",
+                 "map_steps")
+
+    def __init__(self, phase, prediction, time_step_loss, mean_loss, entry_mse, entry_mae=None, spatial_loss=None,
+                 output_std=None, map_steps=()):
+        self.phase, self.prediction, self.time_step_loss, self.mean_loss = phase, prediction, time_step_loss, mean_loss
+        self.entry_mse, self.entry_mae, self.spatial_loss, self.output_std = entry_mse, entry_mae, spatial_loss, output_std
+        self.map_steps = tuple(map_steps)
+
+    @property
+    def batch_size(self):
+        return self.prediction.shape[0]
+
+
 class ForecasterStep(nn.Module):
     """The training_step / loss lines of ``ForecasterModule`` (models/module.py)
     without Lightning: on-device standardisation (:326-367), rollout + masked
@@ -827,3 +848,31 @@ class ForecasterStep(nn.Module):
             pred_std = pred_std.float()
         return prediction, LossFunction.apply(prediction.float(), target_states.float(), pred_std,
                                               self.per_var_std if pred_std is None else None, self.interior_weight, self.loss_kind)
+
+    def evaluate(self, init_states, target_states, forcing, phase="val", steps_to_log=(1,), standardize=None):
+        """``validation_step`` (phase "val", models/module.py:546-576) or ``test_step`` ("test", :607-681) without Lightning:
+        the rollout under ``torch.no_grad()``, then every metric of the step in one ``nlam_eval_metrics`` pass (ops.eval_metrics)
+        with this step's ``loss`` and its std.  ``steps_to_log``: the 1-based lead times of the test loss maps
+        (``val_steps_to_log``); those beyond the rollout are skipped, as in the reference.  No host synchronisation and no
+        data-dependent shape: the call can be captured (trainer.graphed_eval_step).  Returns an ``EvalResult``."""
+        from .ops import eval_metrics
+
+        if phase not in ("val", "test"):
+            raise ValueError(f"evaluate: phase must be 'val' or 'test', got {phase!r}")
+        with torch.no_grad():
+            if standardize is None:
+                standardize = self.standardize_inputs
+            if standardize:
+                init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
+            prediction, pred_std = self.forecaster(init_states, forcing, target_states)
+            prediction = prediction.float().contiguous()
+            if pred_std is not None:
+                pred_std = pred_std.float().contiguous()
+            T = prediction.shape[1]
+            test = phase == "test"
+            map_steps = tuple(int(k) for k in steps_to_log if int(k) <= T) if test else ()
+            m = eval_metrics(prediction, target_states.float().contiguous(), pred_std, self.per_var_std, self.interior_weight,
+                             self.loss_kind, [k - 1 for k in map_steps], want_mae=test, want_std=test and pred_std is not None)
+            time_step_loss = torch.mean(m["step_loss"], dim=0)
+            return EvalResult(phase, prediction, time_step_loss, torch.mean(time_step_loss), m["sq"], m.get("ab"), m.get("maps"),
+                              m.get("std_mean"), map_steps)

@@ -2482,6 +2482,75 @@ class StepTailLossFunction(torch.autograd.Function):
         return d_delta, d_prev, None, None, None, None, None, None, None, None, None
 
 
+def eval_metrics(pred, target, pred_std, var_std, interior_weight, kind, map_steps=(), want_mae=False, want_std=False):
+    """The evaluation tensors of ``validation_step`` / ``test_step`` (models/module.py:491-504, :546-576, :607-681) in one pass
+    over the rollout and a fixed-order reduction (nlam_eval_metrics): no autograd, no host synchronisation (capturable).
+
+    pred, target (B, T, N, F) fp32; pred_std (B, T, N, F) per-entry std (bf16 / fp16 under autocast is widened) or None;
+    var_std (F,) the per-variable std, read when pred_std is None (mse / mae read neither); interior_weight (N,) = interior /
+    #interior; kind a ``_lib.LOSS_*`` value or its name; map_steps 0-based lead times < T of the loss maps.  Returns a dict of
+    device tensors: ``step_loss`` (B, T) and ``sq`` (B, T, F) always, ``ab`` (B, T, F) with ``want_mae``, ``std_mean`` (B, T, F)
+    with ``want_std`` (needs pred_std), ``maps`` (B, len(map_steps), N) when map_steps is not empty (NaN off the interior)."""
+    lib = L.load()
+    if isinstance(kind, str):
+        if kind.lower() not in L.LOSS_KINDS:
+            raise ValueError(f"eval_metrics: unknown loss kind {kind!r}")
+        kind = L.LOSS_KINDS[kind.lower()]
+    if kind not in L.LOSS_KINDS.values():
+        raise ValueError(f"eval_metrics: unknown loss kind {kind!r}")
+    if pred.dim() != 4 or target.shape != pred.shape:
+        raise ValueError(f"eval_metrics: pred {tuple(pred.shape)} and target {tuple(target.shape)} must both be (B, T, N, F)")
+    B, T, N, F = pred.shape
+    if pred_std is not None and pred_std.dtype in (torch.bfloat16, torch.float16):
+        pred_std = pred_std.float()   # an output_std head under autocast
+    reads_std = kind not in (L.LOSS_MSE, L.LOSS_MAE)
+    std = pred_std if (reads_std or want_std) else None
+    vstd = var_std if (reads_std and std is None) else None
+    if reads_std and std is None and vstd is None:
+        raise ValueError("eval_metrics: this loss kind needs pred_std or var_std")
+    if want_std and pred_std is None:
+        raise ValueError("eval_metrics: want_std needs a per-entry pred_std")
+    checks = [("pred", pred, (B, T, N, F)), ("target", target, (B, T, N, F)), ("interior_weight", interior_weight, (N,))]
+    if std is not None:
+        checks.append(("pred_std", std, (B, T, N, F)))
+    if vstd is not None:
+        checks.append(("var_std", vstd, (F,)))
+    for name, t, shape in checks:
+        if not t.is_cuda or t.device != pred.device:
+            raise ValueError(f"eval_metrics: {name} must be on the GPU of pred ({pred.device}), got {t.device}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"eval_metrics: {name} must be fp32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"eval_metrics: {name} must be contiguous")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"eval_metrics: {name} has shape {tuple(t.shape)}, expected {shape}")
+    if F > L.EVAL_MAX_VARS:
+        raise ValueError(f"eval_metrics: at most {L.EVAL_MAX_VARS} variables, got {F}")
+    map_steps = [int(s) for s in map_steps]
+    if len(map_steps) > L.EVAL_MAX_MAPS or any(s < 0 or s >= T for s in map_steps):
+        raise ValueError(f"eval_metrics: map_steps {map_steps} must be at most {L.EVAL_MAX_MAPS} lead times in [0, {T})")
+    dev = pred.device
+    nws = int(lib.nlam_eval_workspace_floats(B, T, N, F))
+    workspace = torch.empty((nws,), device=dev, dtype=torch.float32)
+    out = {"step_loss": torch.empty((B, T), device=dev, dtype=torch.float32),
+           "sq": torch.empty((B, T, F), device=dev, dtype=torch.float32)}
+    if want_mae:
+        out["ab"] = torch.empty((B, T, F), device=dev, dtype=torch.float32)
+    if want_std:
+        out["std_mean"] = torch.empty((B, T, F), device=dev, dtype=torch.float32)
+    if map_steps:
+        out["maps"] = torch.empty((B, len(map_steps), N), device=dev, dtype=torch.float32)
+    p = L.Eval()
+    p.pred, p.target, p.std, p.var_std, p.row_weight = _ptr(pred), _ptr(target), _ptr(std), _ptr(vstd), _ptr(interior_weight)
+    p.workspace, p.workspace_floats = _ptr(workspace), nws
+    p.step_loss, p.sq, p.ab, p.std_mean, p.maps = (_ptr(out.get(k)) for k in ("step_loss", "sq", "ab", "std_mean", "maps"))
+    p.batch, p.steps, p.nodes, p.nvars, p.kind, p.nmaps = B, T, N, F, kind, len(map_steps)
+    for i, s in enumerate(map_steps):
+        p.map_steps[i] = s
+    L.check(lib.nlam_eval_metrics(C.byref(p), _stream()), "nlam_eval_metrics")
+    return out
+
+
 class ConcatFunction(torch.autograd.Function):
     """``torch.cat(sources, dim=-1)`` of (B, N, w_k) rows in one launch (nlam_concat); a stride-0 batch (expand_to_batch)
     is read in place.  Backward: column slices of the incoming gradient (views)."""

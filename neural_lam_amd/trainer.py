@@ -1072,6 +1072,67 @@ class _GraphedStep:
         return out if len(out) > 1 else out[0]
 
 
+class _GraphedEval:
+    """See ``graphed_eval_step``."""
+
+    def __init__(self, step, sample_args, phase, steps_to_log, warmup):
+        import gc
+
+        if not all(isinstance(a, torch.Tensor) and a.is_cuda for a in sample_args):
+            raise ValueError("graphed_eval_step: the sample arguments must be tensors on the GPU")
+        if phase not in ("val", "test"):
+            raise ValueError(f"graphed_eval_step: phase must be 'val' or 'test', got {phase!r}")
+        self.step, self.phase, self.steps_to_log = step, phase, tuple(steps_to_log)
+        self.static_in = [a.detach().clone() for a in sample_args]
+        self.sig = [(tuple(a.shape), a.dtype) for a in sample_args]
+        self.autocast = (torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda"))
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):   # eager passes first: lazy layouts, LDS attributes, allocator state
+            for _ in range(max(1, warmup)):
+                step.evaluate(*self.static_in, phase=phase, steps_to_log=self.steps_to_log)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        gc.collect()
+        was_enabled = gc.isenabled()
+        gc.disable()   # a CUDAGraph destructor synchronises the device: never inside a capture (see Trainer._capture)
+        try:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self.static_out = step.evaluate(*self.static_in, phase=phase, steps_to_log=self.steps_to_log)
+        finally:
+            if was_enabled:
+                gc.enable()
+
+    def __call__(self, *args):
+        sig = [(tuple(a.shape), a.dtype) for a in args]
+        ac = (torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda"))
+        if sig != self.sig or ac[0] != self.autocast[0] or (ac[0] and ac[1] != self.autocast[1]):
+            return self.step.evaluate(*args, phase=self.phase, steps_to_log=self.steps_to_log)   # another shape: eager launches
+        for dst, src in zip(self.static_in, args):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src)
+        self.graph.replay()
+        return self.static_out
+
+
+def graphed_eval_step(forecaster_step, init, target, forcing, phase="val", steps_to_log=(1,), warmup: int = 2):
+    """``forecaster_step.evaluate(batch, phase, steps_to_log)`` (the rollout plus every metric of ``validation_step`` /
+    ``test_step``) as a callable that replays ONE captured HIP graph:
+
+        val_step = graphed_eval_step(forecaster_step, init, target, forcing, phase="val")   # once, on a sample batch
+        ...
+        def validation_step(self, batch, batch_idx):                                        # LightningModule
+            self.val_agg.update(val_step(*batch))
+
+    The contract of ``graphed_training_step``: static input and output buffers -- the returned ``EvalResult`` is the same
+    object on every call and its tensors are overwritten by the next one (``evaluation.MetricAggregator.update`` copies what
+    it keeps) -- and a batch of another shape, dtype or autocast state falls through to the eager ``evaluate``.  The graph
+    reads the module's parameters where they are at capture time, so training between replays (in-place optimizer steps)
+    is seen by the next replay; capture after ``graphed_training_step(flat=True)`` has re-homed them."""
+    return _GraphedEval(forecaster_step, (init, target, forcing), phase, steps_to_log, warmup)
+
+
 class FlatStepModule(nn.Module):
     """A captured step (``graphed_training_step(..., flat=True)``) as an ``nn.Module`` whose ONLY parameter is the flat leaf:
     what ``torch.nn.parallel.DistributedDataParallel`` wraps (one parameter, one bucket, one hook) and what
