@@ -681,6 +681,45 @@ int64_t nlam_window_len(int64_t n_state_times, int64_t n_forcing_times, int32_t 
                         int32_t num_future_forcing_steps);
 int32_t nlam_window_batch(const nlam_window_t* p, void* hip_stream);
 
+/* The same batch launch over STRIDED series: forecast-type and ensemble datastores (weather_dataset.py:135-200, :235-254,
+ * :303-342, :399-418).  Element (sample s, member m, step j) of a series -- one contiguous (nodes x d) block -- sits at
+ *   base + s * stride_sample + j * stride_step + m * stride_member      (floats, 64-bit)
+ *   analysis data (is_forecast = 0): stride_sample = stride_step = the time stride; n_times = time steps
+ *   forecast data (is_forecast = 1): stride_sample = analysis stride, stride_step = lead-time stride; n_times = analysis times
+ *   forcing without a member axis: forcing_stride_member = 0 (every member reads the same forcing)
+ * Flat sample index idx (read on the device, clamped to [0, base_len * members) instead of faulting) -> (s, m) =
+ * divmod(idx, members), time-major as the reference; members = 1 under load_single_member.  base_len: as
+ * nlam_window_len over n_times for analysis data, n_times for forecast data.  With off = max(2, past):
+ *   state rows j = max(0, past - 2) ... off + ar_steps - 1  -> 2 init + ar_steps target
+ *   forcing of step k, window slot w: j = off + k - past + w (window = past + future + 1, feature-major / window-minor)
+ *   target_times[b][k], j = off + k:  analysis: times[s + j], or the time index s + j when times == NULL
+ *                                     forecast: times[s] + elapsed[j], or the lead-time index j when both are NULL
+ * Forecast data needs state_steps >= off + ar_steps and, with forcing, forcing_steps >= off + ar_steps + future lead
+ * times per analysis time (both are ignored for analysis data).  Standardisation as nlam_window_t. */
+typedef struct {
+    const float* state;
+    const float* forcing;            /* NULL when d_forcing == 0 */
+    const int64_t* times;            /* analysis: (n_times) valid times; forecast: (n_times) analysis times; or NULL */
+    const int64_t* elapsed;          /* forecast: (state_steps) lead times, with times; NULL otherwise */
+    const int64_t* sample_idx;       /* device, (batch) flat indices */
+    float* init_states;              /* (batch, 2, nodes, d_state) */
+    float* target_states;            /* (batch, ar_steps, nodes, d_state) */
+    float* forcing_windowed;         /* (batch, ar_steps, nodes, d_forcing * window) or NULL when d_forcing == 0 */
+    int64_t* target_times;           /* (batch, ar_steps) or NULL */
+    const float* state_mean;
+    const float* state_std;
+    const float* forcing_mean;
+    const float* forcing_std;
+    int64_t state_stride_sample, state_stride_step, state_stride_member;
+    int64_t forcing_stride_sample, forcing_stride_step, forcing_stride_member;
+    int64_t n_times;
+    int32_t state_steps, forcing_steps;
+    int32_t is_forecast, members;
+    int32_t nodes, d_state, d_forcing, batch;
+    int32_t ar_steps, num_past_forcing_steps, num_future_forcing_steps, _pad;
+} nlam_window_ens_t;
+int32_t nlam_window_batch_ens(const nlam_window_ens_t* p, void* hip_stream);
+
 /* decoupled-weight-decay Adam on flat buffers; step_count is the 1-based step */
 int32_t nlam_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step_count,

@@ -96,6 +96,7 @@ EXPORTS = [
     "nlam_concat",
     "nlam_window_len",
     "nlam_window_batch",
+    "nlam_window_batch_ens",
 ]
 
 
@@ -270,6 +271,44 @@ class Window(C.Structure):
         ("forcing_mean", C.c_void_p),
         ("forcing_std", C.c_void_p),
         ("n_times", C.c_int64),
+        ("nodes", C.c_int32),
+        ("d_state", C.c_int32),
+        ("d_forcing", C.c_int32),
+        ("batch", C.c_int32),
+        ("ar_steps", C.c_int32),
+        ("num_past_forcing_steps", C.c_int32),
+        ("num_future_forcing_steps", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class WindowEns(C.Structure):
+    """nlam_window_ens_t: the window batch over strided (forecast / ensemble) series."""
+    _fields_ = [
+        ("state", C.c_void_p),
+        ("forcing", C.c_void_p),
+        ("times", C.c_void_p),
+        ("elapsed", C.c_void_p),
+        ("sample_idx", C.c_void_p),
+        ("init_states", C.c_void_p),
+        ("target_states", C.c_void_p),
+        ("forcing_windowed", C.c_void_p),
+        ("target_times", C.c_void_p),
+        ("state_mean", C.c_void_p),
+        ("state_std", C.c_void_p),
+        ("forcing_mean", C.c_void_p),
+        ("forcing_std", C.c_void_p),
+        ("state_stride_sample", C.c_int64),
+        ("state_stride_step", C.c_int64),
+        ("state_stride_member", C.c_int64),
+        ("forcing_stride_sample", C.c_int64),
+        ("forcing_stride_step", C.c_int64),
+        ("forcing_stride_member", C.c_int64),
+        ("n_times", C.c_int64),
+        ("state_steps", C.c_int32),
+        ("forcing_steps", C.c_int32),
+        ("is_forecast", C.c_int32),
+        ("members", C.c_int32),
         ("nodes", C.c_int32),
         ("d_state", C.c_int32),
         ("d_forcing", C.c_int32),
@@ -468,6 +507,8 @@ def load():
     lib.nlam_window_len.restype = i64
     lib.nlam_window_batch.argtypes = [C.POINTER(Window), vp]
     lib.nlam_window_batch.restype = i32
+    lib.nlam_window_batch_ens.argtypes = [C.POINTER(WindowEns), vp]
+    lib.nlam_window_batch_ens.restype = i32
     lib.nlam_mlp_group_blocks.argtypes = [C.POINTER(C.c_int64), i32, C.POINTER(C.c_int32)]
     lib.nlam_mlp_group_blocks.restype = i32
     lib.nlam_mlp_fwd_group.argtypes = [C.POINTER(MlpFwd), i32, vp]

@@ -1,70 +1,238 @@
 """The training data path on the GPU: samples cut out of time series that live in HBM.
 
-Mirror of the reference's ``neural_lam/weather_dataset.py`` ``WeatherDataset`` for analysis data (one contiguous time
-series per category, no ensemble axis) -- ``__len__`` (:118-197), ``__getitem__`` (:467-533): same constructor
-arguments (``ar_steps``, ``num_past_forcing_steps``, ``num_future_forcing_steps``), same 4-tuple
-``(init_states, target_states, forcing, target_times)``, same IndexError / negative-index behaviour -- but the
-xarray slicing, the host tensors and the DataLoader collation are replaced by ONE launch (``nlam_window_batch``) that
-writes a whole batch from the resident series, reading its sample indices on the device, optionally with
-``ForecasterModule.on_after_batch_transfer`` (models/module.py:326-367) folded into the same pass.  A MEPS-sized year
-(2 920 steps x 63 784 nodes x 17 + 6 variables, fp32) is 17 GB: it fits the 288 GB of one MI355X many times over, so
-an epoch needs no host->device traffic at all (a resident permutation supplies the indices).
+Mirror of the reference's ``neural_lam/weather_dataset.py`` ``WeatherDataset`` -- ``__len__`` (:118-200),
+``__getitem__`` (:467-533): same constructor arguments (``ar_steps``, ``num_past_forcing_steps``,
+``num_future_forcing_steps``, ``load_single_member``), same 4-tuple ``(init_states, target_states, forcing, target_times)``,
+same IndexError / negative-index behaviour -- but the xarray slicing, the host tensors and the DataLoader collation are
+replaced by ONE launch that writes a whole batch from the resident series, reading its sample indices on the device,
+optionally with ``ForecasterModule.on_after_batch_transfer`` (models/module.py:326-367) folded into the same pass.  A
+MEPS-sized year of analyses (2 920 steps x 63 784 nodes x 17 + 6 variables, fp32) is 17 GB: it fits the 288 GB of one
+MI355X many times over, so an epoch needs no host->device traffic at all (a resident permutation supplies the indices).
 
-Forecast-type and ensemble datastores (weather_dataset.py:135-178, :233-254, :300-329) are out of scope here.
+Both kinds of datastore are covered: analysis data (one time series, ``(time, [member], N, F)``) and forecast data
+(``(analysis_time, elapsed_forecast_duration, [member], N, F)``, weather_dataset.py:135-178, :233-254, :300-329), each
+with or without an ensemble-member axis.  Plain analysis series (no member axis left on the device) are cut by
+``nlam_window_batch``; everything else by ``nlam_window_batch_ens``, which reads strided series.  Of a forecast only the
+lead times a sample can read stay resident -- ``max(2, past) + ar_steps`` for the state, ``+ future`` for the forcing --
+and host arrays (numpy memmaps included) are uploaded in chunks of analysis times, so the host never holds more than one
+chunk and HBM never holds the unread tail of the forecasts.
 """
 from __future__ import annotations
 
 import ctypes as C
+import warnings
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
+
+# host -> device uploads go in slices of the leading (time / analysis-time) axis of at most this many bytes
+UPLOAD_CHUNK_BYTES = 256 << 20
 
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class Layout(NamedTuple):
+    """What ``plan_layout`` decides from the shapes alone (no device needed)."""
+    n_times: int                    # leading axis: time steps (analysis) or analysis times (forecast), state and forcing in common
+    state_members: Optional[int]    # size of the state's member axis, None without one
+    forcing_members: Optional[int]  # the same for the forcing
+    members: int                    # members the flat index runs over (1 under load_single_member or without a member axis)
+    state_steps: Optional[int]      # forecast: lead times kept resident for the state (max(2, past) + ar_steps)
+    forcing_steps: Optional[int]    # forecast: lead times kept resident for the forcing (+ future)
+    keep_state_members: bool        # False: only member 0 of the state is ever read (and kept)
+    keep_forcing_members: bool      # False: only member 0 of the forcing is ever read (and kept)
+    base_len: int                   # samples per member
+    length: int                     # len(dataset) = base_len * members
+
+
+def plan_layout(state_shape, forcing_shape=None, *, is_forecast=False, ar_steps=3, num_past_forcing_steps=1,
+                num_future_forcing_steps=1, load_single_member=False):
+    """Shape checks, ``len()`` and the resident layout of ``DeviceWeatherDataset`` (weather_dataset.py:85-90, :118-200).
+
+    ``state_shape``: ``(time, [member], N, F)`` for analysis data, ``(analysis_time, elapsed, [member], N, F)`` for forecast
+    data -- the member axis is inferred from the rank; ``forcing_shape`` the same (or None).  Raises ValueError for
+    malformed shapes and, for forecasts, too short a lead-time axis; warns (UserWarning) under ``load_single_member``."""
+    state_shape = tuple(int(x) for x in state_shape)
+    ranks = (4, 5) if is_forecast else (3, 4)
+    dims = "(analysis_time, elapsed_forecast_duration, [ensemble_member], num_grid_nodes, %s)" if is_forecast else \
+        "(n_times, [ensemble_member], num_grid_nodes, %s)"
+    if len(state_shape) not in ranks:
+        raise ValueError("state must be " + dims % "num_state_vars")
+    ar, past, fut = int(ar_steps), int(num_past_forcing_steps), int(num_future_forcing_steps)
+    off = max(2, past)
+    state_members = state_shape[-3] if len(state_shape) == ranks[1] else None
+    forcing_members = None
+    if forcing_shape is not None:
+        forcing_shape = tuple(int(x) for x in forcing_shape)
+        if len(forcing_shape) not in ranks or forcing_shape[-2] != state_shape[-2]:
+            raise ValueError("forcing must be " + dims % "num_forcing_vars" + " on the same nodes as state")
+        if forcing_shape[-1] == 0:
+            forcing_shape = None
+    if forcing_shape is not None:
+        forcing_members = forcing_shape[-3] if len(forcing_shape) == ranks[1] else None
+        if is_forecast and forcing_shape[0] != state_shape[0]:
+            raise ValueError(f"forcing has {forcing_shape[0]} analysis times, state {state_shape[0]}: they must be the same")
+        if forcing_members is not None and state_members is not None and forcing_members != state_members:
+            raise ValueError(f"forcing has {forcing_members} ensemble members, state {state_members}: they must be the same")
+    if state_members is not None and state_members < 1:
+        raise ValueError("the state's ensemble-member axis is empty")
+    if state_members is not None and load_single_member:
+        warnings.warn("only using first ensemble member, so dataset size is effectively reduced by the number of ensemble "
+                      f"members ({state_members})", UserWarning, stacklevel=3)
+    members = state_members if state_members is not None and not load_single_member else 1
+    state_steps = forcing_steps = None
+    if is_forecast:
+        # weather_dataset.py:135-180, with its wording
+        if state_shape[1] < off + ar:
+            raise ValueError(f"The number of forecast steps available ({state_shape[1]}) is less than the required {off + ar} "
+                             f"(max(2, num_past_forcing_steps={past}) + ar_steps={ar}) for creating a sample with initial and "
+                             "target states.")
+        state_steps = off + ar
+        if forcing_shape is not None:
+            if forcing_shape[1] < off + ar + fut:
+                raise ValueError(f"The number of forcing forecast steps available ({forcing_shape[1]}) is less than the "
+                                 f"required {off + ar + fut} (max(2, num_past_forcing_steps={past}) + ar_steps={ar} + "
+                                 f"num_future_forcing_steps={fut}) for constructing forcing windows.")
+            forcing_steps = off + ar + fut
+        n_times = base_len = state_shape[0]
+    else:
+        n_times = state_shape[0] if forcing_shape is None else min(state_shape[0], forcing_shape[0])
+        base_len = max(0, n_times - (off + ar + fut) + 1)   # nlam_window_len: the same arithmetic in the C-ABI
+    return Layout(n_times=n_times, state_members=state_members, forcing_members=forcing_members, members=members,
+                  state_steps=state_steps, forcing_steps=forcing_steps,
+                  keep_state_members=state_members is not None and members > 1,
+                  keep_forcing_members=forcing_members is not None and members > 1,
+                  base_len=base_len, length=base_len * members)
+
+
+def _shape(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _resident(x, dev, steps, member_axis, keep_members):
+    """The part of series ``x`` a sample can read, contiguous fp32 on ``dev``: lead times ``[0, steps)`` of axis 1 when
+    ``steps`` is set, member 0 only (axis dropped) when the member axis exists and ``keep_members`` is False.  A device
+    tensor is sliced on the device (no copy when nothing is cut); a host array -- numpy, memmap, torch CPU tensor -- is
+    copied in chunks of the leading axis of at most UPLOAD_CHUNK_BYTES."""
+    if not hasattr(x, "shape"):
+        x = np.asarray(x, dtype=np.float32)
+    sl = [slice(None)] * len(x.shape)
+    if steps is not None:
+        sl[1] = slice(0, steps)
+    if member_axis is not None and not keep_members:
+        sl[member_axis] = 0
+    sl = tuple(sl)
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        return x.to(dev, torch.float32)[sl].contiguous()
+    rest = sl[1:]
+    n0 = int(x.shape[0])
+    shape = (n0,) + tuple(len(range(*r.indices(int(d)))) for d, r in zip(x.shape[1:], rest) if isinstance(r, slice))
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    row_bytes = 4 * max(1, int(np.prod(shape[1:], dtype=np.int64)))
+    step = max(1, int(UPLOAD_CHUNK_BYTES) // row_bytes)
+    for a0 in range(0, n0, step):
+        a1 = min(n0, a0 + step)
+        piece = x[(slice(a0, a1),) + rest]
+        if isinstance(piece, torch.Tensor):
+            piece = piece.to(torch.float32).contiguous()
+        else:
+            piece = np.ascontiguousarray(piece, dtype=np.float32)
+            if not piece.flags.writeable:   # a read-only memmap chunk: torch.from_numpy wants writable memory
+                piece = piece.copy()
+            piece = torch.from_numpy(piece)
+        out[a0:a1].copy_(piece)
+    return out
+
+
+def _ns(x, dev):
+    """int64 nanoseconds on ``dev`` from int64 / numpy datetime64 / timedelta64 stamps."""
+    if not isinstance(x, torch.Tensor):
+        a = np.asarray(x)
+        if a.dtype.kind == "M":
+            a = a.astype("datetime64[ns]").astype(np.int64)
+        elif a.dtype.kind == "m":
+            a = a.astype("timedelta64[ns]").astype(np.int64)
+        x = a
+    return torch.as_tensor(x, dtype=torch.int64).to(dev).contiguous()
+
+
 class DeviceWeatherDataset:
     """``WeatherDataset`` (weather_dataset.py:20-116) over device-resident series.
 
-    state    (n_times, num_grid_nodes, num_state_vars)   float32
-    forcing  (n_times, num_grid_nodes, num_forcing_vars) float32 or None
-    times    (n_times,) int64 nanoseconds or None (then ``target_times`` are time indices)
+    is_forecast=False (analysis data):
+        state    (n_times, [ensemble_member], num_grid_nodes, num_state_vars)   float32
+        forcing  (n_times, [ensemble_member], num_grid_nodes, num_forcing_vars) float32 or None
+        times    (n_times,) int64 nanoseconds (or datetime64) or None (then ``target_times`` are time indices)
+    is_forecast=True (forecast data, e.g. a ``npyfilesmeps`` store):
+        state    (analysis_time, elapsed_forecast_duration, [ensemble_member], num_grid_nodes, num_state_vars)
+        forcing  (analysis_time, elapsed_forecast_duration, [ensemble_member], num_grid_nodes, num_forcing_vars) or None
+        times    (analysis_time,) analysis times and ``elapsed`` (elapsed_forecast_duration,) lead times, both int64 ns (or
+                 datetime64 / timedelta64) or both None (then ``target_times`` are lead-time indices)
+    The member axis is inferred from the rank.  With one, ``len()`` is samples x members and index ``i`` is sample
+    ``i // members``, member ``i % members`` (weather_dataset.py:399-409); forcing with a member axis follows the state's
+    member, forcing without one is shared.  ``load_single_member=True`` uses member 0 only (and warns, :85-90).
     standardization: optional dict with ``state_mean, state_std, forcing_mean, forcing_std`` (the buffers
     ForecasterModule registers, module.py:159-215, std already clamped) for ``batch(..., standardize=True)``.
+    ``kernel`` names the C entry that cuts the batches: ``"nlam_window_batch"`` for plain analysis series,
+    ``"nlam_window_batch_ens"`` otherwise (the strided entry may be selected for any layout; it gives the same samples).
     """
 
     def __init__(self, state, forcing=None, times=None, ar_steps=3, num_past_forcing_steps=1, num_future_forcing_steps=1,
-                 standardization=None, device="cuda"):
+                 standardization=None, device="cuda", is_forecast=False, elapsed=None, load_single_member=False):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("DeviceWeatherDataset keeps its series in HBM and cuts samples with a HIP kernel: it needs a GPU "
                                "(there is no CPU fallback; the CPU restatement lives in oracle/data.py for the tests)")
-        state = torch.as_tensor(state, dtype=torch.float32)
-        if state.dim() != 3:
-            raise ValueError("state must be (n_times, num_grid_nodes, num_state_vars)")
-        self.state = state.to(dev).contiguous()
-        self.forcing = None
-        if forcing is not None:
-            forcing = torch.as_tensor(forcing, dtype=torch.float32)
-            if forcing.dim() != 3 or forcing.shape[1] != state.shape[1]:
-                raise ValueError("forcing must be (n_times, num_grid_nodes, num_forcing_vars) on the same nodes as state")
-            if forcing.shape[2] > 0:
-                self.forcing = forcing.to(dev).contiguous()
-        self.times = None if times is None else torch.as_tensor(times, dtype=torch.int64).to(dev).contiguous()
-        if self.times is not None and self.times.shape != (state.shape[0],):
-            raise ValueError("times must have one entry per state time step")
+        self.is_forecast = bool(is_forecast)
         self.ar_steps = int(ar_steps)
         self.num_past_forcing_steps = int(num_past_forcing_steps)
         self.num_future_forcing_steps = int(num_future_forcing_steps)
+        self.load_single_member = bool(load_single_member)
+        lay = plan_layout(_shape(state), None if forcing is None else _shape(forcing), is_forecast=self.is_forecast,
+                          ar_steps=self.ar_steps, num_past_forcing_steps=self.num_past_forcing_steps,
+                          num_future_forcing_steps=self.num_future_forcing_steps, load_single_member=self.load_single_member)
+        self.layout = lay
+        if self.is_forecast and (times is None) != (elapsed is None):
+            raise ValueError("forecast data: give both the analysis times and the elapsed forecast durations, or neither")
+        if not self.is_forecast and elapsed is not None:
+            raise ValueError("elapsed is the lead-time axis of forecast data (is_forecast=True)")
+        s_shape = _shape(state)
+        m_ax = len(s_shape) - 3
+        self.state = _resident(state, dev, lay.state_steps, m_ax if lay.state_members is not None else None, lay.keep_state_members)
+        self.forcing = None
+        if forcing is not None and _shape(forcing)[-1] > 0:
+            f_ax = len(_shape(forcing)) - 3
+            self.forcing = _resident(forcing, dev, lay.forcing_steps, f_ax if lay.forcing_members is not None else None,
+                                     lay.keep_forcing_members)
+        self.times = None if times is None else _ns(times, dev)
+        if self.times is not None and self.times.shape != (s_shape[0],):
+            raise ValueError("times must have one entry per state time step" if not self.is_forecast else
+                             "times must have one entry per analysis time")
+        self.elapsed = None
+        if elapsed is not None:
+            e = _ns(elapsed, dev)
+            if e.shape != (s_shape[1],):
+                raise ValueError("elapsed must have one entry per lead time of the state")
+            self.elapsed = e[: lay.state_steps].contiguous()
+        self.members = lay.members
+        self._nodes, self._d_state = int(s_shape[-2]), int(s_shape[-1])
         self.device = dev
         self._lib = L.load()
-        n_forc = -1 if self.forcing is None else self.forcing.shape[0]
-        self._len = int(self._lib.nlam_window_len(self.state.shape[0], n_forc, self.ar_steps, self.num_past_forcing_steps,
-                                                  self.num_future_forcing_steps))
+        plain = not self.is_forecast and self.state.dim() == 3 and (self.forcing is None or self.forcing.dim() == 3)
+        self.kernel = "nlam_window_batch" if plain else "nlam_window_batch_ens"
+        if plain:
+            n_forc = -1 if self.forcing is None else self.forcing.shape[0]
+            self._len = int(self._lib.nlam_window_len(self.state.shape[0], n_forc, self.ar_steps, self.num_past_forcing_steps,
+                                                      self.num_future_forcing_steps))
+        else:
+            self._len = lay.length
         # one common time axis for the kernel: it indexes both series with the same time index
-        self._n_times = int(self.state.shape[0] if self.forcing is None else min(self.state.shape[0], self.forcing.shape[0]))
+        self._n_times = lay.n_times
         self.stats = None
         if standardization is not None:
             g = lambda k: torch.as_tensor(standardization[k], dtype=torch.float32).to(dev).contiguous()  # noqa: E731
@@ -79,7 +247,7 @@ class DeviceWeatherDataset:
 
     @property
     def num_forcing_features(self):
-        return 0 if self.forcing is None else self.forcing.shape[2] * self.window
+        return 0 if self.forcing is None else self.forcing.shape[-1] * self.window
 
     def __len__(self):
         return self._len
@@ -130,7 +298,7 @@ class DeviceWeatherDataset:
             self.check_indices(indices)
         indices = indices.to(torch.int64).contiguous()
         B, T = indices.numel(), self.ar_steps
-        N, ds = self.state.shape[1], self.state.shape[2]
+        N, ds = self._nodes, self._d_state
         fw = self.num_forcing_features
         if out is None:
             o = dict(device=self.device, dtype=torch.float32)
@@ -142,6 +310,12 @@ class DeviceWeatherDataset:
                 raise ValueError(f"output buffer of shape {tuple(t_.shape)}: expected a contiguous {shape} tensor on {self.device}")
         if standardize and self.stats is None:
             raise ValueError("standardize=True needs the standardization statistics (constructor argument)")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.kernel == "nlam_window_batch_ens":
+            self._launch_ens(indices, init, target, forcing if fw else None, times, standardize, stream)
+            return init, target, forcing, times
+        if self.kernel != "nlam_window_batch" or self.state.dim() != 3 or self.is_forecast:
+            raise ValueError(f"kernel {self.kernel!r}: nlam_window_batch cuts plain analysis series only")
         p = L.Window()
         p.state, p.forcing, p.sample_idx = _ptr(self.state), _ptr(self.forcing), _ptr(indices)
         p.init_states, p.target_states = _ptr(init), _ptr(target)
@@ -154,8 +328,38 @@ class DeviceWeatherDataset:
         p.n_times, p.nodes, p.d_state, p.batch = self._n_times, N, ds, B
         p.d_forcing = 0 if self.forcing is None else self.forcing.shape[2]
         p.ar_steps, p.num_past_forcing_steps, p.num_future_forcing_steps = T, self.num_past_forcing_steps, self.num_future_forcing_steps
-        L.check(self._lib.nlam_window_batch(C.byref(p), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nlam_window_batch")
+        L.check(self._lib.nlam_window_batch(C.byref(p), stream), "nlam_window_batch")
         return init, target, forcing, times
+
+    def _launch_ens(self, indices, init, target, forcing, times, standardize, stream):
+        """nlam_window_batch_ens over the resident series: strides in floats from the tensors' own layout."""
+        p = L.WindowEns()
+        p.state, p.forcing, p.sample_idx = _ptr(self.state), _ptr(self.forcing), _ptr(indices)
+        p.init_states, p.target_states, p.forcing_windowed = _ptr(init), _ptr(target), _ptr(forcing)
+        # no time stamps: the kernel reports the time index (analysis) or the lead-time index (forecast) of every target step
+        p.times, p.elapsed, p.target_times = _ptr(self.times), _ptr(self.elapsed), _ptr(times)
+        if standardize:
+            p.state_mean, p.state_std = _ptr(self.stats["state_mean"]), _ptr(self.stats["state_std"])
+            if forcing is not None:
+                p.forcing_mean, p.forcing_std = _ptr(self.stats["forcing_mean"]), _ptr(self.stats["forcing_std"])
+
+        def strides(x):   # (sample, step, member) strides of a resident series; member stride 0 without a member axis
+            if x is None:
+                return 0, 0, 0
+            lead = 1 if self.is_forecast else 0
+            member = x.stride(lead + 1) if x.dim() == 4 + lead else 0
+            return x.stride(0), x.stride(lead), member
+
+        p.state_stride_sample, p.state_stride_step, p.state_stride_member = strides(self.state)
+        p.forcing_stride_sample, p.forcing_stride_step, p.forcing_stride_member = strides(self.forcing)
+        p.n_times, p.is_forecast, p.members = self._n_times, int(self.is_forecast), self.members
+        if self.is_forecast:
+            p.state_steps = self.state.shape[1]
+            p.forcing_steps = 0 if self.forcing is None else self.forcing.shape[1]
+        p.nodes, p.d_state, p.batch = self._nodes, self._d_state, indices.numel()
+        p.d_forcing = 0 if self.forcing is None else self.forcing.shape[-1]
+        p.ar_steps, p.num_past_forcing_steps, p.num_future_forcing_steps = self.ar_steps, self.num_past_forcing_steps, self.num_future_forcing_steps
+        L.check(self._lib.nlam_window_batch_ens(C.byref(p), stream), "nlam_window_batch_ens")
 
     def epoch_permutation(self, seed=0):
         """A resident random permutation of the sample indices: ``perm[k * B : (k + 1) * B]`` feeds ``batch`` with no host copy."""
