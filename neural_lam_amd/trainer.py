@@ -443,6 +443,7 @@ class Trainer:
             self.opt = AdamWFlat(self.fp.flat, self.fp.grad, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         else:
             self.opt = optimizer_factory(self.fp.flat, self.fp.grad)
+        self._built_hyper = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)   # restored by restore_opt=False
 
     @staticmethod
     def _pick_executor(module) -> str:
@@ -877,6 +878,81 @@ class Trainer:
 
     batch_times = None
 
+    # ---- checkpoints (checkpoint.save_checkpoint / load_checkpoint) ----
+    def _flat_adamw(self):
+        ops = self._ops()
+        if ops is None or not isinstance(self.opt, ops.AdamWFlat):
+            raise TypeError(f"Trainer checkpoints need the built-in AdamWFlat optimizer, not {type(self.opt).__name__}")
+        return self.opt
+
+    def _layout(self):
+        from .checkpoint import trainable_names
+
+        return trainable_names(self.module), [tuple(p.shape) for p in self.fp.params], [self.fp.offsets[i] for i in range(len(self.fp.params))]
+
+    def state_dict(self) -> dict:
+        """``{"state_dict", "optimizer_states": [sd]}`` with CPU tensors; ``sd`` is what ``torch.optim.AdamW`` over the
+        reference module's parameters would hold (one entry per parameter, in ``named_parameters()`` order)."""
+        from .checkpoint import export_flat_state, module_state_to_cpu
+
+        opt = self._flat_adamw()
+        names, shapes, offsets = self._layout()
+        t = int(opt.t_dev.item())   # the device counter is the truth; ``t`` mirrors it
+        hyper = dict(lr=opt.lr, betas=opt.betas, eps=opt.eps, weight_decay=opt.wd)
+        return {"state_dict": module_state_to_cpu(self.module),
+                "optimizer_states": [export_flat_state(shapes, offsets, opt.m, opt.v, t, hyper)]}
+
+    def load_state_dict(self, ckpt: dict, restore_opt: bool = True, strict: bool = True):
+        """Load a reference-layout checkpoint (``checkpoint.load_checkpoint`` applies the legacy key remaps first) IN PLACE:
+        weights into ``fp.flat``, moments into ``opt.m`` / ``opt.v``, the step count into ``opt.t_dev`` (and ``opt.t``);
+        no buffer is rebound, so captured graphs, packed weight images (rewritten from the weights at the start of every
+        step) and gradient buckets stay valid, and the next step equals a fresh trainer's.  Restored lr / betas / eps /
+        weight decay that differ from a captured AdamW launch re-record it once, without counting as a schedule change; a
+        trainer already in schedule mode (optimizer uncaptured) simply launches with the new values.
+        ``restore_opt=False``: weights only; step 0, zero moments and the hyper-parameters the trainer was built with.
+        At world > 1 every rank loads, and one all-reduce of a checksum checks that the ranks hold the same state."""
+        from .checkpoint import import_flat_state, load_module_weights, reorder_optimizer_state
+
+        opt = self._flat_adamw()
+        names, shapes, offsets = self._layout()
+        sd = None
+        if restore_opt:
+            states = ckpt.get("optimizer_states")
+            if not isinstance(states, (list, tuple)) or len(states) != 1:
+                raise ValueError("checkpoint 'optimizer_states' must hold one optimizer state")
+            sd = states[0]
+        ckpt_names = load_module_weights(self.module, ckpt["state_dict"], strict=strict, copy=False)   # validate first
+        if sd is not None:   # validated before the moments are written
+            t, hyper = import_flat_state(reorder_optimizer_state(sd, ckpt_names, names, shapes, strict=strict), shapes, offsets,
+                                         opt.m, opt.v)
+        else:
+            with torch.no_grad():
+                opt.m.zero_()
+                opt.v.zero_()
+            t, hyper = 0, self._built_hyper
+        load_module_weights(self.module, ckpt["state_dict"], strict=strict)
+        opt.t = t
+        opt.t_dev.fill_(t)
+        opt.lr, opt.betas, opt.eps, opt.wd = hyper["lr"], tuple(hyper["betas"]), hyper["eps"], hyper["weight_decay"]
+        if self._graph is not None and (self._opt_in_graph or self._tail_graph is not None) and self._opt_signature() != self._opt_sig:
+            changes, self._opt_changes = self._opt_changes, 0
+            try:
+                self._optimizer_changed()   # the first-change path: re-record the optimizer's launch with the restored values
+            finally:
+                self._opt_changes = changes
+        if self.world > 1:
+            self._check_ranks_agree()
+
+    def _check_ranks_agree(self):
+        """One all-reduce (MAX of the checksums and of their negatives): every rank must hold the same weights and moments."""
+        opt = self.opt
+        c = torch.stack([self.fp.flat.double().sum(), (self.fp.flat.double() ** 2).sum(), opt.m.double().sum(),
+                         opt.v.double().sum(), opt.t_dev.double().sum()])
+        both = torch.cat([c, -c])
+        dist.all_reduce(both, op=dist.ReduceOp.MAX, group=self.buckets.group)
+        if not torch.equal(both[:5], -both[5:]):
+            raise ValueError("after loading the checkpoint the ranks hold different weights / optimizer state")
+
 
 # ---------------------------------------------------------------------------
 # The drop-in path: a captured forward + backward for a training loop that owns its optimizer (Lightning)
@@ -912,10 +988,9 @@ class _GraphedStep:
         # autograd as the parameters' gradients.  Same bits as the eager module (0 + x = x; accumulation order = backward order).
         self.gflat, self.gviews = None, None
         if overlap_wgrad:
-            offs, off = [], 0
-            for p in self.params:
-                offs.append(off)
-                off += (p.numel() + 3) // 4 * 4
+            from .checkpoint import staging_offsets
+
+            offs, off = staging_offsets([p.shape for p in self.params])
             self.gflat = torch.zeros(off, device=self.params[0].device, dtype=torch.float32)
             self.goffs = offs
             self.gviews = [self.gflat[o : o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
@@ -1070,6 +1145,49 @@ class _GraphedStep:
         else:
             out = self._fn.apply(*args, *self.params)
         return out if len(out) > 1 else out[0]
+
+    # ---- checkpoints: AdamW([flat_parameter]) <-> the reference's AdamW(module.parameters()) ----
+    def _check_flat_optimizer(self, opt):
+        if self.flat_parameter is None:
+            raise ValueError("optimizer state conversion needs graphed_training_step(..., flat=True)")
+        groups = opt.param_groups
+        if len(groups) != 1 or len(groups[0]["params"]) != 1 or groups[0]["params"][0] is not self.flat_parameter:
+            raise ValueError("the optimizer must hold exactly [step.flat_parameter] in one parameter group")
+
+    def optimizer_state_to_reference(self, opt) -> dict:
+        """The state dict ``torch.optim.AdamW(module.parameters())`` would hold, from ``opt = AdamW([flat_parameter])``:
+        the flat moments cut along ``goffs`` (CPU tensors), one entry per parameter in ``named_parameters()`` order."""
+        from .checkpoint import check_flat_group, export_flat_state
+
+        self._check_flat_optimizer(opt)
+        group = opt.param_groups[0]
+        check_flat_group(group)
+        st = opt.state.get(self.flat_parameter, {})
+        shapes = [tuple(p.shape) for p in self.params]
+        hyper = dict(lr=float(group["lr"]), betas=tuple(group["betas"]), eps=group["eps"], weight_decay=group["weight_decay"])
+        if "step" not in st:
+            z = torch.zeros(0)
+            return export_flat_state(shapes, self.goffs, z, z, 0, hyper, group_template=group)
+        return export_flat_state(shapes, self.goffs, st["exp_avg"], st["exp_avg_sq"], int(float(st["step"])), hyper,
+                                 group_template=group)
+
+    def load_reference_optimizer_state(self, opt, sd, names=None, strict=True):
+        """The inverse of ``optimizer_state_to_reference``: a reference-layout AdamW state dict into ``opt =
+        AdamW([flat_parameter])`` (``opt.load_state_dict`` of the flat equivalent; padding moments 0).  ``names``: the
+        parameter name of every index of ``sd`` (``load_checkpoint`` reads them from the checkpoint's ``state_dict``);
+        default: this module's ``named_parameters()`` order."""
+        from .checkpoint import import_flat_state, reorder_optimizer_state, trainable_names
+
+        self._check_flat_optimizer(opt)
+        target = trainable_names(self.module)
+        shapes = [tuple(p.shape) for p in self.params]
+        re = reorder_optimizer_state(sd, target if names is None else names, target, shapes, strict=strict)
+        m, v = torch.zeros_like(self.gflat), torch.zeros_like(self.gflat)
+        t, _ = import_flat_state(re, shapes, self.goffs, m, v)
+        group = {k: val for k, val in re["param_groups"][0].items() if k != "params"}
+        group["params"] = [0]
+        state = {0: {"step": torch.tensor(float(t), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}} if t > 0 else {}
+        opt.load_state_dict({"state": state, "param_groups": [group]})
 
 
 class _GraphedEval:
