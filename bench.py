@@ -7,6 +7,10 @@ which case it re-launches itself that way (127.0.0.1 rendezvous, free port).  W 
 warm-up steps, then exactly K training steps bracketed by barrier +
 synchronize; the max over ranks is the job time; rank 0 prints ONE JSON line.
 ``--dump-outputs DIR`` writes what the last timed step computed to DIR/*.npy (see dump_outputs).
+A plain run does only that: set up, warm up, time, dump, print.  Everything else it can measure or
+check -- the legs and baselines listed below, forecast throughput, the loss on the initial weights --
+runs only under ``--full`` (that loss before the warm-up, the rest after the timed steps and the
+dump); the ``--no-*`` options thin a ``--full`` run.
 
 A step = ``ForecasterModule.training_step``-equivalent on one pre-resident
 synthetic batch per GPU: standardised inputs -> AR rollout
@@ -19,7 +23,9 @@ Launch mode: zero-grad + forward + loss + backward are captured once into a HIP
 graph and replayed per step (the gradient all-reduce for N > 1 and the fused AdamW
 run after each replay); ``--eager`` issues every launch from Python instead.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (``--full``; a plain run prints ``roofline`` as null and leaves out the rest):
+  forecast_steps_per_s
+                inference rollouts (no grad) per second, same launch mode as the training step.
   roofline      per launch shape (HIP events on the launch stream, second instrumented
                 eager pass): algorithmic FLOPs and HBM bytes, the matrix instruction
                 actually issued, frac = max(executed MFMA FLOPs / dense peak of THAT
@@ -36,6 +42,9 @@ Extra objects on the JSON line:
                 step time the >= 5x target of BASELINE.json is measured against.
   oracle_loss_step0 / loss_step0
                 the CPU oracle's loss and the HIP path's loss on the initial weights.
+  from_device_dataset, lightning_shaped, also
+                the same step fed by the HBM-resident dataset, the Lightning-shaped loop, the wide
+                configurations (cfg3 / cfg5 at N = 1, cfg3 at N > 1).
 """
 from __future__ import annotations
 
@@ -459,12 +468,16 @@ def main():
     ap.add_argument("--steps", type=int, default=300)   # ~2 ms steps: a timed region of >= 0.5 s
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-data-path", action="store_true", help="skip the leg that trains from the HBM-resident dataset")
-    ap.add_argument("--no-lightning-leg", action="store_true", help="skip the Lightning-shaped (eager / graphed + torch AdamW) leg")
-    ap.add_argument("--no-also", action="store_true", help="skip the cfg3 / cfg5 legs reported under 'also'")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the loss on the initial weights (before the warm-up) and, after the timed "
+                         "steps, forecast throughput, the HBM-resident data path, per-launch rooflines, the Lightning-shaped loop, the wide "
+                         "configurations under 'also', the CPU and same-GPU baselines (the --no-* options below leave legs out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg")
+    ap.add_argument("--no-gpu-baseline", action="store_true", help="with --full: skip the same-GPU stock-PyTorch leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented per-launch pass")
+    ap.add_argument("--no-data-path", action="store_true", help="with --full: skip the leg that trains from the HBM-resident dataset")
+    ap.add_argument("--no-lightning-leg", action="store_true", help="with --full: skip the Lightning-shaped (eager / graphed + torch AdamW) leg")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the cfg3 / cfg5 legs reported under 'also'")
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python instead of replaying a HIP graph")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
                     help="bf16 = run the step inside torch.autocast(bfloat16), as Lightning --precision bf16-mixed does (cfg5)")
@@ -523,8 +536,10 @@ def main():
     ds, graph, raw, forecaster, step, batch = build(cfg, device, seed_offset=rank)
     amp = torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.precision == "bf16")
     amp.__enter__()   # whole run (capture included) inside the autocast region; exited before the baselines
-    with torch.no_grad():   # loss on the initial weights, for the parity line against the oracle
-        loss_step0 = float(step(*batch)[1])
+    loss_step0 = None
+    if args.full:
+        with torch.no_grad():   # loss on the initial weights, for the parity line against the oracle
+            loss_step0 = float(step(*batch)[1])
     trainer = Trainer(step, lr=1e-3, use_graph=not args.eager)
 
     def sync():
@@ -562,6 +577,49 @@ def main():
     value = world * cfg["B"] * cfg["T"] * args.steps / elapsed
     if args.dump_outputs and rank == 0:
         dump_outputs(Path(args.dump_outputs), trainer, loss)
+
+    launch_mode = "eager" if args.eager else (
+        "hip_graph, one-graph executor (zero-grad + fwd + loss + bwd [+ AdamW at world 1] captured once, weight gradients as forked branches; "
+        "on_after_batch_transfer writes the graph's inputs before; at world > 1 the all-reduce and the optimizer's own graph follow each replay)"
+        if trainer.executor == "forks" else
+        "hip_graph, segmented executor (the chain -- zero-grad, fwd, loss, data gradients -- as linear graphs replayed back to back on one stream, "
+        f"weight gradients as graphs on side streams behind per-segment events, {trainer.forks_per_segment} fork points per segment; the optimizer's "
+        "graph behind the join; at world > 1 gradient buckets are all-reduced per segment)")
+    out = {
+        "metric": "training sample-steps/s (on_after_batch_transfer+fwd+wmse+bwd+allreduce+AdamW), GraphCast-LAM, MEPS-shaped grid",
+        "value": value,
+        "unit": "sample-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "timed_regions_ms": [x * 1e3 for x in regions],   # one region of exactly `steps` steps: value / ms_per_step come from it
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if args.precision == "fp32" else "bf16",
+        "matmul_mode": ops.matmul_mode_name() if args.precision == "fp32" else "bf16 (autocast)",
+        "data": "synthetic",
+        "launch_mode": launch_mode,
+        "rccl_ranks_seen": ranks_seen,
+        "final_loss": float(loss),
+        "config": {
+            "workload": f"{args.config}: {cfg['model']}, grid {cfg['nx']}x{cfg['ny']} ({ds.num_grid_points} nodes), "
+                        f"{cfg['ns']} state vars, hidden_dim {cfg['d']}, {cfg['L']} processor layers, "
+                        f"ar_steps {cfg['T']}, batch {cfg['B']}/GPU, g2m/m2m/m2g edges "
+                        f"{raw['g2m_edge_index'].shape[1]}/{raw['m2m_edge_index'][0].shape[1]}/{raw['m2g_edge_index'].shape[1]}",
+            "global_batch": world * cfg["B"],
+            "parallelism": f"dp{world}",
+        },
+        "roofline": None,   # --full: the instrumented per-launch pass
+    }
+    if not args.full:   # a plain run ends here: its headline figure and nothing else
+        amp.__exit__(None, None, None)
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # N > 1: BASELINE configs[2] (GraphLAM d = 256, 8 layers, ar_steps 4, one sample per GPU) is the configuration the
     # 0.9-efficiency target is written for; it is timed as well (same contract, fewer steps) and reported under "also".
@@ -719,13 +777,6 @@ def main():
             }
 
     amp.__exit__(None, None, None)
-    launch_mode = "eager" if args.eager else (
-        "hip_graph, one-graph executor (zero-grad + fwd + loss + bwd [+ AdamW at world 1] captured once, weight gradients as forked branches; "
-        "on_after_batch_transfer writes the graph's inputs before; at world > 1 the all-reduce and the optimizer's own graph follow each replay)"
-        if trainer.executor == "forks" else
-        "hip_graph, segmented executor (the chain -- zero-grad, fwd, loss, data gradients -- as linear graphs replayed back to back on one stream, "
-        f"weight gradients as graphs on side streams behind per-segment events, {trainer.forks_per_segment} fork points per segment; the optimizer's "
-        "graph behind the join; at world > 1 gradient buckets are all-reduced per segment)")
     if world == 1:
         # the baseline legs below build their own models: release the timed trainer first (its graphs' private pools hold every saved
         # activation of the step -- ~160 GB at cfg5; the executor object and the trainer reference each other, hence the collection)
@@ -748,36 +799,9 @@ def main():
         also = {"cfg3": also_leg("cfg3", "fp32", device, rank, world, args, timed_regions),
                 "cfg5_bf16": also_leg("cfg5", "bf16", device, rank, world, args, timed_regions)}
     if rank == 0:
-        out = {
-            "metric": "training sample-steps/s (on_after_batch_transfer+fwd+wmse+bwd+allreduce+AdamW), GraphCast-LAM, MEPS-shaped grid",
-            "value": value,
-            "unit": "sample-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "timed_regions_ms": [x * 1e3 for x in regions],   # one region of exactly `steps` steps: value / ms_per_step come from it
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if args.precision == "fp32" else "bf16",
-            "matmul_mode": ops.matmul_mode_name() if args.precision == "fp32" else "bf16 (autocast)",
-            "data": "synthetic",
-            "launch_mode": launch_mode,
-            "forecast_steps_per_s": forecast_steps_per_s,
-            "rccl_ranks_seen": ranks_seen,
-            "final_loss": float(loss),
-            "loss_step0": loss_step0,
-            "config": {
-                "workload": f"{args.config}: {cfg['model']}, grid {cfg['nx']}x{cfg['ny']} ({ds.num_grid_points} nodes), "
-                            f"{cfg['ns']} state vars, hidden_dim {cfg['d']}, {cfg['L']} processor layers, "
-                            f"ar_steps {cfg['T']}, batch {cfg['B']}/GPU, g2m/m2m/m2g edges "
-                            f"{raw['g2m_edge_index'].shape[1]}/{raw['m2m_edge_index'][0].shape[1]}/{raw['m2g_edge_index'].shape[1]}",
-                "global_batch": world * cfg["B"],
-                "parallelism": f"dp{world}",
-            },
-            "roofline": roofline,
-        }
+        out["forecast_steps_per_s"] = forecast_steps_per_s
+        out["loss_step0"] = loss_step0
+        out["roofline"] = roofline
         if data_path is not None:
             out["from_device_dataset"] = data_path
         if drop_in is not None:

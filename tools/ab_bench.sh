@@ -4,9 +4,9 @@
 # Arms are environment variables read at import: NLAM_WGRAD_CHUNKS (32-row chunks a weight-gradient workgroup streams),
 # NLAM_WGRAD_STREAMS (side streams of the weight-gradient work), NLAM_EARLY_LEAF (early backward of leaf MLPs),
 # NLAM_FACTORISE_MIN_EDGES (factorised edge MLP at d <= 64), NLAM_MATMUL (matrix mode).
-mkdir -p gpurun_out/ab
-run() { tag=$1; shift; env "$@" python bench.py --no-cpu-baseline --no-gpu-baseline --no-roofline --steps 200 > gpurun_out/ab/$tag.json 2>/dev/null; python -c "
-import json; d=json.load(open('gpurun_out/ab/$tag.json')); print('$tag', round(d['ms_per_step'],4), 'ms/step', round(d['forecast_steps_per_s'],1), 'forecast steps/s')"; }
+OUT=${OUT:-$(mktemp -d)}; mkdir -p $OUT   # one JSON line per arm
+run() { tag=$1; shift; env "$@" python bench.py --full --no-cpu-baseline --no-gpu-baseline --no-roofline --steps 200 > $OUT/$tag.json 2>/dev/null; python -c "
+import json; d=json.load(open('$OUT/$tag.json')); print('$tag', round(d['ms_per_step'],4), 'ms/step', round(d['forecast_steps_per_s'],1), 'forecast steps/s')"; }
 run base A=1
 run base_again A=1
 run early_leaf NLAM_EARLY_LEAF=1

@@ -20,14 +20,14 @@ python tools/make_pmc_traffic.py gpurun_out/pmc_m2g_edge.json:255136 gpurun_out/
 mkdir -p profiles/round6 && cp $OUT/pmc_traffic.json profiles/round6/pmc_traffic.json   # (this copy of the tree: bench.py below reads roofline.traffic from it)
 # the driver's command line first (with the cfg3 / cfg5 legs under "also"), then the 300-step default
 t0=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_cfg2_driver_cmdline.json 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_cfg2_driver_cmdline.json 2>/dev/null
 echo "driver command line: $(( $(date +%s) - t0 )) s wall" > $OUT/bench_driver_cmdline_wall.txt
-python bench.py --no-also > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-python bench.py --config cfg3 --steps 12 --warmup 2 --no-data-path > $OUT/bench_cfg3.json 2>/dev/null
-python bench.py --config cfg4 --steps 30 --warmup 3 --no-data-path > $OUT/bench_cfg4.json 2>/dev/null
-python bench.py --config cfg4p --steps 30 --warmup 3 --no-data-path > $OUT/bench_cfg4p.json 2>/dev/null
-python bench.py --config cfg5 --precision bf16 --steps 4 --warmup 2 --no-data-path > $OUT/bench_cfg5_bf16.json 2>/dev/null
-python bench.py --config cfg3 --precision bf16 --steps 12 --warmup 2 --no-cpu-baseline --no-data-path --no-lightning-leg > $OUT/bench_cfg3_bf16.json 2>/dev/null
+python bench.py --full --no-also > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+python bench.py --full --config cfg3 --steps 12 --warmup 2 --no-data-path > $OUT/bench_cfg3.json 2>/dev/null
+python bench.py --full --config cfg4 --steps 30 --warmup 3 --no-data-path > $OUT/bench_cfg4.json 2>/dev/null
+python bench.py --full --config cfg4p --steps 30 --warmup 3 --no-data-path > $OUT/bench_cfg4p.json 2>/dev/null
+python bench.py --full --config cfg5 --precision bf16 --steps 4 --warmup 2 --no-data-path > $OUT/bench_cfg5_bf16.json 2>/dev/null
+python bench.py --full --config cfg3 --precision bf16 --steps 12 --warmup 2 --no-cpu-baseline --no-data-path --no-lightning-leg > $OUT/bench_cfg3_bf16.json 2>/dev/null
 for w in m2g g2m m2m; do python tools/kernel_bench.py $w 12 64 2>&1 | grep -v amdgpu.ids; done > $OUT/kernel_bench_d64.log
 { NLAM_KB_AUTOCAST=1 python tools/kernel_bench.py m2m 12 512 2>&1 | grep -v amdgpu.ids | sed 's/^/[autocast bf16] /'; NLAM_KB_AUTOCAST=1 python tools/kernel_bench.py m2g 8 512 2>&1 | grep -v amdgpu.ids | sed 's/^/[autocast bf16] /'; python tools/kernel_bench.py m2m 12 256 2>&1 | grep -v amdgpu.ids; python tools/kernel_bench.py m2g 8 256 2>&1 | grep -v amdgpu.ids; } > $OUT/kernel_bench_wide.log
 python tools/chain_only.py > $OUT/chain_only.log 2>&1
