@@ -47,6 +47,9 @@
  *   nlam_eval_metrics, nlam_eval_workspace_floats
  *       the evaluation tensors of validation_step / test_step (models/module.py:546-576, :607-681): per-step loss,
  *       per-variable masked MSE / MAE / mean std, per-node loss maps; one pass over the rollout + a fixed-order reduction.
+ *   nlam_window_moments, nlam_moments_workspace_doubles
+ *       the per-sample means and second moments of npyfilesmeps/compute_standardization_stats.py (values and
+ *       standardized one-step differences), read in place from the resident series of the data path.
  *   nlam_reduce_partials
  *       deterministic second stage of the per-workgroup partial sums.
  *   nlam_adamw_step
@@ -719,6 +722,50 @@ typedef struct {
     int32_t ar_steps, num_past_forcing_steps, num_future_forcing_steps, _pad;
 } nlam_window_ens_t;
 int32_t nlam_window_batch_ens(const nlam_window_ens_t* p, void* hip_stream);
+
+/* Per-sample moments of a resident series, read in place (the standardization statistics of
+ * neural_lam/datastore/npyfilesmeps/compute_standardization_stats.py; no batch is materialised).  Addressing as
+ * nlam_window_ens_t: element (sample s, member m, row j) is the contiguous (nodes x nvars) block at
+ *   series + s * stride_sample + j * stride_step + m * stride_member      (floats, 64-bit)
+ * for the flat samples idx = first ... first + count - 1, (s, m) = divmod(idx, members), clamped to [0, base_len * members)
+ * (base_len: n_times - (row_begin + nrows) + 1 for analysis data -- nlam_window_len with past = future = 0 when
+ * row_begin + nrows = 2 + ar_steps, sample s reading time steps s + j -- and n_times for forecast data).  The
+ * rows of a sample are j = row_begin ... row_begin + nrows - 1 (the state: 0 ... ar_steps + 1; the forcing with no past /
+ * future window: 2 ... ar_steps + 1).  Two modes, per feature f:
+ *   step == 0 (values): out_mean[i][f] = mean of x, out_sq[i][f] = mean of x^2 over the nrows rows and the nodes of
+ *     sample first + i; count output rows.
+ *   step >= 1 (standardized one-step differences): used = (nrows / step) * step; sub-offset k in [0, step) takes rows
+ *     row_begin + k, row_begin + k + step, ... < row_begin + used; for consecutive pairs (a, b) of them
+ *     d = (x[b] - mean) / std - (x[a] - mean) / std in fp32 (IEEE sub, div, sub, in this order); out_mean / out_sq are the
+ *     means of d and d^2 over pairs and nodes.  Output row i * step + k (sample-major); count * step rows.  Needs at least
+ *     one pair (nrows / step >= 2).
+ * Accumulation is fp64 from the first element: a workgroup owns a fixed node range of one output row; its partial sums
+ * go to `workspace` and a second launch adds them in a fixed order (bit-identical run to run; the split depends on nodes
+ * and nvars only, so a sample's row does not depend on first / count).  No atomics, no allocation, no host
+ * synchronisation.  NLAM_EINVAL (before any launch) for null pointers, sizes < 1, negative strides, samples outside
+ * [0, base_len * members), too short a lead-time axis (forecast: steps < row_begin + nrows), no pair to difference or a
+ * short workspace; NLAM_EUNSUP for nvars > NLAM_MOMENTS_MAX_VARS or a (nodes x nvars) block of 2^31 floats or more. */
+#define NLAM_MOMENTS_MAX_VARS 256   /* a workgroup's lanes keep fixed features: 4 * lanes elements per stride, lanes a multiple of nvars */
+typedef struct {
+    const float* series;
+    const float* mean;               /* (nvars) for step >= 1; NULL for step == 0 */
+    const float* std;                /* (nvars) for step >= 1; NULL for step == 0 */
+    double* workspace;               /* nlam_moments_workspace_doubles(nodes, nvars, count, step) doubles */
+    double* out_mean;                /* (count * max(step, 1), nvars) */
+    double* out_sq;                  /* (count * max(step, 1), nvars) */
+    int64_t workspace_doubles;
+    int64_t stride_sample, stride_step, stride_member;
+    int64_t n_times;                 /* analysis: time steps of the common axis; forecast: analysis times */
+    int64_t first, count;            /* flat sample range */
+    int32_t is_forecast, members;
+    int32_t steps;                   /* forecast: lead times of the resident series (ignored for analysis data) */
+    int32_t nodes, nvars;
+    int32_t row_begin, nrows;
+    int32_t step;                    /* 0: values; >= 1: standardized differences with this stride */
+} nlam_moments_t;
+int32_t nlam_window_moments(const nlam_moments_t* p, void* hip_stream);
+/* doubles of nlam_moments_t.workspace for these sizes; -1 (NLAM_EINVAL) for sizes out of range */
+int64_t nlam_moments_workspace_doubles(int32_t nodes, int32_t nvars, int64_t count, int32_t step);
 
 /* decoupled-weight-decay Adam on flat buffers; step_count is the 1-based step */
 int32_t nlam_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,

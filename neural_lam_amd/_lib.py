@@ -42,6 +42,7 @@ LOSS_MSE, LOSS_MAE, LOSS_WMSE, LOSS_WMAE, LOSS_NLL, LOSS_CRPS_GAUSS = 1, 2, 3, 4
 LOSS_MAX_VARS = 4096
 EVAL_MAX_MAPS = 32    # NLAM_EVAL_MAX_MAPS: lead times of one nlam_eval_metrics call's loss maps
 EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
+MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
 
 EXPORTS = [
     "nlam_abi_version",
@@ -97,6 +98,8 @@ EXPORTS = [
     "nlam_window_len",
     "nlam_window_batch",
     "nlam_window_batch_ens",
+    "nlam_window_moments",
+    "nlam_moments_workspace_doubles",
 ]
 
 
@@ -320,6 +323,33 @@ class WindowEns(C.Structure):
     ]
 
 
+class Moments(C.Structure):
+    """nlam_moments_t: per-sample means and second moments of a strided resident series."""
+    _fields_ = [
+        ("series", C.c_void_p),
+        ("mean", C.c_void_p),
+        ("std", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("out_mean", C.c_void_p),
+        ("out_sq", C.c_void_p),
+        ("workspace_doubles", C.c_int64),
+        ("stride_sample", C.c_int64),
+        ("stride_step", C.c_int64),
+        ("stride_member", C.c_int64),
+        ("n_times", C.c_int64),
+        ("first", C.c_int64),
+        ("count", C.c_int64),
+        ("is_forecast", C.c_int32),
+        ("members", C.c_int32),
+        ("steps", C.c_int32),
+        ("nodes", C.c_int32),
+        ("nvars", C.c_int32),
+        ("row_begin", C.c_int32),
+        ("nrows", C.c_int32),
+        ("step", C.c_int32),
+    ]
+
+
 class Loss(C.Structure):
     _fields_ = [
         ("pred", C.c_void_p),
@@ -509,6 +539,10 @@ def load():
     lib.nlam_window_batch.restype = i32
     lib.nlam_window_batch_ens.argtypes = [C.POINTER(WindowEns), vp]
     lib.nlam_window_batch_ens.restype = i32
+    lib.nlam_window_moments.argtypes = [C.POINTER(Moments), vp]
+    lib.nlam_window_moments.restype = i32
+    lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]
+    lib.nlam_moments_workspace_doubles.restype = i64
     lib.nlam_mlp_group_blocks.argtypes = [C.POINTER(C.c_int64), i32, C.POINTER(C.c_int32)]
     lib.nlam_mlp_group_blocks.restype = i32
     lib.nlam_mlp_fwd_group.argtypes = [C.POINTER(MlpFwd), i32, vp]

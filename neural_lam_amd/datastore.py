@@ -28,7 +28,10 @@ class SyntheticDatastore:
     """Regular ``nx x ny`` grid with ``num_state/num_forcing/num_static`` variables.
 
     Defaults follow SURVEY.md §8(d): standardisation mean 0 / std 1, one-step
-    difference mean 0 / std 1, static features ~ N(0,1) under ``seed``,
+    difference mean 0 / std 1, static features ~ N(0,1) under ``seed``;
+    ``state_stats`` / ``forcing_stats`` replace them (e.g. the dict of
+    ``neural_lam_amd.stats.compute_standardization_stats`` or
+    ``load_standardization_stats``),
     boundary = frame of ``boundary_width`` cells (``boundary="random"`` gives the
     random 0/1 mask of tests/dummy_datastore.py:163-166).
     """
@@ -46,6 +49,7 @@ class SyntheticDatastore:
         boundary_width: int = 10,
         seed: int = 0,
         state_stats: dict | None = None,
+        forcing_stats: dict | None = None,
     ):
         self.nx, self.ny = int(nx), int(ny)
         self._n = {"state": int(num_state), "forcing": int(num_forcing), "static": int(num_static)}
@@ -81,10 +85,14 @@ class SyntheticDatastore:
             for k, v in state_stats.items():
                 stats[k] = np.asarray(v, dtype=np.float32)
         self._state_stats = SimpleNamespace(**{k: _Values(v) for k, v in stats.items()})
-        self._forcing_stats = SimpleNamespace(
-            forcing_mean=_Values(np.zeros(num_forcing, np.float32)),
-            forcing_std=_Values(np.ones(num_forcing, np.float32)),
-        )
+        fstats = {
+            "forcing_mean": np.zeros(num_forcing, np.float32),
+            "forcing_std": np.ones(num_forcing, np.float32),
+        }
+        if forcing_stats:
+            for k, v in forcing_stats.items():
+                fstats[k] = np.asarray(v, dtype=np.float32)
+        self._forcing_stats = SimpleNamespace(**{k: _Values(v) for k, v in fstats.items()})
         self.step_length = datetime.timedelta(hours=3)
 
     # ---- the surface of SURVEY.md Appendix A ----
