@@ -301,7 +301,7 @@ int32_t nlam_max_width(void);
  *   by LDS-DMA into a 3-stage ring, bf16 operands read with the LDS transpose read): bit 0 = launches with bf16 operands
  *   (NLAM_F_A_BF16), bit 1 = fp32-operand one-term launches, bit 2 = fp32-class (three-term) launches; default 3.  With fp32 operands
  *   the kernel alone is no faster than the column-per-thread kernel of rounds 1-5 (profiles/round6/wgrad_check.log: one term 112 vs
- *   98 us without / 84 vs 102 us with the SiLU; three terms 67.9 vs 64.8 us at 57 616 x 256 x 256, bit-identical results); inside the
+ *   98 us without / 84 vs 102 us with the SiLU; three terms 67.9 vs 64.8 us at 57 616 x 256 x 256, bit-identical results without SiLU); inside the
  *   step the one-term form gains 1.2 % at cfg5 (profiles/round6/ab_wgrad_ldma_fp32.log), the three-term form nothing.  0 = the
  *   column-per-thread kernel everywhere. */
 #define NLAM_TUNE_WGRAD_LDMA 9
@@ -334,6 +334,25 @@ int32_t nlam_store_bf16_supported(const nlam_mlp_fwd_t* p);
 int32_t nlam_mlp_bwd_dz2_ld(const nlam_mlp_bwd_t* p);
 /* number of row slices (p->nparts) that fills the chip for this weight-gradient shape */
 int32_t nlam_wgrad_nparts(const nlam_wgrad_t* p);
+/* Kernel family nlam_wgrad launches for this call under the current tuning (host logic, no launch), or the NLAM_EINVAL /
+ * NLAM_EUNSUP nlam_wgrad would return.  nlam_wgrad switches on this code, so the two cannot disagree.  Any nparts >= 1 is
+ * served: slices without rows write zeros.  The LDS-DMA families (NLAM_WGP_DMA, NLAM_WGP_LDMA_*) fetch 16 bytes per lane: they
+ * are taken only when A, every source pointer and every nonzero source batch stride (in bytes) are 16-byte aligned and, for
+ * the bf16 LDS-DMA kernel, m and a bf16 source's width are multiples of 8; otherwise the call falls back to NLAM_WGP_NARROW /
+ * the wgrad_wbf_kernel code of the same flags.  bf16 operands need 4-byte aligned rows (NLAM_EINVAL otherwise) and the
+ * split-bf16 wide family (NLAM_EUNSUP otherwise). */
+#define NLAM_WGP_SMALLN     1   /* wgrad_smalln_kernel: one source of width <= 8, m % 4 == 0                        */
+#define NLAM_WGP_DMA        2   /* wgrad_dma_kernel: m and every width <= 64 and % 4                               */
+#define NLAM_WGP_NARROW     3   /* wgrad_kernel: m or a width not % 4 (blockIdx.y windows above 12 blocks)          */
+#define NLAM_WGP_WIDE       4   /* wgrad_wide_kernel: fp32 MFMA (no NLAM_F_MM_* bits), 128 x 128 windows           */
+#define NLAM_WGP_WBF        5   /* wgrad_wbf_kernel, fp32 operands, 128 x 128 windows                              */
+#define NLAM_WGP_WBF_BIG    6   /* wgrad_wbf_kernel, fp32 operands, 256 x 256 windows                              */
+#define NLAM_WGP_WBF_B      7   /* wgrad_wbf_kernel, bf16 operands, 128 x 128 windows                              */
+#define NLAM_WGP_WBF_B_BIG  8   /* wgrad_wbf_kernel, bf16 operands, 256 x 256 windows                              */
+#define NLAM_WGP_LDMA_B     9   /* wgrad_ldma_kernel, bf16 operands (NLAM_TUNE_WGRAD_LDMA bit 0)                   */
+#define NLAM_WGP_LDMA_1    10   /* wgrad_ldma_kernel, fp32 operands, one term (bit 1)                              */
+#define NLAM_WGP_LDMA_3    11   /* wgrad_ldma_kernel, fp32 operands, three terms (bit 2)                           */
+int32_t nlam_wgrad_plan(const nlam_wgrad_t* p);
 
 int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream);
 int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream);
@@ -457,6 +476,9 @@ typedef struct {
     int32_t _pad;
 } nlam_reduce_jobs_t;
 int32_t nlam_reduce_jobs(const nlam_reduce_jobs_t* jobs, void* hip_stream);
+/* waves per nlam_reduce_jobs workgroup (NLAM_RED_WAVES of the build): job element i sums parts [w per, (w + 1) per) in wave w,
+ * per = ceil(nparts / waves), and the waves' sums are added in wave order -- the summation order the results depend on */
+int32_t nlam_reduce_jobs_waves(void);
 
 /* Node-level product of the factorised edge MLP (NLAM_F_PRE_ADD) and its data gradient:
  *   out[r][h] (+)= sum_c x[r][c] * W[h * ldn + c * ldk],   r < rows, h < n, c < k

@@ -35,6 +35,8 @@ TUNE_WGRAD_LDMA_VAR = 10
 TUNE_WBF_EDGE = 11
 TUNE_WGRAD_MAX_WGS = 12
 TUNE_CHAIN_CUS = 13
+# nlam_wgrad_plan codes (include/nlam_hip.h): the kernel family nlam_wgrad launches
+WGP_SMALLN, WGP_DMA, WGP_NARROW, WGP_WIDE, WGP_WBF, WGP_WBF_BIG, WGP_WBF_B, WGP_WBF_B_BIG, WGP_LDMA_B, WGP_LDMA_1, WGP_LDMA_3 = range(1, 12)
 TILE_SPLIT = 1 << 30
 # training-loss kinds (NLAM_LOSS_*), keyed by the reference's metric names (metrics.DEFINED_METRICS)
 LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
@@ -56,6 +58,7 @@ EXPORTS = [
     "nlam_mlp_bwd_blocks",
     "nlam_mlp_bwd_dz2_ld",
     "nlam_wgrad_nparts",
+    "nlam_wgrad_plan",
     "nlam_mlp_fwd",
     "nlam_mlp_bwd",
     "nlam_mlp_pack_floats",
@@ -72,6 +75,7 @@ EXPORTS = [
     "nlam_store_bf16_supported",
     "nlam_reduce_partials",
     "nlam_reduce_jobs",
+    "nlam_reduce_jobs_waves",
     "nlam_wmse_fwd",
     "nlam_wmse_bwd",
     "nlam_adamw_step",
@@ -475,6 +479,8 @@ def load():
     lib.nlam_mlp_bwd_blocks.restype = i32
     lib.nlam_wgrad_nparts.argtypes = [C.POINTER(Wgrad)]
     lib.nlam_wgrad_nparts.restype = i32
+    lib.nlam_wgrad_plan.argtypes = [C.POINTER(Wgrad)]
+    lib.nlam_wgrad_plan.restype = i32
     lib.nlam_mlp_pack_floats.argtypes = [C.POINTER(PackJob), i32]
     lib.nlam_mlp_pack_floats.restype = i64
     lib.nlam_mlp_pack.argtypes = [vp, i32, vp]
@@ -507,6 +513,7 @@ def load():
     lib.nlam_reduce_partials.restype = i32
     lib.nlam_reduce_jobs.argtypes = [C.POINTER(ReduceJobs), vp]
     lib.nlam_reduce_jobs.restype = i32
+    lib.nlam_reduce_jobs_waves.restype = i32
     lib.nlam_wmse_fwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, i32, vp]
     lib.nlam_wmse_fwd.restype = i32
     lib.nlam_wmse_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, f32, vp, vp]

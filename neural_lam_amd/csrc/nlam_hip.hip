@@ -85,7 +85,7 @@
 namespace nlam_detail {   // launchers: external linkage, each defined in exactly one slice; arguments are already validated
 int32_t fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream);   // slice 1
 int32_t bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream);   // slice 2
-int32_t wgrad_narrow(const nlam_wgrad_t* p, hipStream_t stream);   // slice 2
+int32_t wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t stream);   // slice 2 (plan: nlam_wgrad_plan's code)
 int32_t fwd_wide(const nlam_mlp_fwd_t* p, hipStream_t stream);     // slice 3
 int32_t bwd_wide(const nlam_mlp_bwd_t* p, hipStream_t stream);     // slice 3
 int32_t fwd_wide_group(const nlam_mlp_fwd_t* ps, int n, hipStream_t stream);   // slice 3
@@ -95,7 +95,7 @@ int32_t bwd_check(const nlam_mlp_bwd_t* p);                        // argument c
 int32_t wgrad_wide(const nlam_wgrad_t* p, hipStream_t stream);     // slice 3
 int32_t fwd_wbf(const nlam_mlp_fwd_t* p, hipStream_t stream);      // slice 4
 int32_t bwd_wbf(const nlam_mlp_bwd_t* p, hipStream_t stream);      // slice 4
-int32_t wgrad_wbf(const nlam_wgrad_t* p, hipStream_t stream);      // slice 4
+int32_t wgrad_wbf(const nlam_wgrad_t* p, int plan, hipStream_t stream);      // slice 4 (plan: nlam_wgrad_plan's code)
 int32_t wgrad_wbf_group(const nlam_wgrad_t* ps, int n, hipStream_t stream);   // slice 4
 extern int wbf_min_supertiles;                                     // nlam_set_tuning (defined in slice 1)
 extern int wbf_half;                                               // nlam_set_tuning (defined in slice 1)
@@ -4876,6 +4876,9 @@ void launch_pack(const pack_jobs_t& jobs, hipStream_t stream) {
     hipLaunchKernelGGL(pack_a_kernel, dim3((int)blocks, jobs.njobs), dim3(256), 0, stream, jobs);
 }
 
+// one source of at most kSmallN columns: wgrad_smalln_kernel (streams A once)
+bool wgrad_is_smalln(const nlam_wgrad_t* p) { return p->nsrc == 1 && p->src[0].width <= kSmallN && p->m % 4 == 0; }
+
 bool wgrad_is_narrow_dma(const nlam_wgrad_t* p) {
     bool dma = (p->m % 4 == 0) && p->m <= 64;
     for (int s = 0; s < p->nsrc; ++s) dma = dma && (p->src[s].width % 4 == 0) && p->src[s].width <= 64;
@@ -4903,6 +4906,48 @@ int wgrad_windows(const nlam_wgrad_t* p) { return wgrad_windows_of(p, kWWin, kWW
 // i.e. a quarter of the partial-sum traffic (128 x 512 KB written and read back for a 20 MB node-level problem at d = 256)
 bool wgrad_wbf_big(const nlam_wgrad_t* p) {
     return p->m > 128 && (long)p->rows * p->batch >= (long)nlam_detail::wgrad_big_min_rows;
+}
+
+// The LDS-DMA kernels (wgrad_dma_kernel, wgrad_ldma_kernel) fetch 16 bytes per lane from A and from every source: those pointers
+// and every nonzero source batch stride (`sesz` bytes per source element) must be 16-byte aligned.
+bool wgrad_dma_aligned(const nlam_wgrad_t* p, int sesz) {
+    if ((reinterpret_cast<uintptr_t>(p->A) & 15) != 0) return false;
+    for (int s = 0; s < p->nsrc; ++s)
+        if ((reinterpret_cast<uintptr_t>(p->src[s].ptr) & 15) != 0 || ((p->src[s].bstride * sesz) & 15) != 0) return false;
+    return true;
+}
+
+// nlam_wgrad_plan under the LDS-DMA setting `ldma` (NLAM_TUNE_WGRAD_LDMA bits; nlam_wgrad_group plans with 0): every eligibility
+// test of the weight-gradient launchers lives here, they switch on the code
+int wgrad_plan_of(const nlam_wgrad_t* p, int ldma) {
+    if (p == nullptr || p->A == nullptr || p->partials == nullptr || p->nsrc < 1 || p->nsrc > NLAM_MAX_SRC) return NLAM_EINVAL;
+    int n = 0;
+    for (int s = 0; s < p->nsrc; ++s) n += p->src[s].width;
+    if (n != p->n || p->m < 1 || p->nparts < 1) return NLAM_EINVAL;
+    const bool abf = (p->flags & NLAM_F_A_BF16) != 0, sbf = (p->flags & NLAM_F_S_BF16) != 0;
+    if (wgrad_is_smalln(p)) return abf || sbf ? NLAM_EUNSUP : NLAM_WGP_SMALLN;
+    if (!wgrad_is_wide(p)) {   // fp32 kernels: bf16 operands are read by the split-bf16 wide family only
+        if (abf || sbf) return NLAM_EUNSUP;
+        return wgrad_is_narrow_dma(p) && wgrad_dma_aligned(p, 4) ? NLAM_WGP_DMA : NLAM_WGP_NARROW;
+    }
+    const int wns = wgrad_wbf_ns(p);
+    if (wns == 0) return abf || sbf ? NLAM_EUNSUP : NLAM_WGP_WIDE;
+    const bool big = wgrad_wbf_big(p), silu = (p->flags & NLAM_F_SILU_B) != 0;
+    if (abf || sbf) {
+        // dW1 = dz1^T [fp32 sources]: A bf16; dW2 = dz2^T silu(z1): A and the single un-gathered source bf16
+        if (wns != 1 || !abf || (sbf && (p->nsrc != 1 || p->src[0].idx != nullptr || !silu)) || (!sbf && silu)) return NLAM_EUNSUP;
+        // wgrad_wbf_kernel reads bf16 rows as 4-byte column pairs
+        if ((reinterpret_cast<uintptr_t>(p->A) & 3) != 0 ||
+            (sbf && ((reinterpret_cast<uintptr_t>(p->src[0].ptr) & 3) != 0 || (p->src[0].bstride & 1) != 0)))
+            return NLAM_EINVAL;
+        // wgrad_ldma_kernel fetches 8 bf16 columns per lane and predicates on the first: whole 8-column groups only
+        if (big && (ldma & 1) && p->m % 8 == 0 && (!sbf || p->src[0].width % 8 == 0) && wgrad_dma_aligned(p, sbf ? 2 : 4))
+            return NLAM_WGP_LDMA_B;
+        return big ? NLAM_WGP_WBF_B_BIG : NLAM_WGP_WBF_B;
+    }
+    if (big && ((wns == 1 && (ldma & 2)) || (wns == 3 && (ldma & 4))) && wgrad_dma_aligned(p, 4))
+        return wns == 1 ? NLAM_WGP_LDMA_1 : NLAM_WGP_LDMA_3;
+    return big ? NLAM_WGP_WBF_BIG : NLAM_WGP_WBF;
 }
 
 // workgroups of a grouped launch: kMaxGridBlocks dealt in proportion to the members' tiles, at least one each and never
@@ -5420,7 +5465,7 @@ int32_t nlam_wgrad_nparts(const nlam_wgrad_t* p) {
     const long minp = minp_cfg < 1 ? 1 : minp_cfg;
     if (np < minp && total_chunks > minp) np = minp;
     long cap = 512;
-    if (p->nsrc == 1 && p->src[0].width <= kSmallN && p->m % 4 == 0) np = (total_chunks + 3) / 4;   // streaming kernel: >= 128 rows per workgroup
+    if (wgrad_is_smalln(p)) np = (total_chunks + 3) / 4;   // streaming kernel: >= 128 rows per workgroup
     if (wgrad_is_wide(p)) {
         cap = 1024 / wgrad_windows(p);
         // 8-wave workgroups on 256 x 256 windows: at most NLAM_TUNE_WGRAD_MAX_WGS of them.  One per CU (256) until round 6; measured
@@ -6159,19 +6204,26 @@ int32_t nlam_detail::bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream) {
 #if NLAM_IN_TU(1)
 extern "C" {
 
+int32_t nlam_wgrad_plan(const nlam_wgrad_t* p) { return wgrad_plan_of(p, nlam_detail::wgrad_ldma); }
+
 int32_t nlam_wgrad(const nlam_wgrad_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_wgrad");
-    if (p == nullptr || p->A == nullptr || p->partials == nullptr || p->nsrc < 1 || p->nsrc > NLAM_MAX_SRC) return NLAM_EINVAL;
-    int n = 0;
-    for (int s = 0; s < p->nsrc; ++s) n += p->src[s].width;
-    if (n != p->n || p->m < 1 || p->nparts < 1) return NLAM_EINVAL;
+    const int plan = nlam_wgrad_plan(p);
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (!(p->nsrc == 1 && p->src[0].width <= kSmallN && p->m % 4 == 0) && wgrad_is_wide(p)) {
-        if (wgrad_wbf_ns(p) > 0) return nlam_detail::wgrad_wbf(p, stream);   // split-bf16 matrix path (nlam_wbf.inc)
-        if (p->flags & (NLAM_F_A_BF16 | NLAM_F_S_BF16)) return NLAM_EUNSUP;
-        return nlam_detail::wgrad_wide(p, stream);
+    switch (plan) {
+    case NLAM_WGP_SMALLN:
+    case NLAM_WGP_DMA:
+    case NLAM_WGP_NARROW: return nlam_detail::wgrad_narrow(p, plan, stream);
+    case NLAM_WGP_WIDE: return nlam_detail::wgrad_wide(p, stream);
+    case NLAM_WGP_WBF:
+    case NLAM_WGP_WBF_BIG:
+    case NLAM_WGP_WBF_B:
+    case NLAM_WGP_WBF_B_BIG:
+    case NLAM_WGP_LDMA_B:
+    case NLAM_WGP_LDMA_1:
+    case NLAM_WGP_LDMA_3: return nlam_detail::wgrad_wbf(p, plan, stream);   // split-bf16 matrix path (nlam_wbf.inc)
+    default: return plan < 0 ? plan : NLAM_EINVAL;
     }
-    return nlam_detail::wgrad_narrow(p, stream);
 }
 
 // n <= NLAM_MAX_GROUP weight gradients of ONE shape (m, sources and their widths, flags) in one grid: member k's row slices are
@@ -6180,16 +6232,14 @@ int32_t nlam_wgrad(const nlam_wgrad_t* p, void* hip_stream) {
 int32_t nlam_wgrad_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream) {
     NLAM_RANGE("nlam_wgrad_group");
     if (ps == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
+    // the members' plan without the LDS-DMA kernels: wgrad_wbf_kernel's (the grouped kernel shares its body)
+    const int plan0 = wgrad_plan_of(&ps[0], 0);
     for (int k = 0; k < n; ++k) {
         const nlam_wgrad_t* p = &ps[k];
-        if (p->A == nullptr || p->partials == nullptr || p->nsrc < 1 || p->nsrc > NLAM_MAX_SRC) return NLAM_EINVAL;
-        int w = 0;
-        for (int s = 0; s < p->nsrc; ++s) w += p->src[s].width;
-        if (w != p->n || p->m < 1 || p->nparts < 1 || p->nparts != nlam_wgrad_nparts(p)) return NLAM_EINVAL;
-        if ((p->nsrc == 1 && p->src[0].width <= kSmallN && p->m % 4 == 0) || !wgrad_is_wide(p) || wgrad_wbf_ns(p) == 0) return NLAM_EUNSUP;
-        if (p->flags & (NLAM_F_A_BF16 | NLAM_F_S_BF16)) return NLAM_EUNSUP;
-        if (p->m != ps[0].m || p->n != ps[0].n || p->nsrc != ps[0].nsrc || p->flags != ps[0].flags || wgrad_wbf_big(p) != wgrad_wbf_big(&ps[0]))
-            return NLAM_EUNSUP;
+        const int plan = wgrad_plan_of(p, 0);
+        if (plan == NLAM_EINVAL || p->nparts != nlam_wgrad_nparts(p)) return NLAM_EINVAL;
+        if ((plan != NLAM_WGP_WBF && plan != NLAM_WGP_WBF_BIG) || plan != plan0) return NLAM_EUNSUP;
+        if (p->m != ps[0].m || p->n != ps[0].n || p->nsrc != ps[0].nsrc || p->flags != ps[0].flags) return NLAM_EUNSUP;
         for (int s = 0; s < p->nsrc; ++s)
             if (p->src[s].width != ps[0].src[s].width) return NLAM_EUNSUP;
     }
@@ -6200,10 +6250,10 @@ int32_t nlam_wgrad_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream) {
 #endif
 
 #if NLAM_IN_TU(4)
-int32_t nlam_detail::wgrad_wbf(const nlam_wgrad_t* p, hipStream_t stream) {
+int32_t nlam_detail::wgrad_wbf(const nlam_wgrad_t* p, int plan, hipStream_t stream) {
         const int wns = wgrad_wbf_ns(p);
         // 256 x 256 windows (8 waves) when the output has more than 128 rows, 128 x 128 windows (4 waves) otherwise
-        const bool big = wgrad_wbf_big(p);
+        const bool big = plan != NLAM_WGP_WBF && plan != NLAM_WGP_WBF_B;
         const int winm = big ? 256 : 128, winn = big ? 256 : 128;
         const size_t lds = (size_t)2 * ((winm + winn) / 32) * wns * 1024;
         const dim3 grid(p->nparts, wgrad_windows_of(p, winm, winn));
@@ -6218,12 +6268,6 @@ int32_t nlam_detail::wgrad_wbf(const nlam_wgrad_t* p, hipStream_t stream) {
         if (big) NLAM_LAUNCH_WG_WBF(NS_, S_, 4, 2, 4); \
         else NLAM_LAUNCH_WG_WBF(NS_, S_, 2, 2, 2);     \
     } while (0)
-        const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
-        if (p->flags & (NLAM_F_A_BF16 | NLAM_F_S_BF16)) {   // operands stored as bf16 (layers running with NLAM_F_STORE_BF16)
-            // dW1 = dz1^T [fp32 sources]: A bf16; dW2 = dz2^T silu(z1): A and the single un-gathered source bf16
-            const bool sb = (p->flags & NLAM_F_S_BF16) != 0;
-            if (wns != 1 || (p->flags & NLAM_F_A_BF16) == 0 || (sb && (p->nsrc != 1 || p->src[0].idx != nullptr || !silu)) || (!sb && silu))
-                return NLAM_EUNSUP;
 #define NLAM_LAUNCH_WG_WBF_B(S_, WM_, WN_, NBW_, SB_)                                                                             \
     do {                                                                                                                          \
         int rc = set_lds(wgrad_wbf_kernel<1, S_, 1, WM_, WN_, NBW_, true, SB_>, lds);                                              \
@@ -6237,28 +6281,41 @@ int32_t nlam_detail::wgrad_wbf(const nlam_wgrad_t* p, hipStream_t stream) {
         if (rc != 0) return rc;                                                                                           \
         hipLaunchKernelGGL((wgrad_ldma_kernel<1, ABF_, SBF_, SILU_, R_, NB_>), grid, dim3(512), lds2, stream, *p);         \
     } while (0)
-            const int var = nlam_detail::wgrad_ldma_var;   // (rows per stage, ring depth) variants for A/B runs (NLAM_TUNE_WGRAD_LDMA_VAR)
+#define NLAM_LAUNCH_WG_LDMA3(SILU_, NB_)                                                                                  \
+    do {                                                                                                                  \
+        const size_t lds2 = WgLdma<false, false, SILU_, 16, NB_>::LDS;                                                     \
+        int rc = set_lds(wgrad_ldma_kernel<3, false, false, SILU_, 16, NB_>, lds2);                                        \
+        if (rc != 0) return rc;                                                                                           \
+        hipLaunchKernelGGL((wgrad_ldma_kernel<3, false, false, SILU_, 16, NB_>), grid, dim3(512), lds2, stream, *p);       \
+    } while (0)
+        const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
+        // operands stored as bf16 (layers running with NLAM_F_STORE_BF16): dW1 = dz1^T [fp32 sources] with A bf16, dW2 =
+        // dz2^T silu(z1) with A and the single un-gathered source bf16 (sb)
+        const bool sb = (p->flags & NLAM_F_S_BF16) != 0;
+        const int var = nlam_detail::wgrad_ldma_var;   // (rows per stage, ring depth) variants for A/B runs (NLAM_TUNE_WGRAD_LDMA_VAR)
+        switch (plan) {
+        case NLAM_WGP_LDMA_B:
             if (sb) {
-                if (big && (nlam_detail::wgrad_ldma & 1)) {
-                    if (var == 1) NLAM_LAUNCH_WG_LDMA(true, true, true, 32, 5);
-                    else if (var == 2) NLAM_LAUNCH_WG_LDMA(true, true, true, 16, 6);
-                    else if (var == 3) NLAM_LAUNCH_WG_LDMA(true, true, true, 16, 8);
-                    else NLAM_LAUNCH_WG_LDMA(true, true, true, 32, 4);
-                } else if (big) NLAM_LAUNCH_WG_WBF_B(true, 4, 2, 4, true);
-                else NLAM_LAUNCH_WG_WBF_B(true, 2, 2, 2, true);
+                if (var == 1) NLAM_LAUNCH_WG_LDMA(true, true, true, 32, 5);
+                else if (var == 2) NLAM_LAUNCH_WG_LDMA(true, true, true, 16, 6);
+                else if (var == 3) NLAM_LAUNCH_WG_LDMA(true, true, true, 16, 8);
+                else NLAM_LAUNCH_WG_LDMA(true, true, true, 32, 4);
             } else {
-                if (big && (nlam_detail::wgrad_ldma & 1)) {
-                    if (var == 1) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 4);
-                    else if (var == 2) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 5);
-                    else if (var == 3) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 6);
-                    else NLAM_LAUNCH_WG_LDMA(true, false, false, 32, 3);
-                } else if (big) NLAM_LAUNCH_WG_WBF_B(false, 4, 2, 4, false);
-                else NLAM_LAUNCH_WG_WBF_B(false, 2, 2, 2, false);
+                if (var == 1) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 4);
+                else if (var == 2) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 5);
+                else if (var == 3) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 6);
+                else NLAM_LAUNCH_WG_LDMA(true, false, false, 32, 3);
             }
-            return (int32_t)hipGetLastError();
-        }
-        if (wns == 1 && big && (nlam_detail::wgrad_ldma & 2)) {   // fp32 operands, one term (autocast launches without bf16 storage)
-            const int var = nlam_detail::wgrad_ldma_var;
+            break;
+        case NLAM_WGP_WBF_B_BIG:
+            if (sb) NLAM_LAUNCH_WG_WBF_B(true, 4, 2, 4, true);
+            else NLAM_LAUNCH_WG_WBF_B(false, 4, 2, 4, false);
+            break;
+        case NLAM_WGP_WBF_B:
+            if (sb) NLAM_LAUNCH_WG_WBF_B(true, 2, 2, 2, true);
+            else NLAM_LAUNCH_WG_WBF_B(false, 2, 2, 2, false);
+            break;
+        case NLAM_WGP_LDMA_1:   // fp32 operands, one term (autocast launches without bf16 storage)
             if (silu) {
                 if (var >= 1) NLAM_LAUNCH_WG_LDMA(false, false, true, 16, 5);
                 else NLAM_LAUNCH_WG_LDMA(false, false, true, 16, 4);
@@ -6267,24 +6324,17 @@ int32_t nlam_detail::wgrad_wbf(const nlam_wgrad_t* p, hipStream_t stream) {
                 else if (var >= 2) NLAM_LAUNCH_WG_LDMA(false, false, false, 16, 5);
                 else NLAM_LAUNCH_WG_LDMA(false, false, false, 16, 3);
             }
-            return (int32_t)hipGetLastError();
-        }
-        if (wns == 3 && big && (nlam_detail::wgrad_ldma & 4)) {   // fp32 class: three terms on the LDS-DMA kernel
-#define NLAM_LAUNCH_WG_LDMA3(SILU_, NB_)                                                                                  \
-    do {                                                                                                                  \
-        const size_t lds2 = WgLdma<false, false, SILU_, 16, NB_>::LDS;                                                     \
-        int rc = set_lds(wgrad_ldma_kernel<3, false, false, SILU_, 16, NB_>, lds2);                                        \
-        if (rc != 0) return rc;                                                                                           \
-        hipLaunchKernelGGL((wgrad_ldma_kernel<3, false, false, SILU_, 16, NB_>), grid, dim3(512), lds2, stream, *p);       \
-    } while (0)
+            break;
+        case NLAM_WGP_LDMA_3:   // fp32 class: three terms on the LDS-DMA kernel
             if (silu) NLAM_LAUNCH_WG_LDMA3(true, 4);
             else NLAM_LAUNCH_WG_LDMA3(false, 4);
-            return (int32_t)hipGetLastError();
+            break;
+        default:   // NLAM_WGP_WBF / NLAM_WGP_WBF_BIG
+            if (wns == 1 && silu) NLAM_LAUNCH_WG_WBF2(1, true);
+            else if (wns == 1) NLAM_LAUNCH_WG_WBF2(1, false);
+            else if (silu) NLAM_LAUNCH_WG_WBF2(3, true);
+            else NLAM_LAUNCH_WG_WBF2(3, false);
         }
-        if (wns == 1 && silu) NLAM_LAUNCH_WG_WBF2(1, true);
-        else if (wns == 1) NLAM_LAUNCH_WG_WBF2(1, false);
-        else if (silu) NLAM_LAUNCH_WG_WBF2(3, true);
-        else NLAM_LAUNCH_WG_WBF2(3, false);
         return (int32_t)hipGetLastError();
     }
 #endif
@@ -6343,15 +6393,14 @@ int32_t nlam_detail::wgrad_wide(const nlam_wgrad_t* p, hipStream_t stream) {
 #endif
 
 #if NLAM_IN_TU(2)
-int32_t nlam_detail::wgrad_narrow(const nlam_wgrad_t* p, hipStream_t stream) {
-    if (p->nsrc == 1 && p->src[0].width <= kSmallN && p->m % 4 == 0) {
+int32_t nlam_detail::wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t stream) {
+    if (plan == NLAM_WGP_SMALLN) {
         hipLaunchKernelGGL(wgrad_smalln_kernel, dim3(p->nparts), dim3(256), 0, stream, *p);
         return (int32_t)hipGetLastError();
     }
-    const bool dma = wgrad_is_narrow_dma(p);
     int nb_total = 0;
     for (int s = 0; s < p->nsrc; ++s) nb_total += (p->src[s].width + 31) / 32;
-    if (dma) {
+    if (plan == NLAM_WGP_DMA) {
         const int nblocks = ((p->m + 31) / 32) * nb_total;
         const int nbw = (nblocks + 3) / 4;
         const size_t lds = (size_t)2 * (1 + p->nsrc) * kWgTile * sizeof(float);
@@ -6840,6 +6889,8 @@ int32_t nlam_reduce_partials(const float* partials, int32_t nparts, int64_t stri
                        (long)stride, n, out, accumulate);
     return (int32_t)hipGetLastError();
 }
+
+int32_t nlam_reduce_jobs_waves(void) { return kRedWaves; }
 
 int32_t nlam_reduce_jobs(const nlam_reduce_jobs_t* jobs, void* hip_stream) {
     NLAM_RANGE("nlam_reduce_jobs");

@@ -35,6 +35,7 @@ def test_library_exports_every_declared_symbol():
     assert lib.nlam_abi_version() == L.ABI_VERSION == 8
     assert lib.nlam_max_width() >= 64
     assert lib.nlam_num_blocks(1) == 1 and lib.nlam_num_blocks(10**6) == 256
+    assert 1 <= lib.nlam_reduce_jobs_waves() <= 16   # the reduction-order tests emulate this many waves
     # tuning knob: known key accepted (and restored), unknown key / negative value rejected
     assert lib.nlam_set_tuning(L.TUNE_WBF_MIN_SUPERTILES, 192) == 0
     assert lib.nlam_set_tuning(L.TUNE_WBF_MIN_SUPERTILES, -1) == -1 and lib.nlam_set_tuning(99, 1) == -1
@@ -548,3 +549,80 @@ def test_trainer_picks_its_executor_and_plans_bucket_launches_on_the_host():
         chain_params = {id(P[5])}
 
     assert tr._plan_buckets(SegChain()) == [[], [], [], [0, 1, 2, 3, 4, 5]]
+
+
+def test_wgrad_plan_query_covers_the_dispatch_table():
+    """nlam_wgrad_plan (host logic, no launch): the kernel family of every row of the weight-gradient dispatch, the LDS-DMA
+    eligibility guard (16-byte alignment, bf16 widths % 8) with its fallbacks, NLAM_EUNSUP / NLAM_EINVAL, and each tuning bit."""
+    lib = L.load()
+    EINVAL, EUNSUP = -1, -2
+    AL = 1 << 20   # an aligned (fake) address: nothing below reaches a kernel
+
+    def q(m, widths, rows=1000, batch=1, mm=0, silu=False, abf=False, sbf=False, A=AL, sptr=AL, bstride=0, idx=False):
+        d = L.Wgrad()
+        d.A, d.partials, d.m, d.batch, d.rows, d.nsrc, d.n = A, AL, m, batch, rows, len(widths), sum(widths)
+        d.flags = (mm << 8) | (L.F_SILU_B if silu else 0) | (L.F_A_BF16 if abf else 0) | (L.F_S_BF16 if sbf else 0)
+        for k, w in enumerate(widths):
+            d.src[k].ptr, d.src[k].width, d.src[k].bstride = sptr, w, bstride
+            d.src[k].idx = AL if idx else None
+        d.nparts = lib.nlam_wgrad_nparts(C.byref(d))
+        return lib.nlam_wgrad_plan(C.byref(d))
+
+    def tuned(key, value, fn):
+        assert lib.nlam_set_tuning(key, value) == 0
+        try:
+            return fn()
+        finally:
+            lib.nlam_set_tuning(L.TUNE_WGRAD_LDMA, 3)
+            lib.nlam_set_tuning(L.TUNE_WGRAD_BIG_MIN_ROWS, 0)
+
+    assert lib.nlam_wgrad_plan(None) == EINVAL
+    # each row of the table, default tuning
+    assert q(64, [3]) == q(132, [8], batch=3) == L.WGP_SMALLN
+    assert q(64, [60, 60, 12]) == q(32, [32], rows=15) == L.WGP_DMA
+    assert q(17, [256, 17]) == q(60, [30]) == q(66, [64]) == L.WGP_NARROW
+    assert q(132, [60, 60, 12]) == q(384, [256]) == L.WGP_WIDE
+    assert q(128, [128] * 3, mm=3) == q(96, [60, 60, 12], mm=1) == q(68, [256, 20], mm=3, silu=True) == L.WGP_WBF
+    assert q(260, [256], mm=3) == q(384, [132], mm=2, silu=True) == L.WGP_WBF_BIG
+    assert q(128, [128], mm=1, abf=True) == q(128, [128], mm=1, abf=True, sbf=True, silu=True) == L.WGP_WBF_B
+    assert q(256, [256], mm=1, abf=True) == q(384, [256], mm=1, abf=True, sbf=True, silu=True) == L.WGP_LDMA_B
+    assert q(264, [128, 64], mm=1, abf=True, idx=True) == L.WGP_LDMA_B
+    assert q(256, [256], mm=1) == q(260, [256, 12], mm=1, silu=True) == L.WGP_LDMA_1
+    assert q(256, [256], mm=3) == L.WGP_WBF_BIG                                       # bit 2 off by default
+    # the LDS-DMA guard: bf16 widths % 8, 16-byte aligned pointers and batch strides; otherwise the kernel of the same flags
+    assert q(132, [256], mm=1, abf=True) == L.WGP_WBF_B_BIG                            # m = 132: not whole 8-column groups
+    assert q(256, [132], mm=1, abf=True, sbf=True, silu=True) == L.WGP_WBF_B_BIG       # bf16 S of width 132
+    assert q(256, [256], mm=1, abf=True, A=AL + 8) == L.WGP_WBF_B_BIG                  # A 8 bytes off
+    assert q(256, [256], mm=1, abf=True, sbf=True, silu=True, bstride=256 * 1000 + 4) == L.WGP_WBF_B_BIG   # 8-byte bstride
+    assert q(256, [256], mm=1, abf=True, sptr=AL + 4) == L.WGP_WBF_B_BIG               # fp32 S 4 bytes off
+    assert q(256, [256], mm=1, A=AL + 8) == q(256, [256], mm=1, sptr=AL + 4) == L.WGP_WBF_BIG
+    assert q(256, [256], mm=1, bstride=256 * 1000 + 1, batch=2) == L.WGP_WBF_BIG     # odd batch stride
+    assert q(256, [256], mm=1, bstride=256 * 1000, batch=2) == L.WGP_LDMA_1
+    assert q(64, [64], A=AL + 4) == q(64, [64], sptr=AL + 8) == q(32, [32], bstride=1281, batch=3) == L.WGP_NARROW
+    # bf16 rows are read as 4-byte pairs: a 2-byte offset or an odd bf16 batch stride is an argument error
+    assert q(256, [256], mm=1, abf=True, A=AL + 2) == EINVAL
+    assert q(128, [128], mm=1, abf=True, sbf=True, silu=True, bstride=128 * 1000 + 1, batch=2) == EINVAL
+    # NLAM_EUNSUP: bf16 S without SiLU, bf16 S through a gather index, bf16 operands without a matrix mode or in the fp32 kernels,
+    # bf16 S without bf16 A, bf16 A with SiLU on fp32 sources, bf16 with three terms
+    assert q(256, [256], mm=1, abf=True, sbf=True) == EUNSUP
+    assert q(256, [256], mm=1, abf=True, sbf=True, silu=True, idx=True) == EUNSUP
+    assert q(256, [256], abf=True) == q(64, [64], abf=True) == q(64, [4], abf=True) == EUNSUP
+    assert q(256, [256], mm=1, sbf=True, silu=True) == EUNSUP
+    assert q(256, [256], mm=1, abf=True, silu=True) == EUNSUP
+    assert q(256, [256], mm=3, abf=True) == EUNSUP
+    # tuning: NLAM_TUNE_WGRAD_LDMA bits 0 / 1 / 2, NLAM_TUNE_WGRAD_BIG_MIN_ROWS
+    assert tuned(L.TUNE_WGRAD_LDMA, 2, lambda: q(256, [256], mm=1, abf=True)) == L.WGP_WBF_B_BIG
+    assert tuned(L.TUNE_WGRAD_LDMA, 2, lambda: q(256, [256], mm=1)) == L.WGP_LDMA_1
+    assert tuned(L.TUNE_WGRAD_LDMA, 1, lambda: q(256, [256], mm=1)) == L.WGP_WBF_BIG
+    assert tuned(L.TUNE_WGRAD_LDMA, 1, lambda: q(256, [256], mm=1, abf=True)) == L.WGP_LDMA_B
+    assert tuned(L.TUNE_WGRAD_LDMA, 4, lambda: q(256, [256], mm=3)) == L.WGP_LDMA_3
+    assert tuned(L.TUNE_WGRAD_LDMA, 4, lambda: q(256, [256], mm=3, A=AL + 4)) == L.WGP_WBF_BIG
+    assert tuned(L.TUNE_WGRAD_LDMA, 0, lambda: q(256, [256], mm=1, abf=True)) == L.WGP_WBF_B_BIG
+    assert tuned(L.TUNE_WGRAD_BIG_MIN_ROWS, 1001, lambda: q(256, [256], mm=1, abf=True)) == L.WGP_WBF_B
+    assert tuned(L.TUNE_WGRAD_BIG_MIN_ROWS, 1001, lambda: q(260, [256], mm=3)) == L.WGP_WBF
+    assert tuned(L.TUNE_WGRAD_BIG_MIN_ROWS, 1000, lambda: q(256, [256], mm=1)) == L.WGP_LDMA_1
+    # nlam_wgrad answers exactly what the plan says before any launch
+    d = L.Wgrad()
+    d.A, d.partials, d.m, d.batch, d.rows, d.nsrc, d.n, d.nparts, d.flags = AL, AL, 256, 1, 10, 1, 256, 1, (1 << 8) | L.F_S_BF16 | L.F_A_BF16
+    d.src[0].ptr, d.src[0].width = AL, 256
+    assert lib.nlam_wgrad_plan(C.byref(d)) == lib.nlam_wgrad(C.byref(d), None) == EUNSUP
