@@ -357,6 +357,22 @@ int32_t nlam_wgrad_plan(const nlam_wgrad_t* p);
 int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream);
 int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream);
 
+/* Tiled-GEMM family for any width (the widths above nlam_max_width() that nlam_mlp_fwd / nlam_mlp_bwd answer NLAM_EUNSUP for;
+ * widths <= 512 are accepted too, for comparisons).  Same structs and semantics as nlam_mlp_fwd / nlam_mlp_bwd -- gathered /
+ * concatenated sources (any width >= 1), SiLU or NLAM_F_NO_ACT, LayerNorm, NLAM_F_ADD_SRC0 / _SRC1, out / out_idx, segment
+ * aggregation (sum or NLAM_F_MEAN) over the tile schedule, dmode 0-3, z1 / xhat / rstd, dz1 / dz2, vec_partials -- run as a
+ * chain of kernels (LDS-tiled split-bf16 GEMMs, LayerNorm row kernels, fixed-order segment sums) over intermediates in `wpack`
+ * (wpack_floats >= the workspace query; nothing is packed, the weights are read in nn.Linear layout).  Matrix modes: one bf16
+ * term for NLAM_F_MM_BF16X1, three terms for every other mode (f32 and bf16x2 included).  Not served (NLAM_EUNSUP):
+ * NLAM_F_PRE_ADD, NLAM_F_STORE_BF16, NLAM_F_ACC_DSRC0, NLAM_F_LEAF_WGRAD, concatenated pieces (ncat > 0).  The backward needs
+ * z1, dz1 and dz2 (dz2_ld 0 or dout) and writes nlam_mlp_bwd_gemm_blocks(p) rows of vec_partials.  Workspace queries return
+ * the floats, or the NLAM_EINVAL / NLAM_EUNSUP the launch would return. */
+int64_t nlam_mlp_fwd_gemm_workspace_floats(const nlam_mlp_fwd_t* p);
+int64_t nlam_mlp_bwd_gemm_workspace_floats(const nlam_mlp_bwd_t* p);
+int32_t nlam_mlp_bwd_gemm_blocks(const nlam_mlp_bwd_t* p);
+int32_t nlam_mlp_fwd_gemm(const nlam_mlp_fwd_t* p, void* hip_stream);
+int32_t nlam_mlp_bwd_gemm(const nlam_mlp_bwd_t* p, void* hip_stream);
+
 /* Pre-packed weights for the narrow (hid, dout <= 64) split-bf16 kernels.  The reference's nn.Linear weights
  * (utils/networks.py:8-40) change once per optimizer step (models/module.py:293-304) but every fused-MLP workgroup of
  * every launch used to re-read them as fp32 and split them into bf16 terms itself.  nlam_mlp_pack writes, for a table of

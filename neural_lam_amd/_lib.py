@@ -61,6 +61,11 @@ EXPORTS = [
     "nlam_wgrad_plan",
     "nlam_mlp_fwd",
     "nlam_mlp_bwd",
+    "nlam_mlp_fwd_gemm_workspace_floats",
+    "nlam_mlp_bwd_gemm_workspace_floats",
+    "nlam_mlp_bwd_gemm_blocks",
+    "nlam_mlp_fwd_gemm",
+    "nlam_mlp_bwd_gemm",
     "nlam_mlp_pack_floats",
     "nlam_mlp_pack",
     "nlam_mlp_fwd_pack_records",
@@ -495,6 +500,16 @@ def load():
     lib.nlam_mlp_fwd.restype = i32
     lib.nlam_mlp_bwd.argtypes = [C.POINTER(MlpBwd), vp]
     lib.nlam_mlp_bwd.restype = i32
+    lib.nlam_mlp_fwd_gemm_workspace_floats.argtypes = [C.POINTER(MlpFwd)]
+    lib.nlam_mlp_fwd_gemm_workspace_floats.restype = i64
+    lib.nlam_mlp_bwd_gemm_workspace_floats.argtypes = [C.POINTER(MlpBwd)]
+    lib.nlam_mlp_bwd_gemm_workspace_floats.restype = i64
+    lib.nlam_mlp_bwd_gemm_blocks.argtypes = [C.POINTER(MlpBwd)]
+    lib.nlam_mlp_bwd_gemm_blocks.restype = i32
+    lib.nlam_mlp_fwd_gemm.argtypes = [C.POINTER(MlpFwd), vp]
+    lib.nlam_mlp_fwd_gemm.restype = i32
+    lib.nlam_mlp_bwd_gemm.argtypes = [C.POINTER(MlpBwd), vp]
+    lib.nlam_mlp_bwd_gemm.restype = i32
     lib.nlam_wgrad.argtypes = [C.POINTER(Wgrad), vp]
     lib.nlam_wgrad.restype = i32
     lib.nlam_segment_sum.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, i32, vp]
@@ -608,7 +623,7 @@ def check(rc: int, what: str):
         raise RuntimeError(f"{what} failed: {kind}")
 
 
-SLICES = (1, 2, 3, 4, 5)   # -DNLAM_TU=k translation-unit slices of csrc/nlam_hip.hip (see the comment at its top)
+SLICES = (1, 2, 3, 4, 5, 6)   # -DNLAM_TU=k translation-unit slices of csrc/nlam_hip.hip (see the comment at its top)
 
 
 def source_stamp() -> str:
@@ -626,7 +641,7 @@ def source_stamp() -> str:
 def build(verbose: bool = False, out: Path | None = None, defines=(), single_tu: bool | None = None) -> Path:
     """Compile csrc/nlam_hip.hip for gfx950 into the in-tree shared library.
 
-    Default: the five -DNLAM_TU=k slices are compiled in parallel (objects under csrc/_obj/, re-used when neither the
+    Default: the six -DNLAM_TU=k slices are compiled in parallel (objects under csrc/_obj/, re-used when neither the
     sources nor the flags changed) and linked.  ``single_tu=True`` (and any build with extra ``defines``, e.g. the
     NLAM_TIMING instrumentation) is the one-command build: one hipcc invocation, everything in one translation unit."""
     import hashlib

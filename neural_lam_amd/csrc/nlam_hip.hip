@@ -39,7 +39,7 @@
 // ---------------------------------------------------------------------------
 // Translation-unit slices.  Every kernel here is a template that is instantiated only where a launcher names it, so
 // the same source can be compiled several times with -DNLAM_TU=k, each time emitting one family's launchers (and with
-// them that family's kernels): the four objects build in parallel and link into one library (neural_lam_amd/_lib.py).
+// them that family's kernels): the objects build in parallel and link into one library (neural_lam_amd/_lib.py).
 // NLAM_TU undefined or 0 = everything in one translation unit (the one-command build of INTEGRATION.md, and the
 // -DNLAM_TIMING build, whose counters live in one device variable).
 //   1  C-ABI entry points, argument checks, HBM-bound helper kernels, narrow (d <= 64) forward
@@ -47,6 +47,7 @@
 //   3  fp32 MFMA kernels for 64 < d <= 512 (nlam_wide.inc)
 //   4  split-bf16 kernels for 64 < d <= 512 (nlam_wbf.inc)
 //   5  node-level linear kernels of the factorised edge MLP (nlam_linear)
+//   6  tiled-GEMM MLP family for widths above 512 (nlam_gemm.inc: nlam_mlp_fwd_gemm / nlam_mlp_bwd_gemm)
 // ---------------------------------------------------------------------------
 #ifndef NLAM_TU
 #define NLAM_TU 0
@@ -7123,4 +7124,8 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 
 #if NLAM_IN_TU(5)
 #include "nlam_stats.inc"
+#endif
+
+#if NLAM_IN_TU(6)
+#include "nlam_gemm.inc"
 #endif

@@ -261,7 +261,8 @@ def grouped_mlp_forward(pairs):
     def ok(m, x):
         # (wide members have no grouped kernel: they run one by one, through FusedMLP.forward and its input padding)
         return (isinstance(m, FusedMLP) and m.fully_fused and x.is_cuda and x.dim() == 2 and not x.requires_grad
-                and x.dtype == torch.float32 and max(m[0].out_features, m[2].out_features) <= PAD_EMBEDDER_MIN_WIDTH)
+                and x.dtype == torch.float32 and max(m[0].out_features, m[2].out_features) <= PAD_EMBEDDER_MIN_WIDTH
+                and not ops.uses_gemm_family(m[0].out_features, m[2].out_features, [x.shape[-1]]))
 
     outs = [None] * len(pairs)
     classes = {}
@@ -299,16 +300,18 @@ class SplitMLPs(nn.Module):
 
     @property
     def fully_fused(self) -> bool:
-        """Every chunk is a one-kernel MLP of the same shape: the chunked native path (ops.ChunkedMLPFunction) applies."""
+        """Every chunk is a one-kernel MLP of the same shape within the fused kernels' widths: the chunked native path
+        (ops.ChunkedMLPFunction) applies.  Wider chunks run one by one through FusedMLP (the tiled-GEMM family)."""
         first = self.mlps[0]
-        return all(isinstance(m, FusedMLP) and m.fully_fused and m.has_layer_norm == first.has_layer_norm
-                   and m[0].weight.shape == first[0].weight.shape and m[2].weight.shape == first[2].weight.shape for m in self.mlps)
+        return (all(isinstance(m, FusedMLP) and m.fully_fused and m.has_layer_norm == first.has_layer_norm
+                    and m[0].weight.shape == first[0].weight.shape and m[2].weight.shape == first[2].weight.shape for m in self.mlps)
+                and not ops.uses_gemm_family(first[0].out_features, first[2].out_features, []))
 
     def flat_params(self):
         return [q for m in self.mlps for q in m.params()]
 
     def forward(self, x):
-        if x.is_cuda and self.fully_fused and sum(self.chunk_sizes) == x.shape[-2]:
+        if x.is_cuda and self.fully_fused and sum(self.chunk_sizes) == x.shape[-2] and not ops.uses_gemm_family(0, 0, [x.shape[-1]]):
             # one launch per chunk on its row window of x, written into one output buffer: no split / cat copies
             key = ("plain", str(x.device))
             if getattr(self, "_geom", None) is None or self._geom[0] != key:
@@ -519,6 +522,8 @@ class InteractionNet(nn.Module):
             return False
         d, hid = edge_rep.shape[-1], self.edge_mlp[0].out_features
         dout = self.edge_mlp[2].out_features
+        if ops.uses_gemm_family(hid, dout, [d]):   # above the fused widths: no factorised kernel, the unfactorised launch
+            return False
         wide = max(d, hid, dout) > 64
         if self.propagates_sender or csr.num_edges < (FACTORISE_MIN_EDGES_WIDE if wide else FACTORISE_MIN_EDGES):
             return False

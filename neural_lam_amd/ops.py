@@ -757,6 +757,34 @@ def segment_sum(inp, in_bstride, ptr, order, scale, nseg, width, batch, out=None
     return out
 
 
+def uses_gemm_family(hid: int, dout: int, widths) -> bool:
+    """True when an MLP launch is wider than the fused kernels instantiate (nlam_max_width(): 512) and runs on the tiled-GEMM
+    family (nlam_mlp_fwd_gemm / nlam_mlp_bwd_gemm) instead; narrower launches never do."""
+    return max(int(hid), int(dout), *[int(w) for w in widths]) > _max_fused_width()
+
+
+_MAX_FUSED = None
+
+
+def _max_fused_width() -> int:
+    global _MAX_FUSED
+    if _MAX_FUSED is None:
+        _MAX_FUSED = int(L.load().nlam_max_width())
+    return _MAX_FUSED
+
+
+def _gemm_ws(n: int, what: str) -> int:
+    """A workspace query's answer: the floats, or the NLAM_E* code the launch would return (raised here, before any launch)."""
+    if n < 0:
+        L.check(int(n), what)
+    return int(n)
+
+
+def _gemm_mm(mm_flags):
+    """Matrix instruction of a tiled-GEMM launch (PROFILE metadata): one bf16 term in the bf16 mode, three terms otherwise."""
+    return ("bf16", 1) if (mm_flags >> 8) & 3 == 1 else ("bf16x3", 6)
+
+
 class FusedMLPFunction(torch.autograd.Function):
     """[gather|concat] -> Linear -> SiLU -> Linear -> [LayerNorm] -> residuals / aggregation.
 
@@ -792,6 +820,9 @@ class FusedMLPFunction(torch.autograd.Function):
         ntiles = geom.tiles.shape[0] if geom.tiles is not None else (rows + 31) // 32
         dev = srcs[0].device
         need_grad = any(ctx.needs_input_grad[1:])
+        gemm = uses_gemm_family(hid, dout, widths)   # wider than the fused kernels: the tiled-GEMM family (nlam_mlp_*_gemm)
+        if gemm and pre:
+            raise RuntimeError(f"factorised edge MLP at width {max(hid, dout, *widths)}: above nlam_max_width() the layer runs unfactorised")
 
         p = L.MlpFwd()
         for k in range(geom.nsrc):
@@ -818,7 +849,7 @@ class FusedMLPFunction(torch.autograd.Function):
         sbf = False
         if need_grad:
             # saved tensors as bf16 rows: bf16 autocast only, where forward, backward and both weight gradients have the kernels
-            sbf = (STORE_BF16 and mm_flags == _MM_FLAGS["bf16"] and torch.is_autocast_enabled("cuda")
+            sbf = (STORE_BF16 and not gemm and mm_flags == _MM_FLAGS["bf16"] and torch.is_autocast_enabled("cuda")
                    and bool(lib.nlam_store_bf16_supported(C.byref(p))))
             sdt = torch.bfloat16 if sbf else torch.float32
             if sbf:
@@ -830,11 +861,16 @@ class FusedMLPFunction(torch.autograd.Function):
                 rstd = torch.empty((B, rows), device=dev, dtype=torch.float32)
                 p.xhat, p.rstd = _ptr(xhat), _ptr(rstd)
         ctx.store_bf16 = sbf
-        nwp = lib.nlam_mlp_fwd_wpack_floats(C.byref(p))
-        bflags = _bwd_flags(mm_flags, narrow=nwp == 0)
+        ctx.gemm = gemm
+        nwp = 0 if gemm else lib.nlam_mlp_fwd_wpack_floats(C.byref(p))
+        bflags = mm_flags if gemm else _bwd_flags(mm_flags, narrow=nwp == 0)
         ctx.mm_flags = bflags   # backward reads nothing else
         pack = None
-        if nwp > 0:  # wide kernels: the weights in MFMA A-operand order -- packed once per step under a trainer, else scratch the launch fills
+        if gemm:   # intermediates (z2 / messages) in a scratch of its own; the weights are read as they are, nothing is packed
+            nws = _gemm_ws(lib.nlam_mlp_fwd_gemm_workspace_floats(C.byref(p)), "nlam_mlp_fwd_gemm_workspace_floats")
+            wpack = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
+            p.wpack, p.wpack_floats = _ptr(wpack), nws
+        elif nwp > 0:  # wide kernels: the weights in MFMA A-operand order -- packed once per step under a trainer, else scratch the launch fills
             wbuf = None
             if PACKER is not None and not geom.no_pack:
                 wbuf = PACKER.get_wide("f", p, nwp, ("f", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags) & ~L.F_STORE_BF16, int(p.ldw1),
@@ -864,13 +900,14 @@ class FusedMLPFunction(torch.autograd.Function):
             for t_ in (z1, xhat, rstd):
                 if t_ is not None:
                     nbytes += t_.numel() * t_.element_size()
-            name, mf = _mm_executed(mm_flags, hid, dout, widths, ragged_out_ok=ln_w is None and not geom.aggregate)
+            name, mf = _gemm_mm(mm_flags) if gemm else _mm_executed(mm_flags, hid, dout, widths, ragged_out_ok=ln_w is None and not geom.aggregate)
             k1 = widths[0] if pre else kin
             return {"flops": 2.0 * rows * B * (k1 * hid + hid * dout), "bytes": float(nbytes), "bytes_min": float(nmin), "mm": name, "mfmas_per_block": mf,
                     "what": ("gather + " if geom.nsrc == 3 else "") + ("factorised " if pre else "") + "Linear-SiLU-Linear" + ("-LayerNorm" if ln_w is not None else "")
                             + (" + segment aggregate" if geom.aggregate else "") + (" (saves z1/xhat/rstd)" if need_grad else "")}
 
-        L.check(PROFILE.launch(key, lambda: lib.nlam_mlp_fwd(C.byref(p), _stream()), fwd_meta), "nlam_mlp_fwd")
+        fwd_fn = lib.nlam_mlp_fwd_gemm if gemm else lib.nlam_mlp_fwd
+        L.check(PROFILE.launch(key, lambda: fwd_fn(C.byref(p), _stream()), fwd_meta), fwd_fn.__name__)
         if aggr is not None and geom.comb is not None:
             split_combine(aggr, geom)
             aggr = aggr[:, : geom.nseg_total]
@@ -972,6 +1009,7 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
         p.g_aggr, p.seg_of_row = _ptr(g_aggr), _ptr(geom.seg_of_row)
     p.rowptr, p.inv_deg = _ptr(geom.rowptr), _ptr(geom.inv_deg)
     p.z1, p.xhat, p.rstd = _ptr(z1), _ptr(xhat), _ptr(rstd)
+    gemm = bool(getattr(ctx, "gemm", False))   # the forward ran on the tiled-GEMM family: so does the backward
     sbf = bool(getattr(ctx, "store_bf16", False))   # the forward saved z1 / xhat as bf16 rows: dz1 / dz2 leave as bf16 too
     if sbf:
         p.flags = int(p.flags) | L.F_STORE_BF16
@@ -1001,8 +1039,8 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
             alloc = torch.zeros if geom.has_split else torch.empty
             dsrc[k] = alloc((B, nseg_rows, w), device=dev, dtype=torch.float32)
             p.dsrc[k], p.dsrc_bstride[k] = _ptr(dsrc[k]), nseg_rows * w
-    if sbf:
-        dz2, dpad = torch.empty((B * rows, dout), device=dev, dtype=torch.bfloat16), dout
+    if sbf or gemm:
+        dz2, dpad = torch.empty((B * rows, dout), device=dev, dtype=torch.bfloat16 if sbf else torch.float32), dout
         p.dz2, p.dz2_ld = _ptr(dz2), 0
     else:
         dz2, dpad = _alloc_dz2(lib, p, B * rows, dout, dev)   # (rows, dout); 32-padded columns for a ragged output width (output_map)
@@ -1018,7 +1056,7 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
         remaining = _ROLLOUT_USES.get(acc_key, 1) - 1
         _ROLLOUT_USES[acc_key] = remaining
         prev = _ROLLOUT_ACC.get(acc_key)
-        fam2 = (dsrc[0] is not None and int(p.dmode[0]) == 1 and lib.nlam_mlp_bwd_family(C.byref(p)) == 2
+        fam2 = (not gemm and dsrc[0] is not None and int(p.dmode[0]) == 1 and lib.nlam_mlp_bwd_family(C.byref(p)) == 2
                 and (prev is None or prev.shape == dsrc[0].shape))
         if prev is None:
             if remaining > 0 and fam2:
@@ -1036,9 +1074,13 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
             _ROLLOUT_ACC.pop(acc_key, None)
             if acc_report == "flush":
                 acc_report = prev
-    nwp = lib.nlam_mlp_bwd_wpack_floats(C.byref(p))
+    nwp = 0 if gemm else lib.nlam_mlp_bwd_wpack_floats(C.byref(p))
     wpack = None
-    if nwp > 0:
+    if gemm:
+        nws = _gemm_ws(lib.nlam_mlp_bwd_gemm_workspace_floats(C.byref(p)), "nlam_mlp_bwd_gemm_workspace_floats")
+        wpack = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
+        p.wpack, p.wpack_floats = _ptr(wpack), nws
+    elif nwp > 0:
         wbuf = None
         if PACKER is not None and not geom.no_pack:
             wbuf = PACKER.get_wide("b", p, nwp, ("b", W1.data_ptr(), W2.data_ptr(), tuple(widths), hid, dout, int(p.flags) & ~(L.F_STORE_BF16 | L.F_ACC_DSRC0), int(p.ldw1),
@@ -1050,7 +1092,7 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
             p.wpack, p.wpack_floats = _ptr(wpack), nwp
     elif ctx.pack is not None and PACKER is not None and ctx.pack.packed_step == PACKER.step_id:
         p.wpack, p.wpack_floats = ctx.pack.bwd.data_ptr(), ctx.pack.bwd.numel()
-    nblk = lib.nlam_mlp_bwd_blocks(C.byref(p))
+    nblk = lib.nlam_mlp_bwd_gemm_blocks(C.byref(p)) if gemm else lib.nlam_mlp_bwd_blocks(C.byref(p))
     vs = _vec_stride(hid, dout)
     vecp = torch.empty((nblk, 4, vs), device=dev, dtype=torch.float32)
     p.vec_partials, p.vec_partials_rows, p.vec_stride = _ptr(vecp), nblk, vs
@@ -1083,13 +1125,15 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
         nmin = sum(t_.numel() * t_.element_size() for t_ in (g_out, g_aggr) if t_ is not None)
         nmin += sum(t_.numel() * 4 for t_ in dsrc if t_ is not None) + min(saved, rows * B * kin * 4)
         kin_live = sum(w_ for k_, w_ in enumerate(widths) if p.dmode[k_] != 0 and not (pre and k_ > 0))
-        name, mf = _mm_executed(ctx.mm_flags, hid, dout, [w_ for k_, w_ in enumerate(widths) if p.dmode[k_] != 0] or [hid],
-                                ragged_out_ok=dpad != dout)
+        name, mf = _gemm_mm(ctx.mm_flags) if gemm else _mm_executed(ctx.mm_flags, hid, dout, [w_ for k_, w_ in enumerate(widths) if p.dmode[k_] != 0] or [hid],
+                                                                     ragged_out_ok=dpad != dout)
         return {"flops": 2.0 * rows * B * (kin_live * hid + hid * dout), "bytes": float(nbytes), "bytes_min": float(nmin), "mm": name, "mfmas_per_block": mf,
                 "what": "LayerNorm/SiLU backward + dh = dz2 W2 + dx = dz1 W1 (data gradients; writes dz1, dz2 for the weight gradients)"}
 
+    bwd_fn = lib.nlam_mlp_bwd_gemm if gemm else lib.nlam_mlp_bwd
+
     def launch_data():
-        L.check(PROFILE.launch(key, lambda: lib.nlam_mlp_bwd(C.byref(p), _stream()), bwd_meta), "nlam_mlp_bwd")
+        L.check(PROFILE.launch(key, lambda: bwd_fn(C.byref(p), _stream()), bwd_meta), bwd_fn.__name__)
 
     if not whole_side:
         launch_data()
@@ -2643,7 +2687,8 @@ class CatMLPFunction(torch.autograd.Function):
                 rstd = torch.empty((B, N), device=dev, dtype=torch.float32)
                 p.xhat, p.rstd = _ptr(xhat), _ptr(rstd)
         pack = None
-        wide = lib.nlam_mlp_fwd_wpack_floats(C.byref(p)) > 0
+        gemm = uses_gemm_family(hid, dout, [kin])   # above the fused widths: concatenation, then the tiled-GEMM family
+        wide = gemm or lib.nlam_mlp_fwd_wpack_floats(C.byref(p)) > 0
         if not wide and PACKER is not None:
             pack = PACKER.get(W1c, W2c, [kin], hid, dout, False, 0, mm_flags)
             if pack is not None:
@@ -2668,11 +2713,14 @@ class CatMLPFunction(torch.autograd.Function):
             L.check(lib.nlam_concat(C.byref(q), _stream()), "nlam_concat")
             p.ncat, p.cat_out = 0, None
             _fill_src(p.src[0], catbuf, N * kin, kin, None)
-            nwp = lib.nlam_mlp_fwd_wpack_floats(C.byref(p))
+            if gemm:
+                nwp = _gemm_ws(lib.nlam_mlp_fwd_gemm_workspace_floats(C.byref(p)), "nlam_mlp_fwd_gemm_workspace_floats")
+            else:
+                nwp = lib.nlam_mlp_fwd_wpack_floats(C.byref(p))
             if nwp > 0:
                 wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
                 p.wpack, p.wpack_floats = _ptr(wpack), nwp
-            rc = lib.nlam_mlp_fwd(C.byref(p), _stream())
+            rc = (lib.nlam_mlp_fwd_gemm if gemm else lib.nlam_mlp_fwd)(C.byref(p), _stream())
         L.check(rc, "nlam_mlp_fwd (concatenated pieces)")
         if need_grad:
             ctx.geom, ctx.B, ctx.rows, ctx.ntiles = MlpGeometry(nsrc=1), B, N, (N + 31) // 32
@@ -2681,7 +2729,8 @@ class CatMLPFunction(torch.autograd.Function):
             ctx.twin_of = {}
             ctx.has_ln = ln_w is not None
             ctx.param_refs = (W1, b1, W2, b2, ln_w, ln_b)
-            bflags = _bwd_flags(mm_flags, narrow=not wide)
+            ctx.gemm = gemm
+            bflags = mm_flags if gemm else _bwd_flags(mm_flags, narrow=not wide)
             ctx.mm_flags, ctx.pack = bflags, _bwd_pack(pack, mm_flags, bflags, W1c, W2c, [kin], hid, dout, False, 0)
             ctx.widths, ctx.piece_shapes = widths, [tuple(x.shape) for x in pieces]
             if GRAD_LISTENER is not None:
