@@ -55,6 +55,10 @@
  *   nlam_adamw_step
  *       torch.optim.AdamW(lr, betas=(0.9, 0.95)) of models/module.py:293-304 on
  *       one flat fp32 parameter buffer.
+ *   nlam_grad_sumsq, nlam_grad_sumsq_workspace_doubles, nlam_adamw_step_controlled
+ *       the global gradient norm, and the AdamW update with clipping by that norm, a closed-form learning-rate schedule
+ *       and the skip of a non-finite step decided on the device (what Lightning's gradient_clip_val and LR scheduler
+ *       give the reference's loop), in launches whose arguments do not depend on the step.
  */
 #ifndef NLAM_HIP_H
 #define NLAM_HIP_H
@@ -815,6 +819,53 @@ int32_t nlam_adamw_step(float* param, const float* grad, float* exp_avg, float* 
 int32_t nlam_adamw_step_resident(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                                  float beta1, float beta2, float eps, float weight_decay, int32_t* step_count_dev,
                                  float* bias_corr_dev, float grad_scale, void* hip_stream);
+
+/* Sum of squares of `n` floats (the flat gradient): one pass with 16-byte loads, fp64 from the first element, a fixed-order
+ * reduction to one fp64 partial per workgroup in partials[0 .. nlam_grad_sumsq_workspace_doubles(n)) -- no atomics, so the
+ * same buffer gives the same bits on every run.  With `norm` non-null a one-wave launch behind it adds the partials in a
+ * fixed order and writes norm[0] = (float)(scale * sqrt(sum)). */
+int64_t nlam_grad_sumsq_workspace_doubles(int64_t n);
+int32_t nlam_grad_sumsq(const float* grad, int64_t n, double* partials, int64_t workspace_doubles, float scale, float* norm,
+                        void* hip_stream);
+
+/* nlam_adamw_step_resident with the decisions about the update taken on the device, in three launches none of whose
+ * arguments depends on the step (so they can be captured and replayed):
+ *   1. nlam_grad_sumsq's first launch over `grad`;
+ *   2. one wave: norm = grad_scale * sqrt(sum) (the norm of the averaged gradient).  Not finite and skip_nonfinite set: the
+ *      step count and bias corrections stay, control[3] = 1, control[4] += 1.  Otherwise the step count advances, the bias
+ *      corrections are left as nlam_adamw_step_resident leaves them, lr_t = lr * f(s) for s = step count - 1, and
+ *      coefficient = min(1, max_grad_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_);
+ *   3. the update of nlam_adamw_step_resident with lr_t and grad * grad_scale * coefficient; nothing is touched on a skip.
+ * Schedule (torch.optim.lr_scheduler.LambdaLR stepped after every optimizer step), W = warmup_steps, T = total_steps,
+ * r = min_ratio: f(s) = (s + 1) / W for s < W; otherwise with p = min(1, (s - W) / max(1, T - W)):
+ *   NLAM_SCHED_CONSTANT 1;  NLAM_SCHED_WARMUP_COSINE r + (1 - r) (1 + cos(pi p)) / 2;  NLAM_SCHED_WARMUP_LINEAR r + (1 - r)(1 - p)
+ * evaluated in fp64 and rounded once.  NLAM_SCHED_NONE: lr_t = lr.  max_grad_norm <= 0: no clipping (coefficient 1).
+ * control: NLAM_OPTCTL_WORDS 4-byte words, zero before the first step:
+ *   [0] float lr_t  [1] float coefficient (0 on a skip)  [2] float norm  [3] int32 skip flag  [4] int32 skipped steps */
+#define NLAM_SCHED_NONE 0
+#define NLAM_SCHED_CONSTANT 1
+#define NLAM_SCHED_WARMUP_COSINE 2
+#define NLAM_SCHED_WARMUP_LINEAR 3
+#define NLAM_OPTCTL_WORDS 8
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int32_t* step_count_dev;
+    float* bias_corr_dev;
+    double* partials;                /* nlam_grad_sumsq_workspace_doubles(n) doubles */
+    void* control;
+    int64_t n;
+    int64_t partials_doubles;
+    float lr, beta1, beta2, eps, weight_decay, grad_scale;
+    float max_grad_norm;
+    float min_ratio;
+    int32_t schedule;                /* NLAM_SCHED_* */
+    int32_t warmup_steps, total_steps;
+    int32_t skip_nonfinite;
+} nlam_optctl_t;
+int32_t nlam_adamw_step_controlled(const nlam_optctl_t* p, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,11 @@ LOSS_MAX_VARS = 4096
 EVAL_MAX_MAPS = 32    # NLAM_EVAL_MAX_MAPS: lead times of one nlam_eval_metrics call's loss maps
 EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
 MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
+# learning-rate schedules of nlam_adamw_step_controlled (NLAM_SCHED_*) and the words of its control block
+SCHED_KINDS = {"constant": 1, "warmup_cosine": 2, "warmup_linear": 3}
+SCHED_NONE = 0
+OPTCTL_WORDS = 8
+OPTCTL_LR, OPTCTL_COEF, OPTCTL_NORM, OPTCTL_SKIP, OPTCTL_SKIPPED = range(5)
 
 EXPORTS = [
     "nlam_abi_version",
@@ -109,6 +114,9 @@ EXPORTS = [
     "nlam_window_batch_ens",
     "nlam_window_moments",
     "nlam_moments_workspace_doubles",
+    "nlam_grad_sumsq_workspace_doubles",
+    "nlam_grad_sumsq",
+    "nlam_adamw_step_controlled",
 ]
 
 
@@ -435,6 +443,34 @@ class PackJob(C.Structure):
     ]
 
 
+class OptCtl(C.Structure):
+    """nlam_optctl_t: the AdamW update with norm, clipping, schedule and skip decided on the device."""
+    _fields_ = [
+        ("param", C.c_void_p),
+        ("grad", C.c_void_p),
+        ("exp_avg", C.c_void_p),
+        ("exp_avg_sq", C.c_void_p),
+        ("step_count_dev", C.c_void_p),
+        ("bias_corr_dev", C.c_void_p),
+        ("partials", C.c_void_p),
+        ("control", C.c_void_p),
+        ("n", C.c_int64),
+        ("partials_doubles", C.c_int64),
+        ("lr", C.c_float),
+        ("beta1", C.c_float),
+        ("beta2", C.c_float),
+        ("eps", C.c_float),
+        ("weight_decay", C.c_float),
+        ("grad_scale", C.c_float),
+        ("max_grad_norm", C.c_float),
+        ("min_ratio", C.c_float),
+        ("schedule", C.c_int32),
+        ("warmup_steps", C.c_int32),
+        ("total_steps", C.c_int32),
+        ("skip_nonfinite", C.c_int32),
+    ]
+
+
 class PackRec(C.Structure):
     _fields_ = [("bytes", C.c_ubyte * 64)]
 
@@ -565,6 +601,12 @@ def load():
     lib.nlam_window_moments.restype = i32
     lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]
     lib.nlam_moments_workspace_doubles.restype = i64
+    lib.nlam_grad_sumsq_workspace_doubles.argtypes = [i64]
+    lib.nlam_grad_sumsq_workspace_doubles.restype = i64
+    lib.nlam_grad_sumsq.argtypes = [vp, i64, vp, i64, f32, vp, vp]
+    lib.nlam_grad_sumsq.restype = i32
+    lib.nlam_adamw_step_controlled.argtypes = [C.POINTER(OptCtl), vp]
+    lib.nlam_adamw_step_controlled.restype = i32
     lib.nlam_mlp_group_blocks.argtypes = [C.POINTER(C.c_int64), i32, C.POINTER(C.c_int32)]
     lib.nlam_mlp_group_blocks.restype = i32
     lib.nlam_mlp_fwd_group.argtypes = [C.POINTER(MlpFwd), i32, vp]

@@ -79,6 +79,7 @@ def save_checkpoint(path, trainer_or_step, optimizer=None, *, epoch, global_step
         "lr_schedulers": [],
         NAMESPACE: {"format_version": FORMAT_VERSION, "extra": {} if extra is None else extra},
     }
+    ckpt[NAMESPACE].update(body.get(NAMESPACE, {}))   # a Trainer's optimizer controls (schedule, skipped steps), when it has any
     if hyper_parameters is not None:
         ckpt["hyper_parameters"] = hyper_parameters
     if path is not None and _rank(group) == 0:

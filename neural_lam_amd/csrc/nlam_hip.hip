@@ -7124,6 +7124,7 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 
 #if NLAM_IN_TU(5)
 #include "nlam_stats.inc"
+#include "nlam_optctl.inc"
 #endif
 
 #if NLAM_IN_TU(6)

@@ -1,0 +1,272 @@
+// Optimizer controls decided on the device (nlam_grad_sumsq, nlam_adamw_step_controlled): the global norm of the flat
+// gradient, the clip coefficient, the learning rate of a closed-form schedule and the skip of a non-finite step, by kernels
+// that sit in front of the AdamW update inside the captured step.  No launch argument depends on the step.
+//
+//   grad_sumsq_kernel     one pass over the gradient with 16-byte loads; fp64 from the first element (two fp64 operations per
+//                         fp32 element are far below what the stream delivers), lanes -> wave -> workgroup in a fixed order,
+//                         one fp64 partial per workgroup.  No atomics: the same buffer gives the same bits on every run.
+//   adamw_control_kernel  one wave: the partials in a fixed order, norm = grad_scale * sqrt(sum), the finiteness test, the
+//                         resident step count and bias corrections (adamw_prep_kernel's expressions), the schedule in fp64
+//                         rounded once, torch's clip coefficient; everything the update needs goes to a block of
+//                         NLAM_OPTCTL_WORDS words that the host may read later.
+//   adamw_ctl_kernel      adamw_kernel's arithmetic with lr and the clip coefficient read from that block; returns before
+//                         touching anything when the skip flag is up.
+// Included from nlam_hip.hip inside NLAM_IN_TU(5).
+
+namespace {
+
+constexpr int kSumsqThreads = 256;
+constexpr int kSumsqQuads = 4;   // 16-byte loads in flight per lane
+
+__host__ __device__ inline int sumsq_blocks(long n) {
+    const long per_wg = 4L * kSumsqThreads * kSumsqQuads;
+    const long need = n < 1 ? 1 : (n + per_wg - 1) / per_wg;
+    return (int)(need < kMaxGridBlocks ? need : kMaxGridBlocks);
+}
+
+// butterfly: every lane ends with the same sum, added in an order that depends on nothing but the lane numbers
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(kSumsqThreads) void grad_sumsq_kernel(const float* g, long n, double* partials) {
+    __shared__ double red[kSumsqThreads / 64];
+    const int tid = threadIdx.x;
+    // elements in front of the first 16-byte boundary and behind the last whole quad: lanes 0-2 / 3-5 of workgroup 0
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const long nq = (n - head) >> 2;
+    const long tail0 = head + 4 * nq;
+    const f32x4* q = reinterpret_cast<const f32x4*>(g + head);
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const long stride = (long)gridDim.x * kSumsqThreads;
+    long i = (long)blockIdx.x * kSumsqThreads + tid;
+    for (; i + (kSumsqQuads - 1) * stride < nq; i += kSumsqQuads * stride) {
+        f32x4 v[kSumsqQuads];
+#pragma unroll
+        for (int u = 0; u < kSumsqQuads; ++u) v[u] = q[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < kSumsqQuads; ++u) {
+            const double x0 = (double)v[u][0], x1 = (double)v[u][1], x2 = (double)v[u][2], x3 = (double)v[u][3];
+            a0 = fma(x0, x0, a0);
+            a1 = fma(x1, x1, a1);
+            a2 = fma(x2, x2, a2);
+            a3 = fma(x3, x3, a3);
+        }
+    }
+    for (; i < nq; i += stride) {
+        const f32x4 v = q[i];
+        const double x0 = (double)v[0], x1 = (double)v[1], x2 = (double)v[2], x3 = (double)v[3];
+        a0 = fma(x0, x0, a0);
+        a1 = fma(x1, x1, a1);
+        a2 = fma(x2, x2, a2);
+        a3 = fma(x3, x3, a3);
+    }
+    if (blockIdx.x == 0) {
+        if (tid < head) {
+            const double x = (double)g[tid];
+            a0 = fma(x, x, a0);
+        } else if (tid >= 3 && tail0 + (tid - 3) < n && tid < 6) {
+            const double x = (double)g[tail0 + (tid - 3)];
+            a0 = fma(x, x, a0);
+        }
+    }
+    const double w = wave_sum_f64((a0 + a1) + (a2 + a3));
+    if ((tid & 63) == 0) red[tid >> 6] = w;
+    __syncthreads();
+    if (tid == 0) {
+        double s = red[0];
+#pragma unroll
+        for (int k = 1; k < kSumsqThreads / 64; ++k) s += red[k];
+        partials[blockIdx.x] = s;
+    }
+}
+
+// the partials in a fixed order, by one wave: lane l adds l, l + 64, ... in order, then the butterfly
+__device__ __forceinline__ double partials_sum(const double* partials, int nparts) {
+    double s = 0.0;
+    for (int k = (int)(threadIdx.x & 63); k < nparts; k += 64) s += partials[k];
+    return wave_sum_f64(s);
+}
+
+__global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* partials, int nparts, float scale, float* norm) {
+    const double s = partials_sum(partials, nparts);
+    if (threadIdx.x == 0) norm[0] = (float)((double)scale * sqrt(s));
+}
+
+// f(s) of the header: LambdaLR's factor for the update that follows s earlier ones
+__device__ __forceinline__ double schedule_factor(int kind, long s, long W, long T, double r) {
+    if (s < W) return (double)(s + 1) / (double)W;
+    if (kind == NLAM_SCHED_CONSTANT) return 1.0;
+    const long span = T - W > 1 ? T - W : 1;
+    double p = (double)(s - W) / (double)span;
+    if (p > 1.0) p = 1.0;
+    if (kind == NLAM_SCHED_WARMUP_COSINE) return r + (1.0 - r) * 0.5 * (1.0 + cos(3.14159265358979323846 * p));
+    return r + (1.0 - r) * (1.0 - p);
+}
+
+struct OptCtlArgs {
+    const double* partials;
+    int32_t* step_count;
+    float* bias_corr;
+    float* ctl_f;      // the control block as floats: [0] lr_t, [1] clip coefficient, [2] norm
+    int32_t* ctl_i;    // and as words: [3] skip flag, [4] skipped steps
+    int nparts;
+    float lr, b1, b2, grad_scale, max_norm, min_ratio;
+    int kind, warmup, total, skip_nonfinite;
+};
+
+__global__ __launch_bounds__(64) void adamw_control_kernel(const OptCtlArgs a) {
+    const double sum = partials_sum(a.partials, a.nparts);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)((double)a.grad_scale * sqrt(sum));
+    const bool finite = fabsf(norm) <= 3.402823466e+38f;   // false for inf and nan
+    a.ctl_f[2] = norm;
+    if (a.skip_nonfinite && !finite) {
+        a.ctl_f[1] = 0.f;
+        a.ctl_i[3] = 1;
+        a.ctl_i[4] = a.ctl_i[4] + 1;
+        return;
+    }
+    const int t = *a.step_count + 1;
+    *a.step_count = t;
+    a.bias_corr[0] = 1.f - powf(a.b1, (float)t);
+    a.bias_corr[1] = sqrtf(1.f - powf(a.b2, (float)t));
+    float lr_t = a.lr;
+    if (a.kind != NLAM_SCHED_NONE)
+        lr_t = (float)((double)a.lr * schedule_factor(a.kind, (long)t - 1, a.warmup, a.total, (double)a.min_ratio));
+    float coef = 1.f;
+    if (a.max_norm > 0.f) {
+        const float c = a.max_norm / (norm + 1e-6f);   // torch.nn.utils.clip_grad_norm_
+        coef = c < 1.f ? c : 1.f;
+    }
+    a.ctl_f[0] = lr_t;
+    a.ctl_f[1] = coef;
+    a.ctl_i[3] = 0;
+}
+
+// One element of adamw_kernel with the roundings of the code the compiler makes of it: it fuses 1 - lr * wd into one fma (hoisted
+// here as `decay`) and nothing else, so every other product and sum is rounded on its own.  Contraction is switched off and the
+// one fma written out, because what the compiler fuses is its choice per kernel (it fused more in this one's unrolled quads):
+// coef = 1 and lr_t = lr then give adamw_kernel's bits (x * 1.0f is exact).
+__device__ __forceinline__ void adamw_ctl_one(float& pv, float gr, float& mo, float& vo, float decay, float step, float b1, float b2,
+                                              float eps, float bc2_sqrt, float gscale, float coef) {
+#pragma clang fp contract(off)
+    const float g = gr * gscale * coef;
+    pv *= decay;
+    const float mi = b1 * mo + (1.f - b1) * g;
+    const float vi = b2 * vo + (1.f - b2) * g * g;
+    mo = mi;
+    vo = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pv = pv - step * (mi / denom);
+}
+
+// nq quads from 16-byte aligned bases, then the n - 4 nq elements behind them
+__global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const float* grad, float* m, float* v, long n, long nq, float b1,
+                                                        float b2, float eps, float wd, float gscale, const float* bias_corr,
+                                                        const float* ctl_f, const int32_t* ctl_i) {
+    if (ctl_i[3] != 0) return;   // a non-finite step: parameters and moments stay as they are
+    const float lr = ctl_f[0], coef = ctl_f[1];
+    const float bc1 = bias_corr[0], bc2_sqrt = bias_corr[1];
+    const float decay = fmaf(-lr, wd, 1.f), step = lr / bc1;   // torch.optim.AdamW: decoupled decay first
+    f32x4* p4 = reinterpret_cast<f32x4*>(param);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(grad);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += stride) {
+        f32x4 pv = p4[i], mo = m4[i], vo = v4[i];
+        const f32x4 gr = g4[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float pk = pv[k], mk = mo[k], vk = vo[k];
+            adamw_ctl_one(pk, gr[k], mk, vk, decay, step, b1, b2, eps, bc2_sqrt, gscale, coef);
+            pv[k] = pk;
+            mo[k] = mk;
+            vo[k] = vk;
+        }
+        m4[i] = mo;
+        v4[i] = vo;
+        p4[i] = pv;
+    }
+    for (long idx = 4 * nq + (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
+        float pk = param[idx], mk = m[idx], vk = v[idx];
+        adamw_ctl_one(pk, grad[idx], mk, vk, decay, step, b1, b2, eps, bc2_sqrt, gscale, coef);
+        m[idx] = mk;
+        v[idx] = vk;
+        param[idx] = pk;
+    }
+}
+
+int32_t sumsq_launch(const float* grad, int64_t n, double* partials, int64_t workspace_doubles, hipStream_t stream, int* nparts) {
+    if (grad == nullptr || partials == nullptr || n < 0) return NLAM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(grad) & 3) != 0 || (reinterpret_cast<uintptr_t>(partials) & 7) != 0) return NLAM_EINVAL;
+    const int blocks = sumsq_blocks((long)n);
+    if (workspace_doubles < blocks) return NLAM_EINVAL;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(kSumsqThreads), 0, stream, grad, (long)n, partials);
+    *nparts = blocks;
+    return (int32_t)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nlam_grad_sumsq_workspace_doubles(int64_t n) {
+    if (n < 0) return NLAM_EINVAL;
+    return sumsq_blocks((long)n);
+}
+
+int32_t nlam_grad_sumsq(const float* grad, int64_t n, double* partials, int64_t workspace_doubles, float scale, float* norm,
+                        void* hip_stream) {
+    NLAM_RANGE("nlam_grad_sumsq");
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    int nparts = 0;
+    if (const int32_t rc = sumsq_launch(grad, n, partials, workspace_doubles, stream, &nparts)) return rc;
+    if (norm == nullptr) return 0;
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(64), 0, stream, (const double*)partials, nparts, scale, norm);
+    return (int32_t)hipGetLastError();
+}
+
+int32_t nlam_adamw_step_controlled(const nlam_optctl_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_adamw_step_controlled");
+    if (p == nullptr || p->param == nullptr || p->grad == nullptr || p->exp_avg == nullptr || p->exp_avg_sq == nullptr ||
+        p->step_count_dev == nullptr || p->bias_corr_dev == nullptr || p->control == nullptr || p->n < 0)
+        return NLAM_EINVAL;
+    if (p->schedule < NLAM_SCHED_NONE || p->schedule > NLAM_SCHED_WARMUP_LINEAR || p->warmup_steps < 0 || p->total_steps < 0 ||
+        !(p->min_ratio >= 0.f && p->min_ratio <= 1.f) || p->max_grad_norm != p->max_grad_norm)
+        return NLAM_EINVAL;
+    if (p->schedule == NLAM_SCHED_NONE && p->warmup_steps != 0) return NLAM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(p->control) & 3) != 0) return NLAM_EINVAL;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    int nparts = 0;
+    if (const int32_t rc = sumsq_launch(p->grad, p->n, p->partials, p->partials_doubles, stream, &nparts)) return rc;
+    OptCtlArgs a;
+    a.partials = p->partials;
+    a.step_count = p->step_count_dev;
+    a.bias_corr = p->bias_corr_dev;
+    a.ctl_f = reinterpret_cast<float*>(p->control);
+    a.ctl_i = reinterpret_cast<int32_t*>(p->control);
+    a.nparts = nparts;
+    a.lr = p->lr, a.b1 = p->beta1, a.b2 = p->beta2, a.grad_scale = p->grad_scale;
+    a.max_norm = p->max_grad_norm, a.min_ratio = p->min_ratio;
+    a.kind = p->schedule, a.warmup = p->warmup_steps, a.total = p->total_steps, a.skip_nonfinite = p->skip_nonfinite != 0;
+    hipLaunchKernelGGL(adamw_control_kernel, dim3(1), dim3(64), 0, stream, a);
+    if (p->n == 0) return (int32_t)hipGetLastError();
+    // quads only where all four buffers sit on a 16-byte boundary (the flat buffers do); element by element otherwise
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(p->param) | reinterpret_cast<uintptr_t>(p->grad) |
+                           reinterpret_cast<uintptr_t>(p->exp_avg) | reinterpret_cast<uintptr_t>(p->exp_avg_sq);
+    const long nq = (bits & 15) == 0 ? (long)(p->n >> 2) : 0L;
+    const long work = nq > 0 ? nq : (long)p->n;
+    long blocks = (work + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(adamw_ctl_kernel, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg, p->exp_avg_sq,
+                       (long)p->n, nq, p->beta1, p->beta2, p->eps, p->weight_decay, p->grad_scale, (const float*)p->bias_corr_dev,
+                       (const float*)a.ctl_f, (const int32_t*)a.ctl_i);
+    return (int32_t)hipGetLastError();
+}
+
+}  // extern "C"

@@ -2788,11 +2788,92 @@ def standardize(items, outs=None):
     return outs
 
 
+class LRSchedule:
+    """A closed-form learning-rate schedule that ``AdamWFlat`` evaluates ON THE DEVICE from its resident step count, so a
+    captured optimizer stays captured while the rate moves.  ``kind``: ``"constant"``, ``"warmup_cosine"`` or
+    ``"warmup_linear"``; ``warmup_steps`` = W, ``total_steps`` = T, ``min_ratio`` = r.  The update after ``s`` earlier
+    ones uses ``lr * factor(s)`` -- ``torch.optim.lr_scheduler.LambdaLR(opt, schedule.factor)`` stepped after every
+    ``opt.step()``:
+
+        f(s) = (s + 1) / W                        s < W
+        p    = min(1, (s - W) / max(1, T - W))    otherwise
+        constant 1;  warmup_cosine r + (1 - r) (1 + cos(pi p)) / 2;  warmup_linear r + (1 - r) (1 - p)"""
+
+    KINDS = ("constant", "warmup_cosine", "warmup_linear")
+
+    def __init__(self, kind, warmup_steps=0, total_steps=None, min_ratio=0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"unknown schedule {kind!r}: one of {', '.join(self.KINDS)}")
+        if int(warmup_steps) != warmup_steps or not 0 <= warmup_steps < 2**31:
+            raise ValueError(f"warmup_steps must be a step count, not {warmup_steps!r}")
+        if kind != "constant":
+            if total_steps is None:
+                raise ValueError(f"the {kind!r} schedule needs total_steps")
+            if int(total_steps) != total_steps or not 0 <= total_steps < 2**31:
+                raise ValueError(f"total_steps must be a step count, not {total_steps!r}")
+        if not 0.0 <= float(min_ratio) <= 1.0:
+            raise ValueError(f"min_ratio must lie in [0, 1], not {min_ratio!r}")
+        fields = dict(kind=kind, warmup_steps=int(warmup_steps), total_steps=None if total_steps is None else int(total_steps),
+                      min_ratio=float(min_ratio))
+        for k, v in fields.items():
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        # W, T, r and the kind are launch constants of a captured control kernel: a replay would not see a change
+        raise AttributeError(f"LRSchedule is immutable (cannot set {name!r}): build a new one and a new optimizer / Trainer")
+
+    def factor(self, s) -> float:
+        s, W, r = int(s), self.warmup_steps, self.min_ratio
+        if s < W:
+            return (s + 1) / W
+        if self.kind == "constant":
+            return 1.0
+        p = min(1.0, (s - W) / max(1, self.total_steps - W))
+        if self.kind == "warmup_cosine":
+            return r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * p))
+        return r + (1.0 - r) * (1.0 - p)
+
+    def state_dict(self) -> dict:
+        return dict(kind=self.kind, warmup_steps=self.warmup_steps, total_steps=self.total_steps, min_ratio=self.min_ratio)
+
+    def __repr__(self):
+        return f"LRSchedule({self.kind!r}, warmup_steps={self.warmup_steps}, total_steps={self.total_steps}, min_ratio={self.min_ratio})"
+
+
+def global_grad_norm(flat_grad, scale: float = 1.0):
+    """``scale * ||flat_grad||_2`` as a 0-dim fp32 device tensor, with no host synchronisation (it can be captured): one
+    pass with fp64 sums in a fixed order (``nlam_grad_sumsq``), bit-identical from run to run.  What
+    ``torch.nn.utils.clip_grad_norm_`` returns for the one flat gradient of the drop-in path."""
+    _require_gpu(flat_grad)
+    if flat_grad.dtype != torch.float32 or not flat_grad.is_contiguous():
+        raise RuntimeError(f"global_grad_norm: a contiguous fp32 tensor is needed, not {flat_grad.dtype} / strides {flat_grad.stride()}")
+    lib = L.load()
+    n = flat_grad.numel()
+    nws = int(lib.nlam_grad_sumsq_workspace_doubles(n))
+    partials = torch.empty((nws,), device=flat_grad.device, dtype=torch.float64)
+    norm = torch.empty((), device=flat_grad.device, dtype=torch.float32)
+    L.check(lib.nlam_grad_sumsq(_ptr(flat_grad), n, _ptr(partials), nws, float(scale), _ptr(norm), _stream()), "nlam_grad_sumsq")
+    return norm
+
+
 class AdamWFlat:
     """torch.optim.AdamW(lr, betas=(0.9, 0.95)) semantics (models/module.py:293-304)
-    on one flat fp32 buffer: a single HBM-bound kernel per step."""
+    on one flat fp32 buffer: a single HBM-bound kernel per step.
 
-    def __init__(self, flat_param, flat_grad, lr=1e-3, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-2):
+    Optimizer controls (all off by default; with none set ``step`` issues exactly the two launches of
+    ``nlam_adamw_step_resident``).  With any of them ``step`` is three launches -- the gradient's sum of squares, one wave
+    that decides, the update (``nlam_adamw_step_controlled``) -- none of whose arguments depends on the step, so the
+    optimizer stays inside a captured graph:
+
+    * ``max_grad_norm``: clip by global norm, ``torch.nn.utils.clip_grad_norm_``'s coefficient, taken from the norm of the
+      gradient AFTER the ``grad_scale`` (1 / world) average;
+    * ``lr_schedule``: an ``LRSchedule`` evaluated from the resident step count (``lr`` stays the base rate);
+    * ``skip_nonfinite``: a step whose gradient norm is inf / nan changes nothing -- parameters, moments, step count and bias
+      corrections stay -- and is counted in ``skipped_steps``.  The host mirror ``t`` then counts attempts, not updates:
+      ``step_count()`` reads the truth from the device."""
+
+    def __init__(self, flat_param, flat_grad, lr=1e-3, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 lr_schedule=None, skip_nonfinite=False):
         self.p, self.g = flat_param, flat_grad
         self.m = torch.zeros_like(flat_param)
         self.v = torch.zeros_like(flat_param)
@@ -2802,15 +2883,96 @@ class AdamWFlat:
         self.t = 0
         self.t_dev = torch.zeros((1,), device=flat_param.device, dtype=torch.int32)
         self.bc_dev = torch.zeros((2,), device=flat_param.device, dtype=torch.float32)
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be positive (or None), not {max_grad_norm!r}")
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise TypeError("lr_schedule must be an ops.LRSchedule (a host-driven scheduler sets opt.lr instead)")
+        # launch constants of the control kernel, fixed here (read-only properties below): a captured step carries them
+        self._max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._lr_schedule, self._skip_nonfinite = lr_schedule, bool(skip_nonfinite)
+        self._controlled = self._max_grad_norm is not None or lr_schedule is not None or self._skip_nonfinite
+        if self.controlled:
+            # the device block of nlam_optctl_t.control (lr_t, coefficient, norm as floats; skip flag, skipped steps as words)
+            self.ctl = torch.zeros((L.OPTCTL_WORDS,), device=flat_param.device, dtype=torch.int32)
+            self._ctl_f = self.ctl.view(torch.float32)
+            nws = int(L.load().nlam_grad_sumsq_workspace_doubles(flat_param.numel()))
+            self._partials = torch.zeros((nws,), device=flat_param.device, dtype=torch.float64)
+
+    # The controls are chosen at construction and cannot be assigned afterwards: they size the device blocks and are
+    # constants of a captured control launch, which a replay would go on using whatever the attribute said.  (``lr``,
+    # ``betas``, ``eps`` and ``wd`` stay assignable: the trainer watches those, see ``Trainer._opt_signature``.)
+    max_grad_norm = property(lambda self: self._max_grad_norm)
+    lr_schedule = property(lambda self: self._lr_schedule)
+    skip_nonfinite = property(lambda self: self._skip_nonfinite)
+    controlled = property(lambda self: self._controlled)
 
     def step(self, grad_scale: float = 1.0):
         """One update (eager or inside a stream capture).  A caller that REPLAYS a captured step calls ``note_replayed``."""
         self.t += 1
+        if self.controlled:
+            return self._step_controlled(grad_scale)
         rc = L.load().nlam_adamw_step_resident(
             _ptr(self.p), _ptr(self.g), _ptr(self.m), _ptr(self.v), self.p.numel(), self.lr, self.betas[0],
             self.betas[1], self.eps, self.wd, _ptr(self.t_dev), _ptr(self.bc_dev), grad_scale, _stream(),
         )
         L.check(rc, "nlam_adamw_step_resident")
+
+    def _step_controlled(self, grad_scale):
+        c, sch = L.OptCtl(), self.lr_schedule
+        c.param, c.grad, c.exp_avg, c.exp_avg_sq = _ptr(self.p), _ptr(self.g), _ptr(self.m), _ptr(self.v)
+        c.step_count_dev, c.bias_corr_dev = _ptr(self.t_dev), _ptr(self.bc_dev)
+        c.partials, c.control = _ptr(self._partials), _ptr(self.ctl)
+        c.n, c.partials_doubles = self.p.numel(), self._partials.numel()
+        c.lr, c.beta1, c.beta2, c.eps, c.weight_decay, c.grad_scale = self.lr, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale
+        c.max_grad_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm
+        if sch is not None:
+            c.schedule, c.warmup_steps, c.min_ratio = L.SCHED_KINDS[sch.kind], sch.warmup_steps, sch.min_ratio
+            c.total_steps = 0 if sch.total_steps is None else sch.total_steps
+        else:
+            c.schedule = L.SCHED_NONE
+        c.skip_nonfinite = int(self.skip_nonfinite)
+        L.check(L.load().nlam_adamw_step_controlled(C.byref(c), _stream()), "nlam_adamw_step_controlled")
+
+    def _control_word(self, k, as_float):
+        if not self.controlled:
+            raise AttributeError("grad_norm / last_lr / skipped_steps exist with max_grad_norm, lr_schedule or skip_nonfinite set")
+        return (self._ctl_f if as_float else self.ctl)[k]
+
+    @property
+    def grad_norm(self):
+        """The last step's pre-clip norm of the averaged gradient: a 0-dim device tensor, read without a synchronise (a
+        view of the control block: ``clone()`` it to keep a step's value)."""
+        return self._control_word(L.OPTCTL_NORM, True)
+
+    @property
+    def last_lr(self):
+        """The learning rate the last applied update used (device tensor, as ``grad_norm``)."""
+        return self._control_word(L.OPTCTL_LR, True)
+
+    @property
+    def clip_coef(self):
+        """The factor the last step's gradient was multiplied with: 1 unless clipped, 0 for a skipped step."""
+        return self._control_word(L.OPTCTL_COEF, True)
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps the non-finite guard refused so far (reads the device counter: a synchronise)."""
+        return int(self.ctl[L.OPTCTL_SKIPPED].item()) if self.controlled else 0
+
+    def set_skipped_steps(self, n: int):
+        """Restore the device counter (checkpoints)."""
+        self.ctl[L.OPTCTL_SKIPPED : L.OPTCTL_SKIPPED + 1].fill_(n)
+
+    def step_count(self) -> int:
+        """Updates applied so far, from the device (with ``skip_nonfinite`` the mirror ``t`` also counts refused steps)."""
+        return int(self.t_dev.item())
+
+    def scheduled_lr(self, t=None) -> float:
+        """The rate update ``t + 1`` uses (``t``: updates applied, default ``step_count()``): where a torch scheduler
+        stepped after every update leaves ``param_groups[0]["lr"]``."""
+        if self.lr_schedule is None:
+            return self.lr
+        return self.lr * self.lr_schedule.factor(self.step_count() if t is None else t)
 
     capturable = True
 

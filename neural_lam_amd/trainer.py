@@ -405,7 +405,11 @@ class Trainer:
     def __init__(self, module: nn.Module, lr=1e-3, betas=(0.9, 0.95), weight_decay=1e-2, eps=1e-8,
                  bucket_bytes: int = 32 << 20, optimizer_factory=None, group=None, use_graph: bool = False,
                  overlap_wgrad: bool = True, early_leaf_backward: bool | None = None, grad_comm_dtype=None,
-                 executor: str | None = None, forks_per_segment: int | None = None):
+                 executor: str | None = None, forks_per_segment: int | None = None, max_grad_norm=None, lr_schedule=None,
+                 skip_nonfinite: bool = False):
+        """``max_grad_norm`` / ``lr_schedule`` (an ``ops.LRSchedule``) / ``skip_nonfinite``: the optimizer controls of
+        ``ops.AdamWFlat``, decided on the device inside the captured step.  A schedule given here never re-records anything
+        and never evicts the optimizer from the graph; setting ``opt.lr`` by hand keeps doing both (see ``_optimizer_changed``)."""
         import os
 
         self.module = module
@@ -440,8 +444,12 @@ class Trainer:
         if optimizer_factory is None:
             from .ops import AdamWFlat
 
-            self.opt = AdamWFlat(self.fp.flat, self.fp.grad, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+            self.opt = AdamWFlat(self.fp.flat, self.fp.grad, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                 max_grad_norm=max_grad_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
         else:
+            if max_grad_norm is not None or lr_schedule is not None or skip_nonfinite:
+                raise ValueError("max_grad_norm / lr_schedule / skip_nonfinite are options of the built-in AdamWFlat: an "
+                                 "optimizer_factory builds its own optimizer")
             self.opt = optimizer_factory(self.fp.flat, self.fp.grad)
         self._built_hyper = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)   # restored by restore_opt=False
 
@@ -685,7 +693,9 @@ class Trainer:
 
     def _opt_signature(self):
         """The optimizer's hyper-parameters are launch arguments of the captured AdamW kernel: a change (a learning-rate
-        schedule) must re-record it, or the replays would keep applying the old values."""
+        schedule) must re-record it, or the replays would keep applying the old values.  ``max_grad_norm``, ``lr_schedule`` and
+        ``skip_nonfinite`` are launch constants too, but read-only on ``AdamWFlat`` (and ``LRSchedule`` is immutable): they
+        cannot change after construction, so they need no place here."""
         o = self.opt
         captured = self._opt_in_graph or self._tail_graph is not None
         return tuple(getattr(o, k, None) for k in ("lr", "betas", "eps", "wd")) if captured else None
@@ -878,6 +888,27 @@ class Trainer:
 
     batch_times = None
 
+    # ---- optimizer controls (ops.AdamWFlat): device tensors of the last step, read without a synchronise ----
+    @property
+    def grad_norm(self):
+        return self.opt.grad_norm
+
+    @property
+    def last_lr(self):
+        return self.opt.last_lr
+
+    @property
+    def skipped_steps(self) -> int:
+        return self.opt.skipped_steps
+
+    @property
+    def global_step(self) -> int:
+        """Optimizer updates applied so far.  With ``skip_nonfinite`` the device counter decides (a refused step does not
+        count), which costs a synchronise; otherwise the host mirror is exact."""
+        if getattr(self.opt, "skip_nonfinite", False):
+            return self.opt.step_count()
+        return self.opt.t
+
     # ---- checkpoints (checkpoint.save_checkpoint / load_checkpoint) ----
     def _flat_adamw(self):
         ops = self._ops()
@@ -893,14 +924,22 @@ class Trainer:
     def state_dict(self) -> dict:
         """``{"state_dict", "optimizer_states": [sd]}`` with CPU tensors; ``sd`` is what ``torch.optim.AdamW`` over the
         reference module's parameters would hold (one entry per parameter, in ``named_parameters()`` order)."""
-        from .checkpoint import export_flat_state, module_state_to_cpu
+        from .checkpoint import NAMESPACE, export_flat_state, module_state_to_cpu
 
         opt = self._flat_adamw()
         names, shapes, offsets = self._layout()
         t = int(opt.t_dev.item())   # the device counter is the truth; ``t`` mirrors it
-        hyper = dict(lr=opt.lr, betas=opt.betas, eps=opt.eps, weight_decay=opt.wd)
-        return {"state_dict": module_state_to_cpu(self.module),
-                "optimizer_states": [export_flat_state(shapes, offsets, opt.m, opt.v, t, hyper)]}
+        hyper = dict(lr=opt.scheduled_lr(t), betas=opt.betas, eps=opt.eps, weight_decay=opt.wd)
+        out = {"state_dict": module_state_to_cpu(self.module),
+               "optimizer_states": [export_flat_state(shapes, offsets, opt.m, opt.v, t, hyper)]}
+        if opt.controlled:
+            # param_groups[0]["lr"] is the rate the NEXT update uses, where a torch scheduler leaves it; the base rate goes
+            # next to it under torch's own key, and the controls into this project's entry of the checkpoint
+            out["optimizer_states"][0]["param_groups"][0]["initial_lr"] = opt.lr
+            out[NAMESPACE] = {"optimizer_controls": {
+                "base_lr": opt.lr, "lr_schedule": None if opt.lr_schedule is None else opt.lr_schedule.state_dict(),
+                "max_grad_norm": opt.max_grad_norm, "skip_nonfinite": opt.skip_nonfinite, "skipped_steps": opt.skipped_steps}}
+        return out
 
     def load_state_dict(self, ckpt: dict, restore_opt: bool = True, strict: bool = True):
         """Load a reference-layout checkpoint (``checkpoint.load_checkpoint`` applies the legacy key remaps first) IN PLACE:
@@ -908,10 +947,12 @@ class Trainer:
         no buffer is rebound, so captured graphs, packed weight images (rewritten from the weights at the start of every
         step) and gradient buckets stay valid, and the next step equals a fresh trainer's.  Restored lr / betas / eps /
         weight decay that differ from a captured AdamW launch re-record it once, without counting as a schedule change; a
-        trainer already in schedule mode (optimizer uncaptured) simply launches with the new values.
+        trainer already in schedule mode (optimizer uncaptured) simply launches with the new values.  A checkpoint written
+        with optimizer controls also restores the base learning rate and the skipped-steps count; one written without them
+        loads as before.
         ``restore_opt=False``: weights only; step 0, zero moments and the hyper-parameters the trainer was built with.
         At world > 1 every rank loads, and one all-reduce of a checksum checks that the ranks hold the same state."""
-        from .checkpoint import import_flat_state, load_module_weights, reorder_optimizer_state
+        from .checkpoint import NAMESPACE, import_flat_state, load_module_weights, reorder_optimizer_state
 
         opt = self._flat_adamw()
         names, shapes, offsets = self._layout()
@@ -934,6 +975,21 @@ class Trainer:
         opt.t = t
         opt.t_dev.fill_(t)
         opt.lr, opt.betas, opt.eps, opt.wd = hyper["lr"], tuple(hyper["betas"]), hyper["eps"], hyper["weight_decay"]
+        # a checkpoint written with optimizer controls: its group's lr is the SCHEDULED rate at the saved step, the base rate
+        # is recorded beside it.  The schedule itself is a closed form of the restored step count and belongs to this
+        # trainer's constructor (as a LambdaLR's function does): the recorded one is checked against it, not loaded.
+        controls = (ckpt.get(NAMESPACE) or {}).get("optimizer_controls") if sd is not None else None
+        if controls is not None:
+            if getattr(opt, "lr_schedule", None) is not None:
+                opt.lr = float(controls["base_lr"])   # (a trainer without a schedule goes on at the rate the run had reached)
+            mine = None if getattr(opt, "lr_schedule", None) is None else opt.lr_schedule.state_dict()
+            if controls.get("lr_schedule") != mine:
+                import warnings
+
+                warnings.warn(f"the checkpoint was written under the learning-rate schedule {controls.get('lr_schedule')}, this "
+                              f"trainer runs {mine}: the run continues under this trainer's")
+        if getattr(opt, "controlled", False):
+            opt.set_skipped_steps(int(controls.get("skipped_steps", 0)) if controls is not None else 0)
         if self._graph is not None and (self._opt_in_graph or self._tail_graph is not None) and self._opt_signature() != self._opt_sig:
             changes, self._opt_changes = self._opt_changes, 0
             try:
