@@ -642,7 +642,8 @@ PROFILE = _LaunchProfile()
 
 
 def _ptr(t):
-    return None if t is None else t.data_ptr()
+    """Device address of a tensor; None and raw addresses pass through."""
+    return t.data_ptr() if isinstance(t, torch.Tensor) else t
 
 
 _MM_NAMES = {0: "f32", 1: "bf16", 2: "bf16x2", 3: "bf16x3"}
@@ -785,6 +786,133 @@ def _gemm_mm(mm_flags):
     return ("bf16", 1) if (mm_flags >> 8) & 3 == 1 else ("bf16x3", 6)
 
 
+# ---- from row gradients in HBM to dW / db / dgamma / dbeta: the one path every MLP backward takes ------------------------------------
+# nlam_wgrad[_group] writes row-slice partial sums (_wgrad_request), nlam_reduce_jobs sums them in a fixed order (_ReduceBatch)
+# either into a fresh tensor handed back to autograd or -- under a trainer, _direct_grad -- onto the parameter's .grad view.
+
+
+def _direct_grad(param, shape) -> bool:
+    """The gradient of ``param`` (of ``shape``) is accumulated straight into ``param.grad`` by the reduction launch instead of
+    being returned to autograd: only in a trainer's direct mode, for a leaf whose .grad is a contiguous fp32 tensor of that shape.
+    Under a trainer every parameter is a leaf whose .grad is an fp32 view of the flat gradient buffer with a matching shape: there
+    this is simply "direct mode and .grad is set".  Every site that decides where a gradient lands, or whether an MLP's weight
+    gradients may leave for a side stream, asks here, so that the two decisions cannot disagree."""
+    return (DIRECT_PARAM_GRADS and param is not None and param.is_leaf and param.grad is not None and param.grad.is_contiguous()
+            and tuple(param.grad.shape) == tuple(shape) and param.grad.dtype == torch.float32)
+
+
+def _all_direct(params, needs) -> bool:
+    """Every needed, non-None parameter of one MLP is direct for its own shape: nothing is returned to autograd."""
+    return all(q is None or not nd or _direct_grad(q, q.shape) for q, nd in zip(params, needs))
+
+
+class _ReduceBatch:
+    """Jobs of nlam_reduce_jobs launches on the current stream: each sums ``nparts`` partial results in a fixed order."""
+
+    def __init__(self, dev):
+        self.jobs, self.keep, self.dev = L.ReduceJobs(), [], dev
+
+    def reserve(self, n):
+        """Room for ``n`` more jobs in the pending launch (the jobs of one MLP stay in one launch)."""
+        if self.jobs.njobs + n > L.NLAM_MAX_REDUCE_JOBS:
+            self.flush()
+
+    def add(self, partials_ptr, nparts, stride, shape, param, *, ncols=0, out=None, out_off=0):
+        """One job for the gradient of ``param`` (of ``shape``) -> (destination, direct).  Direct (_direct_grad): accumulated
+        onto ``param.grad``; else written to a fresh tensor, which the caller returns to autograd.  ``ncols`` > 0: the partials
+        are a (shape[0], ncols) column block of the matrix, written at column ``out_off`` (into ``out`` when several blocks share
+        one destination; a fresh one is zeroed: the blocks need not cover it)."""
+        direct = _direct_grad(param, shape)
+        if out is None:
+            out = param.grad if direct else (torch.zeros if ncols else torch.empty)(tuple(shape), device=self.dev, dtype=torch.float32)
+        self.keep.append(out)
+        self.reserve(1)
+        j = self.jobs.job[self.jobs.njobs]
+        j.partials, j.out, j.stride, j.nparts, j.accumulate = partials_ptr, out.data_ptr() + 4 * out_off, stride, nparts, 1 if direct else 0
+        j.n, j.ncols, j.ld = (shape[0] * ncols, ncols, shape[1]) if ncols else (math.prod(shape), 0, 0)
+        self.jobs.njobs += 1
+        return out, direct
+
+    def flush(self):
+        if self.jobs.njobs > 0:
+            L.check(L.load().nlam_reduce_jobs(C.byref(self.jobs), _stream()), "nlam_reduce_jobs")
+            self.jobs.njobs = 0
+
+
+def _mlp_reduce_jobs(batch, part1, part2, vecp, nblk, vs, vec_rows, dims, params, needs, has_ln, ncols=0):
+    """The reduction jobs of one MLP's (dW1, db1, dW2, db2, dgamma, dbeta) -> the six results for autograd (None: not needed, or
+    direct).  ``part1`` / ``part2``: (nparts, m, n) partial sums of dW1 (``ncols`` > 0: of its leading column block) / dW2, None =
+    no job; the vector gradients are rows 0 .. 3 of the ``nblk`` blocks of ``vecp`` (``vec_rows`` rows of ``vs`` floats each)."""
+    hid, kin, dout = dims
+    res = [None] * 6
+    mat = lambda part: (_ptr(part), part.shape[0], part.shape[1] * part.shape[2])   # noqa: E731  (nparts, m, n) partial sums
+    vec = lambda r: (vecp.data_ptr() + r * vs * 4, nblk, vec_rows * vs)             # noqa: E731  row r of every block of vecp
+    # (a padded dz2 gives (dpad, hid) partials of dW2: the first dout rows are the gradient)
+    jobs = ((part1 is not None and mat(part1), (hid, kin)), (needs[1] and vec(0), (hid,)), (part2 is not None and mat(part2), (dout, hid)),
+            (needs[3] and vec(1), (dout,)), (has_ln and needs[4] and vec(2), (dout,)), (has_ln and needs[5] and vec(3), (dout,)))
+    for slot, (job, shape) in enumerate(jobs):
+        if job:
+            out, direct = batch.add(*job, shape, params[slot], ncols=ncols if slot == 0 else 0)
+            if not direct:
+                res[slot] = out
+    return res
+
+
+def _wgrad_request(A, m, n, B, rows, src_list, flags, dev):
+    """-> (nlam_wgrad_t, partials) of dW (m, n) = A^T [sources]: ``A`` the (B * rows, m) row gradients, ``src_list`` entries
+    (tensor | address, bstride, width, index tensor | address | None); ``partials`` (nparts, m, n) is what the launch writes."""
+    q = L.Wgrad()
+    q.A, q.m, q.batch, q.rows, q.nsrc, q.flags, q.n = _ptr(A), m, B, rows, len(src_list), flags, n
+    for k, (t, bstride, w, idx) in enumerate(src_list):
+        _fill_src(q.src[k], t, bstride, w, idx)
+    nparts = L.load().nlam_wgrad_nparts(C.byref(q))
+    partials = torch.empty((nparts, m, n), device=dev, dtype=torch.float32)
+    q.partials, q.nparts = _ptr(partials), nparts
+    return q, partials
+
+
+@dataclass
+class _WgradItem:
+    """What the weight gradients of one fused MLP are computed from, once its data-gradient launch has written dz1 / dz2 / vecp."""
+
+    B: int
+    rows: int
+    hid: int
+    dout: int
+    kin: int
+    mm_flags: int
+    dz1: torch.Tensor
+    dz2: torch.Tensor
+    z1: torch.Tensor
+    vecp: torch.Tensor
+    nblk: int
+    vs: int
+    src_list: list
+    params: tuple
+    needs: list
+    has_ln: bool
+
+
+def _wide_wpack(p, nwp, side, key, dev, use_packer=True):
+    """Give the wide launch ``p`` (MlpFwd for side "f", MlpBwd for "b") its ``nwp`` floats of weights in MFMA A-operand order:
+    the image the trainer's packer filled once for this step (``key``: its cache key), else scratch that the launch fills itself --
+    returned, for the caller to keep alive; None otherwise."""
+    wbuf = PACKER.get_wide(side, p, nwp, key) if (PACKER is not None and use_packer) else None
+    if wbuf is not None:
+        p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
+        return None
+    wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
+    p.wpack, p.wpack_floats = _ptr(wpack), nwp
+    return wpack
+
+
+def _unbatch_grad(g, shape, B):
+    """The (B, ...) gradient of a source of ``shape``: summed over the batch when the source had no batch dimension of its own."""
+    if math.prod(shape[:-2]) != B:
+        g = g.sum(0) if B > 1 else g[0]
+    return g.reshape(shape)
+
+
 class FusedMLPFunction(torch.autograd.Function):
     """[gather|concat] -> Linear -> SiLU -> Linear -> [LayerNorm] -> residuals / aggregation.
 
@@ -871,15 +999,8 @@ class FusedMLPFunction(torch.autograd.Function):
             wpack = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
             p.wpack, p.wpack_floats = _ptr(wpack), nws
         elif nwp > 0:  # wide kernels: the weights in MFMA A-operand order -- packed once per step under a trainer, else scratch the launch fills
-            wbuf = None
-            if PACKER is not None and not geom.no_pack:
-                wbuf = PACKER.get_wide("f", p, nwp, ("f", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags) & ~L.F_STORE_BF16, int(p.ldw1),
-                                                      rows, ntiles, B))
-            if wbuf is not None:
-                p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
-            else:
-                wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
-                p.wpack, p.wpack_floats = _ptr(wpack), nwp
+            wpack = _wide_wpack(p, nwp, "f", ("f", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags) & ~L.F_STORE_BF16, int(p.ldw1),
+                                              rows, ntiles, B), dev, not geom.no_pack)
         elif PACKER is not None and mm_flags != 0 and not geom.no_pack:   # narrow split-bf16 kernels under a trainer: the image packed once for this step
             pack = PACKER.get(W1c, W2c, widths, hid, dout, pre, kin if pre else 0, mm_flags)
             if pack is not None:
@@ -1081,15 +1202,8 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
         wpack = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
         p.wpack, p.wpack_floats = _ptr(wpack), nws
     elif nwp > 0:
-        wbuf = None
-        if PACKER is not None and not geom.no_pack:
-            wbuf = PACKER.get_wide("b", p, nwp, ("b", W1.data_ptr(), W2.data_ptr(), tuple(widths), hid, dout, int(p.flags) & ~(L.F_STORE_BF16 | L.F_ACC_DSRC0), int(p.ldw1),
-                                                  rows, ntiles, B, tuple(int(p.dmode[k]) for k in range(nsrc)), int(p.dz2_ld)))
-        if wbuf is not None:
-            p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
-        else:
-            wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
-            p.wpack, p.wpack_floats = _ptr(wpack), nwp
+        wpack = _wide_wpack(p, nwp, "b", ("b", W1.data_ptr(), W2.data_ptr(), tuple(widths), hid, dout, int(p.flags) & ~(L.F_STORE_BF16 | L.F_ACC_DSRC0), int(p.ldw1),
+                                          rows, ntiles, B, tuple(int(p.dmode[k]) for k in range(nsrc)), int(p.dz2_ld)), dev, not geom.no_pack)
     elif ctx.pack is not None and PACKER is not None and ctx.pack.packed_step == PACKER.step_id:
         p.wpack, p.wpack_floats = ctx.pack.bwd.data_ptr(), ctx.pack.bwd.numel()
     nblk = lib.nlam_mlp_bwd_gemm_blocks(C.byref(p)) if gemm else lib.nlam_mlp_bwd_blocks(C.byref(p))
@@ -1098,20 +1212,8 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
     p.vec_partials, p.vec_partials_rows, p.vec_stride = _ptr(vecp), nblk, vs
 
     prm = ctx.param_refs
-
-    def is_direct(param, shape):
-        return (
-            DIRECT_PARAM_GRADS and param is not None and param.is_leaf and param.grad is not None and param.grad.is_contiguous()
-            and tuple(param.grad.shape) == tuple(shape) and param.grad.dtype == torch.float32
-        )
-
-    wanted = [  # (slot, needs_grad, param, shape)
-        (0, needs[1], prm[0], (hid, kin)), (1, needs[2], prm[1], (hid,)),
-        (2, needs[3], prm[2], (dout, hid)), (3, needs[4], prm[3], (dout,)),
-        (4, ctx.has_ln and needs[5], prm[4], (dout,)),
-        (5, ctx.has_ln and needs[6], prm[5], (dout,)),
-    ]
-    on_side = OVERLAP.active and all(is_direct(pp, sh) for _, need, pp, sh in wanted if need)
+    pneeds = [needs[1], needs[2], needs[3], needs[4], ctx.has_ln and needs[5], ctx.has_ln and needs[6]]   # dW1, db1, dW2, db2, dgamma, dbeta
+    on_side = OVERLAP.active and _all_direct(prm, pneeds)
     whole_side = on_side and not any(needs[n_fixed:])
     key = ("mlp_bwd", rows * B, kin, hid, dout, nsrc, g_aggr is not None)
 
@@ -1185,13 +1287,7 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
 
     # ---- weight gradients: TN GEMMs with a deterministic two-stage reduction ----
     def wgrad(A, m, src_list, n, flags):
-        q = L.Wgrad()
-        q.A, q.m, q.batch, q.rows, q.nsrc, q.flags, q.n = _ptr(A), m, B, rows, len(src_list), flags | ctx.mm_flags | _wgrad_solo(), n
-        for k, (t, bstride, w, idx) in enumerate(src_list):
-            _fill_src(q.src[k], t, bstride, w, idx)
-        nparts = lib.nlam_wgrad_nparts(C.byref(q))
-        partials = torch.empty((nparts, m, n), device=dev, dtype=torch.float32)
-        q.partials, q.nparts = _ptr(partials), nparts
+        q, partials = _wgrad_request(A, m, n, B, rows, src_list, flags | ctx.mm_flags | _wgrad_solo(), dev)
         key = ("wgrad", rows * B, m, n)
 
         def wg_meta():
@@ -1216,47 +1312,14 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
     def launch_weights():
         part1 = wgrad(dz1, hid, src_list, kin1, L.F_A_BF16 if sbf else 0) if needs[1] else None
         part2 = wgrad(dz2, dpad, [(z1, rows * hid, hid, None)], hid, L.F_SILU_B | ((L.F_A_BF16 | L.F_S_BF16) if sbf else 0)) if needs[3] else None
-
         # ---- one launch reduces every partial sum; with DIRECT_PARAM_GRADS it accumulates into .grad ----
-        jobs = L.ReduceJobs()
-        keep = []
-
-        def add_job(slot, partials_ptr, nparts, stride, shape, param, ncols=0):
-            """``ncols`` > 0: the partials are the leading (shape[0], ncols) column block of the (shape) matrix."""
-            n = 1
-            for d_ in shape:
-                n *= d_
-            direct = is_direct(param, shape)
-            if direct:
-                out = param.grad
-            else:
-                out = (torch.zeros if ncols else torch.empty)(shape, device=dev, dtype=torch.float32)
-                results[slot] = out
-            keep.append(out)
-            j = jobs.job[jobs.njobs]
-            j.partials, j.out, j.stride, j.nparts, j.accumulate = partials_ptr, _ptr(out), stride, nparts, 1 if direct else 0
-            j.n, j.ncols, j.ld = (shape[0] * ncols, ncols, shape[1]) if ncols else (n, 0, 0)
-            jobs.njobs += 1
-
-        vbase = vecp.data_ptr()
-        if part1 is not None:
-            add_job(0, _ptr(part1), part1.shape[0], hid * kin1, (hid, kin), prm[0], ncols=kin1 if pre else 0)
-        if needs[2]:
-            add_job(1, vbase + 0 * vs * 4, nblk, 4 * vs, (hid,), prm[1])
-        if part2 is not None:   # a padded dz2 gives (dpad, hid) partials: the first dout rows are the gradient
-            add_job(2, _ptr(part2), part2.shape[0], dpad * hid, (dout, hid), prm[2])
-        if needs[4]:
-            add_job(3, vbase + 1 * vs * 4, nblk, 4 * vs, (dout,), prm[3])
-        if ctx.has_ln and needs[5]:
-            add_job(4, vbase + 2 * vs * 4, nblk, 4 * vs, (dout,), prm[4])
-        if ctx.has_ln and needs[6]:
-            add_job(5, vbase + 3 * vs * 4, nblk, 4 * vs, (dout,), prm[5])
-        if jobs.njobs > 0:
-            L.check(lib.nlam_reduce_jobs(C.byref(jobs), _stream()), "nlam_reduce_jobs")
+        batch = _ReduceBatch(dev)
+        results[:] = _mlp_reduce_jobs(batch, part1, part2, vecp, nblk, vs, 4, (hid, kin, dout), prm, pneeds, ctx.has_ln, ncols=kin1 if pre else 0)
+        batch.flush()
         if on_side:
             OVERLAP.hold(torch.cuda.current_stream(), part1, part2)
         if GRAD_LISTENER is not None:   # inside the side-stream context: a collective launched from here waits on it
-            GRAD_LISTENER.note_done([pp for _, need, pp, sh in wanted if need and is_direct(pp, sh)])
+            GRAD_LISTENER.note_done([q for q, nd in zip(prm, pneeds) if nd and q is not None and _direct_grad(q, q.shape)])
 
     # Where the launches go: weight gradients (needed only by the optimizer) on a side stream when the trainer owns the
     # parameter gradients (see _WgradOverlap); an MLP none of whose inputs needs a gradient is a dead end of backward, so
@@ -1272,19 +1335,7 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
     if isinstance(acc_report, torch.Tensor):
         # the held-back sum: reported as it is when this launch accumulated into it, added to this launch's own gradient when it could not
         dsrc[0] = acc_report if dsrc[0] is None else dsrc[0].add_(acc_report)
-    grads_src = []
-    for k in range(nsrc):
-        g = dsrc[k]
-        if g is not None:
-            b_, _ = ctx.binfo[k]
-            shape = ctx.src_shapes[k]
-            lead_numel = 1
-            for s in shape[:-2]:
-                lead_numel *= s
-            if lead_numel != B:  # source had no batch dim of its own
-                g = g.sum(0) if B > 1 else g[0]
-            g = g.reshape(shape)
-        grads_src.append(g)
+    grads_src = [None if g is None else _unbatch_grad(g, ctx.src_shapes[k], B) for k, g in enumerate(dsrc)]
     return (None, dW1, db1, dW2, db2, dg, dbt, *grads_src)
 
 
@@ -1316,6 +1367,20 @@ def _row_window(x: torch.Tensor):
     """(..., N, w) -> (tensor to keep alive, B, batch stride in floats): no copy for contiguous tensors and stride-0 batches."""
     t, B, bstride, _ = as_batched(x)
     return t, B, bstride
+
+
+def _chunk_sources(geom, bases, win_meta, widths, B, r0):
+    """The sources of the chunk that starts at row ``r0``, as (address, batch stride, width, index address | None) per source
+    (``win_meta``: (B, batch stride) of each, _row_window): what its launches and its weight-gradient request read."""
+    srcs = []
+    for k in range(geom.nsrc):
+        b_, bstride = win_meta[k]
+        bs = bstride if (b_ == B or B == 1) else 0
+        if geom.src_mode[k] == "slice":
+            srcs.append((bases[k].data_ptr() + 4 * r0 * widths[k], bs, widths[k], None))
+        else:
+            srcs.append((bases[k].data_ptr(), bs, widths[k], geom.src_idx[k].data_ptr() + 4 * r0))
+    return srcs
 
 
 class ChunkedMLPFunction(torch.autograd.Function):
@@ -1360,15 +1425,8 @@ class ChunkedMLPFunction(torch.autograd.Function):
                 saved.append((None, None, None))
                 continue
             p = L.MlpFwd()
-            for k in range(geom.nsrc):
-                t, b_, bstride = win[k]
-                bs = bstride if (b_ == B or B == 1) else 0
-                if geom.src_mode[k] == "slice":
-                    _fill_src(p.src[k], None, bs, widths[k], None)
-                    p.src[k].ptr = t.data_ptr() + 4 * r0 * widths[k]
-                else:
-                    _fill_src(p.src[k], t, bs, widths[k], None)
-                    p.src[k].idx = geom.src_idx[k].data_ptr() + 4 * r0
+            for k, src in enumerate(_chunk_sources(geom, [w[0] for w in win], [w[1:] for w in win], widths, B, r0)):
+                _fill_src(p.src[k], *src)
             p.nsrc, p.batch, p.rows, p.ntiles = geom.nsrc, B, rows, (rows + 31) // 32
             W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
             keep.extend((W1c, b1c, W2c, b2c))
@@ -1385,15 +1443,8 @@ class ChunkedMLPFunction(torch.autograd.Function):
                     p.xhat, p.rstd = _ptr(xhat), _ptr(rstd)
             nwp = lib.nlam_mlp_fwd_wpack_floats(C.byref(p))
             if nwp > 0:
-                wbuf = None
-                if PACKER is not None:   # packed once per step with every other wide MLP of the model (nlam_pack_records)
-                    wbuf = PACKER.get_wide("f", p, nwp, ("cf", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags), rows, B))
-                if wbuf is not None:
-                    p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
-                else:
-                    wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
-                    keep.append(wpack)
-                    p.wpack, p.wpack_floats = _ptr(wpack), nwp
+                # (under a trainer: packed once per step with every other wide MLP of the model, nlam_pack_records)
+                keep.append(_wide_wpack(p, nwp, "f", ("cf", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags), rows, B), dev))
             launches.append(p)
             saved.append((z1, xhat, rstd))
         _launch_chunks(lib, "fwd", launches)
@@ -1454,16 +1505,9 @@ class ChunkedMLPFunction(torch.autograd.Function):
             z1, xhat, rstd = ctx.saved_acts[c]
             W1c, W2c = W1.contiguous(), W2.contiguous()
             p = L.MlpBwd()
-            for k in range(nsrc):
-                b_, bstride = ctx.win_meta[k]
-                bs = bstride if (b_ == B or B == 1) else 0
-                t = ctx.bases[k]
-                if geom.src_mode[k] == "slice":
-                    _fill_src(p.src[k], None, bs, widths[k], None)
-                    p.src[k].ptr = t.data_ptr() + 4 * r0 * widths[k]
-                else:
-                    _fill_src(p.src[k], t, bs, widths[k], None)
-                    p.src[k].idx = geom.src_idx[k].data_ptr() + 4 * r0
+            src_list = _chunk_sources(geom, ctx.bases, ctx.win_meta, widths, B, r0)
+            for k, src in enumerate(src_list):
+                _fill_src(p.src[k], *src)
             p.nsrc, p.batch, p.rows, p.ntiles = nsrc, B, rows, (rows + 31) // 32
             p.W1, p.W2, p.ln_w = _ptr(W1c), _ptr(W2c), _ptr(ln_w) if ctx.has_ln else None
             p.hid, p.dout, p.flags, p.nseg_total = hid, dout, geom.flags_bwd | ctx.mm_flags, geom.num_rec
@@ -1493,21 +1537,14 @@ class ChunkedMLPFunction(torch.autograd.Function):
             nwp = lib.nlam_mlp_bwd_wpack_floats(C.byref(p))
             wpack = None
             if nwp > 0:
-                wbuf = None
-                if PACKER is not None:
-                    wbuf = PACKER.get_wide("b", p, nwp, ("cb", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags), rows, B,
-                                                          tuple(int(p.dmode[k]) for k in range(nsrc)), int(p.dz2_ld)))
-                if wbuf is not None:
-                    p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
-                else:
-                    wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
-                    p.wpack, p.wpack_floats = _ptr(wpack), nwp
+                wpack = _wide_wpack(p, nwp, "b", ("cb", W1c.data_ptr(), W2c.data_ptr(), tuple(widths), hid, dout, int(p.flags), rows, B,
+                                                  tuple(int(p.dmode[k]) for k in range(nsrc)), int(p.dz2_ld)), dev)
             nblk = lib.nlam_mlp_bwd_blocks(C.byref(p))
             vs = _vec_stride(hid, dout)
             vecp = torch.empty((nblk, 4, vs), device=dev, dtype=torch.float32)
             p.vec_partials, p.vec_partials_rows, p.vec_stride = _ptr(vecp), nblk, vs
             launches.append(p)
-            work.append((c, r0, rows, z1, dz1, dz2, vecp, vs, needs, (wpack, W1c, W2c)))
+            work.append((c, src_list, rows, z1, dz1, dz2, vecp, vs, needs, (wpack, W1c, W2c)))
         # data gradients: the chunks of the fp32 wide family in one grid, the others one launch each; `nblks` = the rows of
         # vec_partials every launch wrote
         nblks = _launch_chunks(lib, "bwd", launches)
@@ -1517,26 +1554,15 @@ class ChunkedMLPFunction(torch.autograd.Function):
         # the chain's next kernel is edge 7, and the graph executor (DESIGN finding 38) puts it on a hardware queue behind one
         # chunk's weight gradients -- 150 us of waiting per processor layer in the replayed cfg4p step ----
         done = {}
-        jobs, here = [], []
-        for (c, r0, rows, z1, dz1, dz2, vecp, vs, needs, _alive), nblk in zip(work, nblks):
-            prm = params[c]
-            direct_all = DIRECT_PARAM_GRADS and all(q is None or not nd or (q.grad is not None and q.grad.is_contiguous()) for q, nd in zip(prm, needs))
-            src_list = []
-            for k in range(nsrc):
-                b_, bstride = ctx.win_meta[k]
-                bs = bstride if (b_ == B or B == 1) else 0
-                t = ctx.bases[k]
-                if geom.src_mode[k] == "slice":
-                    src_list.append((t.data_ptr() + 4 * r0 * widths[k], bs, widths[k], None))
-                else:
-                    src_list.append((t.data_ptr(), bs, widths[k], geom.src_idx[k].data_ptr() + 4 * r0))
-            args = (lib, B, rows, hid, dout, kin, ctx.mm_flags, dz1, dz2, z1, vecp, nblk, vs, src_list, prm, needs, ctx.has_ln)
-            if OVERLAP.active and direct_all:   # (every gradient lands in the flat views: nothing to return)
-                jobs.append((args, (dz1, dz2, vecp, z1)))
+        side, here = [], []
+        for (c, src_list, rows, z1, dz1, dz2, vecp, vs, needs, _alive), nblk in zip(work, nblks):
+            item = _WgradItem(B, rows, hid, dout, kin, ctx.mm_flags, dz1, dz2, z1, vecp, nblk, vs, src_list, params[c], needs, ctx.has_ln)
+            if OVERLAP.active and DIRECT_PARAM_GRADS and _all_direct(params[c], needs):   # (every gradient lands in the flat views: nothing to return)
+                side.append(item)
                 done[c] = [None] * 6
             else:
-                here.append((c, args))
-        for (c, _), res in zip(here, _chunks_weight_grads([a for _, a in here]) if here else []):
+                here.append((c, item))
+        for (c, _), res in zip(here, _chunks_weight_grads([it for _, it in here]) if here else []):
             done[c] = res
         grads_params = []
         for c, (r0, r1) in enumerate(geom.chunks):
@@ -1556,17 +1582,11 @@ class ChunkedMLPFunction(torch.autograd.Function):
                     rowbuf = dbuf[k] if B == 1 else torch.cat(tmp_chunks[k], dim=1)
                     ptr, order, nseg = geom.scatter[k]
                     g = segment_sum(rowbuf, R * widths[k], ptr, order, None, nseg, widths[k], B)
-                shape = ctx.src_shapes[k]
-                lead_numel = 1
-                for s_ in shape[:-2]:
-                    lead_numel *= s_
-                if lead_numel != B:
-                    g = g.sum(0) if B > 1 else g[0]
-                g = g.reshape(shape)
+                g = _unbatch_grad(g, ctx.src_shapes[k], B)
             grads_src.append(g)
-        if jobs:   # forked behind the segment sums: those are the chain, and the fork takes their hardware queue (finding 38)
-            OVERLAP.run(jobs[0][0][14][0], tuple(t for _, held in jobs for t in held) + tuple(ctx.bases),
-                        lambda: _chunks_weight_grads([a for a, _ in jobs]))
+        if side:   # forked behind the segment sums: those are the chain, and the fork takes their hardware queue (finding 38)
+            OVERLAP.run(side[0].params[0], tuple(t for it in side for t in (it.dz1, it.dz2, it.vecp, it.z1)) + tuple(ctx.bases),
+                        lambda: _chunks_weight_grads(side))
         return (None, None, *grads_params, *grads_src)
 
 
@@ -1611,34 +1631,15 @@ def _launch_chunks(lib, which, launches):
 GROUP_WGRADS = os.environ.get("NLAM_GROUP_WGRADS", "1") == "1"
 
 
-def _chunk_weight_grads(lib, B, rows, hid, dout, kin, mm_flags, dz1, dz2, z1, vecp, nblk, vs, src_list, params, needs, has_ln):
-    """dW1, db1, dW2, db2, dgamma, dbeta of one fused MLP from the saved row gradients: two TN GEMMs (nlam_wgrad) + one
-    reduction launch; with a trainer's direct-gradient mode the sums land in the flat gradient views (returns None)."""
-    return _chunks_weight_grads([(lib, B, rows, hid, dout, kin, mm_flags, dz1, dz2, z1, vecp, nblk, vs, src_list, params, needs, has_ln)])[0]
-
-
 def _chunks_weight_grads(items):
-    """The weight gradients of several fused MLPs (``items``: argument tuples of ``_chunk_weight_grads``; the chunks of a
-    ``SplitMLPs`` layer, gnn_layers.py:311-324): every dW1 GEMM of one shape in ONE launch, every dW2 GEMM in one
-    (``nlam_wgrad_group``: members of the split-bf16 wide family; others one launch each), and the reductions of up to
-    NLAM_MAX_REDUCE_JOBS partial sums per launch -- 4 launches instead of 21 for the seven edge chunks of a Hi-LAM-Parallel
-    layer.  Per member the arithmetic is that of its own launch: the results are bit-identical.  Returns one 6-list per item."""
-    lib = items[0][0]
-    dev = items[0][7].device
-
-    def is_direct(param, shape):
-        return (DIRECT_PARAM_GRADS and param is not None and param.grad is not None and param.grad.is_contiguous()
-                and tuple(param.grad.shape) == tuple(shape) and param.grad.dtype == torch.float32)
-
-    def describe(A, m, slist, n, flags, B, rows):
-        q = L.Wgrad()
-        q.A, q.m, q.batch, q.rows, q.nsrc, q.flags, q.n = _ptr(A), m, B, rows, len(slist), flags, n
-        for k, (ptr, bstride, w, idx) in enumerate(slist):
-            q.src[k].ptr, q.src[k].idx, q.src[k].bstride, q.src[k].width = ptr, idx, bstride, w
-        nparts = lib.nlam_wgrad_nparts(C.byref(q))
-        partials = torch.empty((nparts, m, n), device=dev, dtype=torch.float32)
-        q.partials, q.nparts = _ptr(partials), nparts
-        return q, partials
+    """dW1, db1, dW2, db2, dgamma, dbeta of several fused MLPs from their saved row gradients (``items``: _WgradItem; the chunks
+    of a ``SplitMLPs`` layer, gnn_layers.py:311-324, or one member of a grouped launch): every dW1 GEMM of one shape in ONE launch,
+    every dW2 GEMM in one (``nlam_wgrad_group``: members of the split-bf16 wide family; others one launch each), and the
+    reductions of up to NLAM_MAX_REDUCE_JOBS partial sums per launch -- 4 launches instead of 21 for the seven edge chunks of a
+    Hi-LAM-Parallel layer.  Per member the arithmetic is that of its own launch: the results are bit-identical.  Returns one
+    6-list per item (None where, in a trainer's direct-gradient mode, the sum landed in the flat gradient view)."""
+    lib = L.load()
+    dev = items[0].dz1.device
 
     def launch(qs):
         """members of one shape share a grid, NLAM_MAX_GROUP at a time"""
@@ -1662,64 +1663,25 @@ def _chunks_weight_grads(items):
 
     parts = []
     q1s, q2s = [], []
-    for (_, B, rows, hid, dout, kin, mm_flags, dz1, dz2, z1, vecp, nblk, vs, src_list, params, needs, has_ln) in items:
+    for it in items:
         part1 = part2 = None
-        dpad = dz2.shape[1]   # dout, or 32-padded (zero columns) for a ragged output width: the first dout rows of the partials count
-        if needs[0]:
-            q, part1 = describe(dz1, hid, src_list, kin, mm_flags, B, rows)
+        if it.needs[0]:
+            q, part1 = _wgrad_request(it.dz1, it.hid, it.kin, it.B, it.rows, it.src_list, it.mm_flags, dev)
             q1s.append(q)
-        if needs[2]:
-            q, part2 = describe(dz2, dpad, [(z1.data_ptr(), rows * hid, hid, None)], hid, L.F_SILU_B | mm_flags, B, rows)
+        if it.needs[2]:   # dz2 is (rows, dout), or 32-padded (zero columns) for a ragged output width: the first dout rows of the partials count
+            q, part2 = _wgrad_request(it.dz2, it.dz2.shape[1], it.hid, it.B, it.rows, [(it.z1, it.rows * it.hid, it.hid, None)], L.F_SILU_B | it.mm_flags, dev)
             q2s.append(q)
-        parts.append((part1, part2, dpad))
+        parts.append((part1, part2))
     launch(q1s)
     launch(q2s)
 
-    all_results = []
-    jobs = L.ReduceJobs()
-    keep = []
-
-    def flush():
-        if jobs.njobs > 0:
-            L.check(lib.nlam_reduce_jobs(C.byref(jobs), _stream()), "nlam_reduce_jobs")
-            jobs.njobs = 0
-
-    done = []
-    for (_, B, rows, hid, dout, kin, mm_flags, dz1, dz2, z1, vecp, nblk, vs, src_list, params, needs, has_ln), (part1, part2, dpad) in zip(items, parts):
-        results = [None] * 6
-        if jobs.njobs + 6 > L.NLAM_MAX_REDUCE_JOBS:
-            flush()
-
-        def add_job(slot, partials_ptr, nparts, stride, shape, param):
-            n = 1
-            for d_ in shape:
-                n *= d_
-            direct = is_direct(param, shape)
-            out = param.grad if direct else torch.empty(shape, device=dev, dtype=torch.float32)
-            if not direct:
-                results[slot] = out
-            keep.append(out)
-            j = jobs.job[jobs.njobs]
-            j.partials, j.out, j.stride, j.nparts, j.n, j.accumulate = partials_ptr, _ptr(out), stride, nparts, n, 1 if direct else 0
-            j.ncols, j.ld = 0, 0
-            jobs.njobs += 1
-
-        vbase = vecp.data_ptr()
-        if part1 is not None:
-            add_job(0, _ptr(part1), part1.shape[0], hid * kin, (hid, kin), params[0])
-        if needs[1]:
-            add_job(1, vbase + 0 * vs * 4, nblk, 4 * vs, (hid,), params[1])
-        if part2 is not None:
-            add_job(2, _ptr(part2), part2.shape[0], dpad * hid, (dout, hid), params[2])
-        if needs[3]:
-            add_job(3, vbase + 1 * vs * 4, nblk, 4 * vs, (dout,), params[3])
-        if has_ln and needs[4]:
-            add_job(4, vbase + 2 * vs * 4, nblk, 4 * vs, (dout,), params[4])
-        if has_ln and needs[5]:
-            add_job(5, vbase + 3 * vs * 4, nblk, 4 * vs, (dout,), params[5])
-        all_results.append(results)
-        done.extend(q for q, nd in zip(params, needs) if nd and q is not None and is_direct(q, q.shape))
-    flush()
+    all_results, done = [], []
+    batch = _ReduceBatch(dev)
+    for it, (part1, part2) in zip(items, parts):
+        batch.reserve(6)
+        all_results.append(_mlp_reduce_jobs(batch, part1, part2, it.vecp, it.nblk, it.vs, 4, (it.hid, it.kin, it.dout), it.params, it.needs, it.has_ln))
+        done.extend(q for q, nd in zip(it.params, it.needs) if nd and q is not None and _direct_grad(q, q.shape))
+    batch.flush()
     if GRAD_LISTENER is not None:
         GRAD_LISTENER.note_done(done)
     return all_results
@@ -1827,16 +1789,8 @@ class GroupedMLPFunction(torch.autograd.Function):
             nwp = lib.nlam_mlp_fwd_wpack_floats(C.byref(p))
             if nwp > 0:
                 W1c, W2c = saved[k][4], saved[k][5]
-                wbuf = None
-                if PACKER is not None:
-                    wbuf = PACKER.get_wide("f", p, nwp, ("gf", W1c.data_ptr(), W2c.data_ptr(), int(p.src[0].width), int(p.hid), int(p.dout), int(p.flags),
-                                                          int(p.rows), int(p.batch)))
-                if wbuf is not None:
-                    p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
-                else:
-                    wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
-                    keep.append(wpack)
-                    p.wpack, p.wpack_floats = _ptr(wpack), nwp
+                keep.append(_wide_wpack(p, nwp, "f", ("gf", W1c.data_ptr(), W2c.data_ptr(), int(p.src[0].width), int(p.hid), int(p.dout), int(p.flags),
+                                                      int(p.rows), int(p.batch)), dev))
                 packs[k] = None
         # one grid for members of the narrow family, or of the fp32 wide one (the embedders at d = 128); mixed families and
         # split-bf16 super-tile members run one launch each
@@ -1871,7 +1825,6 @@ class GroupedMLPFunction(torch.autograd.Function):
                 raise RuntimeError("nlam_mlp_bwd_group has no fused-weight-gradient kernel for a shape the forward planned it for")
             return (None, *grads, *([None] * n))
         arr = (L.MlpBwd * m)()
-        tiles = (C.c_int64 * m)()
         work = []
         for i, k in enumerate(live):
             t, B, bstride, rows, W1c, W2c, z1, xhat, rstd = ctx.saved[k]
@@ -1889,7 +1842,6 @@ class GroupedMLPFunction(torch.autograd.Function):
             dz1 = torch.empty((B * rows, hid), device=dev, dtype=torch.float32)
             p.dz1 = _ptr(dz1)
             dz2, _ = _alloc_dz2(lib, p, B * rows, dout, dev)
-            tiles[i] = p.ntiles * B
             work.append([k, g, dz1, dz2, None, 0, None])
         fams = {int(lib.nlam_mlp_bwd_family(C.byref(arr[i]))) for i in range(m)}
         for i, k in enumerate(live):   # wide members: transposed weights in MFMA A-operand order
@@ -1897,16 +1849,8 @@ class GroupedMLPFunction(torch.autograd.Function):
             nwp = lib.nlam_mlp_bwd_wpack_floats(C.byref(p))
             if nwp > 0:
                 W1c, W2c = ctx.saved[k][4], ctx.saved[k][5]
-                wbuf = None
-                if PACKER is not None:
-                    wbuf = PACKER.get_wide("b", p, nwp, ("gb", W1c.data_ptr(), W2c.data_ptr(), int(p.src[0].width), int(p.hid), int(p.dout), int(p.flags),
-                                                          int(p.rows), int(p.batch), int(p.dz2_ld)))
-                if wbuf is not None:
-                    p.wpack, p.wpack_floats, p.flags = wbuf.data_ptr(), nwp, int(p.flags) | L.F_WPACK_READY
-                else:
-                    wpack = torch.empty((nwp,), device=dev, dtype=torch.float32)
-                    work[i][6] = wpack
-                    p.wpack, p.wpack_floats = _ptr(wpack), nwp
+                work[i][6] = _wide_wpack(p, nwp, "b", ("gb", W1c.data_ptr(), W2c.data_ptr(), int(p.src[0].width), int(p.hid), int(p.dout), int(p.flags),
+                                                       int(p.rows), int(p.batch), int(p.dz2_ld)), dev)
         blocks = (C.c_int32 * m)()
         can_group = m > 1 and fams in ({0}, {1})
         if can_group:
@@ -1951,14 +1895,11 @@ class GroupedMLPFunction(torch.autograd.Function):
             prm = params[k]
             needs = [ctx.needs_input_grad[1 + 6 * k + q] for q in range(6)]
             has_ln = prm[4] is not None
-            direct_all = DIRECT_PARAM_GRADS and all(q is None or not nd or (q.grad is not None and q.grad.is_contiguous()) for q, nd in zip(prm, needs))
-            on_side = OVERLAP.active and direct_all
-            src_list = [(t.data_ptr(), bstride, kin, None)]
-            args = (lib, B, rows, hid, dout, kin, ctx.mm_flags, dz1, dz2, z1, vecp, nblk, _vec_stride(hid, dout), src_list, prm, needs, has_ln)
-            if on_side:
-                OVERLAP.run(prm[0], (g, dz1, dz2, vecp, z1, t, wpack), lambda a=args: _chunk_weight_grads(*a))
+            item = _WgradItem(B, rows, hid, dout, kin, ctx.mm_flags, dz1, dz2, z1, vecp, nblk, _vec_stride(hid, dout), [(t, bstride, kin, None)], prm, needs, has_ln)
+            if OVERLAP.active and DIRECT_PARAM_GRADS and _all_direct(prm, needs):
+                OVERLAP.run(prm[0], (g, dz1, dz2, vecp, z1, t, wpack), lambda it=item: _chunks_weight_grads([it]))
             else:
-                grads[6 * k : 6 * k + 6] = _chunk_weight_grads(*args)
+                grads[6 * k : 6 * k + 6] = _chunks_weight_grads([item])[0]
         return (None, *grads, *([None] * n))
 
 
@@ -2015,91 +1956,51 @@ def _grouped_backward_fused(ctx, g_outs, live, grads):
     if lib.nlam_mlp_bwd_family(arr) != 0:   # the fused-weight-gradient kernel is a narrow one
         return False
 
-    def is_direct(param, shape):
-        return (DIRECT_PARAM_GRADS and param is not None and param.grad is not None and param.grad.is_contiguous()
-                and tuple(param.grad.shape) == tuple(shape) and param.grad.dtype == torch.float32)
-
     # A dead end of backward (nothing upstream of a static-feature embedder needs a gradient): under a trainer that owns the
     # parameter gradients the launch and its reduction go to a weight-gradient side stream.  At the end of backward that changes
     # nothing; for an embedder whose output gradient is complete EARLY (early_backward_leaf: the m2g edge embedding right behind
     # the decoder's backward) it takes 64 % of this kernel's rows out of the tail of the step (round 6).
-    all_direct = all(q is None or not ctx.needs_input_grad[1 + 6 * k + i_] or is_direct(q, q.shape)
-                     for (k, *_r) in work for i_, q in enumerate(params[k]))
+    all_direct = all(_all_direct(params[k], ctx.needs_input_grad[1 + 6 * k : 7 + 6 * k]) for (k, *_r) in work)
     if OVERLAP.active and all_direct:
         hold = [t_ for (k, g, dw2p, vecp, nblk, vs, b1c) in work for t_ in (g, dw2p, vecp, b1c, *[x_ for x_ in ctx.saved[k] if isinstance(x_, torch.Tensor)])]
         hold += [pk_.bwd for pk_ in ctx.packs if pk_ is not None and getattr(pk_, "bwd", None) is not None]
-        OVERLAP.run(params[work[0][0]][0], hold, lambda: _grouped_backward_fused_launch(ctx, arr, m, work, rows_all, meta, grads, is_direct), dead_end=True)
+        OVERLAP.run(params[work[0][0]][0], hold, lambda: _grouped_backward_fused_launch(ctx, arr, m, work, rows_all, meta, grads), dead_end=True)
     else:
-        _grouped_backward_fused_launch(ctx, arr, m, work, rows_all, meta, grads, is_direct)
+        _grouped_backward_fused_launch(ctx, arr, m, work, rows_all, meta, grads)
     return True
 
 
-def _grouped_backward_fused_launch(ctx, arr, m, work, rows_all, meta, grads, is_direct):
+def _grouped_backward_fused_launch(ctx, arr, m, work, rows_all, meta, grads):
     lib = L.load()
     params = ctx.params
-    dev = params[0][0].device
     rc = PROFILE.launch(("mlp_bwd_group_lw", rows_all, m, int(arr[0].hid), int(arr[0].dout)), lambda: lib.nlam_mlp_bwd_group(arr, m, _stream()), meta)
     if rc == -2:
         raise RuntimeError("nlam_mlp_bwd_group has no fused-weight-gradient kernel for a shape the forward planned it for")
     L.check(rc, "nlam_mlp_bwd_group (fused weight gradients)")
 
-    keep = []
-    jobs = L.ReduceJobs()   # ONE reduction launch for all members (<= 9 jobs each): they were four serial launches at the very end of the step
-
-    def flush():
-        if jobs.njobs > 0:
-            L.check(lib.nlam_reduce_jobs(C.byref(jobs), _stream()), "nlam_reduce_jobs")
-            jobs.njobs = 0
-
+    batch = _ReduceBatch(params[0][0].device)   # ONE reduction launch for all members (<= 9 jobs each): they were four serial launches at the very end of the step
+    done = []
     for (k, g, dw2p, vecp, nblk, vs, _b1c) in work:
         prm = params[k]
         hid, kin = prm[0].shape
         dout = prm[2].shape[0]
         needs = [ctx.needs_input_grad[1 + 6 * k + q] for q in range(6)]
-        has_ln = prm[4] is not None
-        if jobs.njobs + 9 > L.NLAM_MAX_REDUCE_JOBS:
-            flush()
-        res = [None] * 6
-        vbase = vecp.data_ptr()
-
-        def add(slot, ptr, stride, shape, param, ncols=0, ld=0, out_off=0, out=None):
-            n = 1
-            for d_ in shape:
-                n *= d_
-            direct = is_direct(param, param.shape)
-            if out is None:
-                out = param.grad if direct else (torch.zeros if ncols else torch.empty)(tuple(param.shape), device=dev, dtype=torch.float32)
-                if not direct:
-                    res[slot] = out
-            keep.append(out)
-            j = jobs.job[jobs.njobs]
-            j.partials, j.out, j.stride, j.nparts, j.accumulate = ptr, out.data_ptr() + 4 * out_off, stride, nblk, 1 if direct else 0
-            j.n, j.ncols, j.ld = n, ncols, ld
-            jobs.njobs += 1
-            return out
-
+        batch.reserve(9)
+        out = None
         if needs[0]:   # dW1[:, c] = vector row 4 + c, scattered into column c of the (hid, kin) matrix
-            out = None
             for c in range(kin):
-                out = add(0, vbase + (4 + c) * vs * 4, 7 * vs, (hid,), prm[0], ncols=1, ld=kin, out_off=c, out=out)
-        if needs[1]:
-            add(1, vbase + 0 * vs * 4, 7 * vs, (hid,), prm[1])
-        if needs[2]:
-            add(2, _ptr(dw2p), dout * hid, (dout, hid), prm[2])
-        if needs[3]:
-            add(3, vbase + 1 * vs * 4, 7 * vs, (dout,), prm[3])
-        if has_ln and needs[4]:
-            add(4, vbase + 2 * vs * 4, 7 * vs, (dout,), prm[4])
-        if has_ln and needs[5]:
-            add(5, vbase + 3 * vs * 4, 7 * vs, (dout,), prm[5])
+                out, direct = batch.add(vecp.data_ptr() + (4 + c) * vs * 4, nblk, 7 * vs, (hid, kin), prm[0], ncols=1, out=out, out_off=c)
+        res = _mlp_reduce_jobs(batch, None, dw2p if needs[2] else None, vecp, nblk, vs, 7, (hid, kin, dout), prm, needs, prm[4] is not None)
+        if out is not None and not direct:
+            res[0] = out
         grads[6 * k : 6 * k + 6] = res
-    flush()
+        done.append([q for q, nd in zip(prm, needs) if nd and q is not None and _direct_grad(q, q.shape)])
+    batch.flush()
     if GRAD_LISTENER is not None:
-        for (k, *_rest) in work:
-            needs = [ctx.needs_input_grad[1 + 6 * k + q] for q in range(6)]
-            GRAD_LISTENER.note_done([q for q, nd in zip(params[k], needs) if nd and q is not None and is_direct(q, q.shape)])
+        for d in done:
+            GRAD_LISTENER.note_done(d)
     if OVERLAP.active and not OVERLAP.capturing and OVERLAP.deferred is None:
-        OVERLAP.hold(torch.cuda.current_stream(), *keep)
+        OVERLAP.hold(torch.cuda.current_stream(), *batch.keep)
 
 
 def _linear_launch(x2d, W, ldn, ldk, k, n, out=None, accumulate=False, mm_flags=None, W2=None, out2=None):
@@ -2193,35 +2094,27 @@ def _node_linear_wgrad(prm, g_cols, x2d, mm):
     hid, kin = prm.shape
     rows, k = x2d.shape
     dev = x2d.device
-    direct = (DIRECT_PARAM_GRADS and prm.grad is not None and prm.grad.is_contiguous()
-              and tuple(prm.grad.shape) == (hid, kin) and prm.grad.dtype == torch.float32)
+    direct = _direct_grad(prm, (hid, kin))
     on_side = OVERLAP.active and direct
     out = prm.grad if direct else torch.zeros((hid, kin), device=dev, dtype=torch.float32)
 
     def launch():
-        jobs = L.ReduceJobs()
-        keep = []
+        batch = _ReduceBatch(dev)
+        parts = []
         for g2d, col0 in g_cols:
-            q = L.Wgrad()
-            q.A, q.m, q.batch, q.rows, q.nsrc, q.flags, q.n = _ptr(g2d), hid, 1, rows, 1, mm | _wgrad_solo(), k
-            _fill_src(q.src[0], x2d, 0, k, None)
-            nparts = lib.nlam_wgrad_nparts(C.byref(q))
-            partials = torch.empty((nparts, hid, k), device=dev, dtype=torch.float32)
-            q.partials, q.nparts = _ptr(partials), nparts
-            keep.append(partials)
+            q, partials = _wgrad_request(g2d, hid, k, 1, rows, [(x2d, 0, k, None)], mm | _wgrad_solo(), dev)
+            nparts = partials.shape[0]
+            parts.append(partials)
             key = ("wgrad", rows, hid, k)
             L.check(PROFILE.launch(key, lambda: lib.nlam_wgrad(C.byref(q), _stream()),
                                    lambda: {"flops": 2.0 * rows * hid * k, "bytes": 4.0 * (rows * (hid + k) + nparts * hid * k), "bytes_min": 4.0 * (rows * (hid + k) + hid * k),
                                             "mm": "f32" if max(hid, k) <= 64 else _MM_NAMES[(mm >> 8) & 3],
                                             "mfmas_per_block": 0 if max(hid, k) <= 64 else ((mm >> 8) & 3) * (((mm >> 8) & 3) + 1) // 2,
                                             "what": "node-level weight gradient of the factorised edge MLP"}), "nlam_wgrad")
-            j = jobs.job[jobs.njobs]
-            j.partials, j.out, j.stride, j.nparts, j.accumulate = _ptr(partials), out.data_ptr() + 4 * col0, hid * k, nparts, 1 if direct else 0
-            j.n, j.ncols, j.ld = hid * k, k, kin
-            jobs.njobs += 1
-        L.check(lib.nlam_reduce_jobs(C.byref(jobs), _stream()), "nlam_reduce_jobs")
+            batch.add(_ptr(partials), nparts, hid * k, (hid, kin), prm, ncols=k, out=out, out_off=col0)
+        batch.flush()
         if on_side:
-            OVERLAP.hold(torch.cuda.current_stream(), *keep)
+            OVERLAP.hold(torch.cuda.current_stream(), *parts)
         if GRAD_LISTENER is not None and direct:
             GRAD_LISTENER.note_done([prm])
 

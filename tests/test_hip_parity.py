@@ -375,6 +375,115 @@ def test_grouped_static_embedders_match_oracle(dev, monkeypatch, d, shapes, ln, 
             assert rel_err(pp.grad.cpu(), q.grad) < TOL, (i, k)
 
 
+def _count_reduce_launches(monkeypatch, ops):
+    """-> a list that receives the number of jobs of every nlam_reduce_jobs launch made from here on."""
+    launches = []
+    flush = ops._ReduceBatch.flush
+
+    def counting(self):
+        if self.jobs.njobs:
+            launches.append(int(self.jobs.njobs))
+        flush(self)
+
+    monkeypatch.setattr(ops._ReduceBatch, "flush", counting)
+    return launches
+
+
+def _small_mlp_params(kin, d, seed):
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g)   # noqa: E731
+    return [r(d, kin) / kin ** 0.5, 0.1 * r(d), r(d, d) / d ** 0.5, 0.1 * r(d), 1.0 + 0.1 * r(d), 0.1 * r(d)]
+
+
+def test_chunked_weight_gradients_across_a_reduction_flush(dev, monkeypatch):
+    """A chunked layer whose reductions do not fit one nlam_reduce_jobs launch: 8 chunks x 6 gradients = 48 jobs against
+    NLAM_MAX_REDUCE_JOBS = 40, a chunk's six jobs staying in one launch -> 36 + 12.  Chunks of 33 .. 70 rows (ragged last tiles,
+    one chunk above two tiles), a sliced and a gathered source, B = 2, LayerNorm, outside a trainer.  Every parameter and source
+    gradient: bit for bit that of the run without shared launches, and the float64 MLP applied per chunk within TOL."""
+    from neural_lam_amd import _lib as L
+    from neural_lam_amd import ops
+
+    rows, d, w, B, N = (33, 70, 40, 64, 35, 50, 69, 47), 16, 8, 2, 50
+    assert len(rows) * 6 == 48 > L.NLAM_MAX_REDUCE_JOBS == 40
+    bounds = [(sum(rows[:c]), sum(rows[: c + 1])) for c in range(len(rows))]
+    R = bounds[-1][1]
+    torch.manual_seed(48)
+    idx = torch.randint(0, N, (R,))
+    idx[:N] = torch.randperm(N)   # every row of the gathered table is used
+    ptr = torch.zeros(N + 1, dtype=torch.int64)
+    ptr[1:] = torch.bincount(idx, minlength=N).cumsum(0)
+    i32 = lambda t: t.to(torch.int32).contiguous().to(dev)   # noqa: E731
+    geom = ops.ChunkedGeometry(nsrc=2, chunks=bounds, rows=R, src_mode=["slice", "gather"], src_idx=[None, i32(idx)],
+                               scatter=[None, (i32(ptr), i32(torch.argsort(idx, stable=True)), N)])
+    params = [_small_mlp_params(2 * w, d, c) for c in range(len(rows))]
+    x0, x1, cot = torch.randn(B, R, w), torch.randn(B, N, w), torch.randn(B, R, d)
+    launches = _count_reduce_launches(monkeypatch, ops)
+
+    def run(grouped):
+        monkeypatch.setattr(ops, "GROUP_CHUNKS", grouped)
+        monkeypatch.setattr(ops, "GROUP_WGRADS", grouped)
+        del launches[:]
+        flat = [t.to(dev).requires_grad_() for pr in params for t in pr]
+        a, b = x0.to(dev).requires_grad_(), x1.to(dev).requires_grad_()
+        out, _ = ops.ChunkedMLPFunction.apply(geom, len(rows), *flat, a, b)
+        (out * cot.to(dev)).sum().backward()
+        assert launches == [36, 12]
+        return [t.grad for t in flat] + [a.grad, b.grad]
+
+    g1, g0 = run(True), run(False)
+    for a, b in zip(g1, g0):
+        assert torch.equal(a, b)
+
+    def mlp64(x, W1, b1, W2, b2, gamma, beta):
+        h = torch.nn.functional.silu(x @ W1.T + b1) @ W2.T + b2
+        return torch.nn.functional.layer_norm(h, (d,), gamma, beta, 1e-5)
+
+    p64 = [[t.double().requires_grad_() for t in pr] for pr in params]
+    a64, b64 = x0.double().requires_grad_(), x1.double().requires_grad_()
+    y = torch.cat([mlp64(torch.cat([a64[:, r0:r1], b64[:, idx[r0:r1]]], -1), *p64[c]) for c, (r0, r1) in enumerate(bounds)], 1)
+    (y * cot.double()).sum().backward()
+    ref = [t.grad for pr in p64 for t in pr] + [a64.grad, b64.grad]
+    for i, (a, b) in enumerate(zip(g1, ref)):
+        assert rel_err(a.cpu(), b) < TOL, i
+
+
+@pytest.mark.parametrize("d", [16, 32])
+def test_grouped_embedder_weight_gradients_across_a_reduction_flush(dev, monkeypatch, d):
+    """Five grouped embedders of three input columns, rows (40, 33, 64, 1, 97), LayerNorm, with FUSED_LEAF_WGRAD on against off
+    (TOL), and under ops.direct_param_grads() with zeroed .grad against the returned gradients (bit for bit).  d = 32 is the
+    smallest width the fused-weight-gradient kernel covers: there a member has 3 + 5 = 8 reduction jobs and room for 9 is kept,
+    so the fifth member does not join the first four's launch (32 + 8).  At d = 16 the switch changes nothing and every member's
+    six jobs are a launch of their own."""
+    import contextlib
+
+    from neural_lam_amd import ops
+
+    rows, kin = (40, 33, 64, 1, 97), 3
+    params = [_small_mlp_params(kin, d, 10 + i) for i in range(len(rows))]
+    torch.manual_seed(45)
+    xs, cots = [torch.randn(r, kin) for r in rows], [torch.randn(r, d) for r in rows]
+    launches = _count_reduce_launches(monkeypatch, ops)
+
+    def run(fused, direct):
+        monkeypatch.setattr(ops, "FUSED_LEAF_WGRAD", fused)
+        del launches[:]
+        flat = [t.to(dev).requires_grad_() for pr in params for t in pr]
+        if direct:
+            for t in flat:
+                t.grad = torch.zeros_like(t)
+        with ops.direct_param_grads(early_leaf=False) if direct else contextlib.nullcontext():
+            outs = ops.GroupedMLPFunction.apply(len(rows), *flat, *[x.to(dev) for x in xs])
+            torch.autograd.backward(outs, [c.to(dev) for c in cots])
+        assert launches == ([32, 8] if fused and d == 32 else [6] * len(rows))
+        return [t.grad for t in flat]
+
+    g_on, g_off, g_direct = run(True, False), run(False, False), run(True, True)
+    for i, (a, b) in enumerate(zip(g_on, g_off)):
+        assert rel_err(a.cpu(), b.cpu()) < TOL, i
+    for i, (a, b) in enumerate(zip(g_direct, g_on)):
+        assert torch.equal(a, b), i
+
+
 @pytest.mark.parametrize("mode", ["bf16x3", "bf16", "f32"])
 @pytest.mark.parametrize("widths,hid,B,shared_last", [
     ([17, 17, 18, 4], 64, 2, True),    # the grid input features of the MEPS configuration (graph/base.py:275-283): 56 columns
