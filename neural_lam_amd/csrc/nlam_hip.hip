@@ -4783,6 +4783,32 @@ int set_lds(K kernel, size_t bytes) {
     return 0;
 }
 
+// every launch with dynamic LDS: the kernel instantiation K is a template argument, its one argument struct goes by value
+template <auto K, typename A>
+int32_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A& arg) {
+    if (const int rc = set_lds(K, lds)) return rc;
+    hipLaunchKernelGGL(K, grid, block, lds, stream, arg);
+    return (int32_t)hipGetLastError();
+}
+
+// A run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V of Vs that equals v (inside f, v.value
+// is a constant expression), NLAM_EUNSUP when there is none.  Only the listed values are instantiated.
+template <int... Vs, typename F>
+int32_t pick(int v, F&& f) {
+    int32_t rc = NLAM_EUNSUP;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+// the same for a ladder that ends in an unconditional `else`: every v that is none of Vs runs as D
+template <int D, int... Vs, typename F>
+int32_t pick_else(int v, F&& f) {
+    return pick<Vs..., D>(((v == Vs) || ...) ? v : D, f);
+}
+template <typename F>
+int32_t pick_bool(bool v, F&& f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+
 // backward kernels: one persistent 8-wave workgroup per CU; tiles are dealt to workgroups first, then to waves
 int grid_blocks(long total_tiles) {
     long need = total_tiles < 1 ? 1 : total_tiles;
@@ -4801,14 +4827,8 @@ WideCfg wide_cfg(int maxw) {
     return {0, 0};
 }
 
-bool fwd_is_wide(const nlam_mlp_fwd_t* p) {
-    if (p->hid > kMaxWidth || p->dout > kMaxWidth) return true;
-    for (int s = 0; s < p->nsrc; ++s)
-        if (p->src[s].width > kMaxWidth) return true;
-    return false;
-}
-
-bool bwd_is_wide(const nlam_mlp_bwd_t* p) {
+template <typename P>   // nlam_mlp_fwd_t or nlam_mlp_bwd_t
+bool mlp_is_wide(const P* p) {
     if (p->hid > kMaxWidth || p->dout > kMaxWidth) return true;
     for (int s = 0; s < p->nsrc; ++s)
         if (p->src[s].width > kMaxWidth) return true;
@@ -4818,7 +4838,7 @@ bool bwd_is_wide(const nlam_mlp_bwd_t* p) {
 // narrow backward with an output width that is not a whole 32-column block on the split-bf16 fast kernel (RO instantiation):
 // one output block, no LayerNorm / aggregation / residual, a split-bf16 matrix mode, FAST hidden width and source widths
 bool bwd_ragged_out(const nlam_mlp_bwd_t* p) {
-    if (bwd_is_wide(p) || p->dout % 32 == 0 || p->dout > 32 || p->hid % 32 != 0) return false;
+    if (mlp_is_wide(p) || p->dout % 32 == 0 || p->dout > 32 || p->hid % 32 != 0) return false;
     if (p->ln_w != nullptr || p->g_aggr != nullptr || p->g_out == nullptr || p->out_idx != nullptr) return false;
     if ((p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1 | NLAM_F_PRE_ADD | NLAM_F_LEAF_WGRAD)) != 0) return false;
     if ((p->flags & NLAM_F_MM_MASK) == 0) return false;
@@ -4876,6 +4896,16 @@ void launch_pack(const pack_jobs_t& jobs, hipStream_t stream) {
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(pack_a_kernel, dim3((int)blocks, jobs.njobs), dim3(256), 0, stream, jobs);
 }
+
+#if NLAM_IN_TU(4)   // naming pack_bf_kernel<> emits it: in the slice of its callers only
+// the split-bf16 pack of build_fwd_wbf_jobs / build_bwd_wbf_jobs (`most`: lane items of their largest job)
+void launch_pack_bf(const packbf_jobs_t& jobs, long most, int wns, hipStream_t stream) {
+    long blocks = (most + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    if (wns == 1) hipLaunchKernelGGL(pack_bf_kernel<1>, dim3((int)blocks, jobs.njobs), dim3(256), 0, stream, jobs);
+    else hipLaunchKernelGGL(pack_bf_kernel<3>, dim3((int)blocks, jobs.njobs), dim3(256), 0, stream, jobs);
+}
+#endif
 
 // one source of at most kSmallN columns: wgrad_smalln_kernel (streams A once)
 bool wgrad_is_smalln(const nlam_wgrad_t* p) { return p->nsrc == 1 && p->src[0].width <= kSmallN && p->m % 4 == 0; }
@@ -4963,6 +4993,16 @@ void group_blocks(const long* tiles, int n, int* blocks) {
         if (b > t) b = t;
         blocks[k] = (int)b;
     }
+}
+
+// the workgroup ranges of a grouped launch: member k runs its count[k] workgroups as first[k] .. first[k + 1), first[n] is the
+// grid size and the unused slots repeat it
+template <typename G>
+void group_prefix(G& grp, int n, const int* count) {
+    grp.n = n;
+    grp.first[0] = 0;
+    for (int k = 0; k < n; ++k) grp.first[k + 1] = grp.first[k] + count[k];
+    for (int k = n + 1; k <= NLAM_MAX_GROUP; ++k) grp.first[k] = grp.first[n];
 }
 
 // members of one grouped wide launch run one kernel instantiation (hid, dout, the widest gradient decide it); the kernel reads
@@ -5137,7 +5177,7 @@ __global__ void pack_bf_table_kernel(const nlam_pack_rec_t* recs) {
 // mlp_bwd_edge_kernel takes the launch: the data gradients of the factorised InteractionNet edge layer of width 512 in the one-term
 // mode or of width 256 in the three-term mode (the backward of what mlp_fwd_edge_kernel<1, 512, .> / <3, 256, false> compute)
 bool bwd_edge_ok(const nlam_mlp_bwd_t* p) {
-    if (nlam_detail::wbf_edge == 0 || !bwd_is_wide(p)) return false;
+    if (nlam_detail::wbf_edge == 0 || !mlp_is_wide(p)) return false;
     const int wns = bwd_wbf_ns(p);
     const int d = wns == 1 ? 512 : 256;
     if (wns != 1 && !(wns == 3 && (nlam_detail::wbf_edge & 2) == 0 && !(p->flags & NLAM_F_STORE_BF16))) return false;
@@ -5286,7 +5326,7 @@ int32_t nlam_mlp_pack(const nlam_pack_job_t* jobs_device, int32_t njobs, void* h
 
 int32_t nlam_mlp_fwd_pack_records(const nlam_mlp_fwd_t* p, nlam_pack_rec_t* out, int32_t cap, int32_t* kind) {
     if (p == nullptr || out == nullptr || kind == nullptr || p->W1 == nullptr || p->W2 == nullptr) return NLAM_EINVAL;
-    if (!fwd_is_wide(p)) return 0;
+    if (!mlp_is_wide(p)) return 0;
     if (p->wpack == nullptr || p->wpack_floats < nlam_mlp_fwd_wpack_floats(p)) return NLAM_EINVAL;
     int n = 0;
     const int wns = fwd_wbf_ns(p);
@@ -5315,7 +5355,7 @@ int32_t nlam_mlp_fwd_pack_records(const nlam_mlp_fwd_t* p, nlam_pack_rec_t* out,
 
 int32_t nlam_mlp_bwd_pack_records(const nlam_mlp_bwd_t* p, nlam_pack_rec_t* out, int32_t cap, int32_t* kind) {
     if (p == nullptr || out == nullptr || kind == nullptr || p->W1 == nullptr || p->W2 == nullptr) return NLAM_EINVAL;
-    if (!bwd_is_wide(p)) return 0;
+    if (!mlp_is_wide(p)) return 0;
     if (p->wpack == nullptr || p->wpack_floats < nlam_mlp_bwd_wpack_floats(p)) return NLAM_EINVAL;
     int n = 0;
     const int wns = bwd_wbf_ns(p);
@@ -5356,7 +5396,7 @@ int32_t nlam_pack_records(const nlam_pack_rec_t* recs_device, int32_t n, int32_t
 }
 
 int64_t nlam_mlp_fwd_wpack_floats(const nlam_mlp_fwd_t* p) {
-    if (p == nullptr || !fwd_is_wide(p)) return 0;
+    if (p == nullptr || !mlp_is_wide(p)) return 0;
     const int ns = fwd_wbf_ns(p);
     if (ns > 0) return fwd_wbf_wpack_floats(p, ns);
     const int64_t HBT = (p->hid + 31) / 32, OBT = (p->dout + 31) / 32;
@@ -5364,7 +5404,7 @@ int64_t nlam_mlp_fwd_wpack_floats(const nlam_mlp_fwd_t* p) {
 }
 
 int64_t nlam_mlp_bwd_wpack_floats(const nlam_mlp_bwd_t* p) {
-    if (p == nullptr || !bwd_is_wide(p)) return 0;
+    if (p == nullptr || !mlp_is_wide(p)) return 0;
     if (bwd_wbf_ns(p) > 0) return bwd_wbf_wpack_floats(p, bwd_wbf_ns(p));
     const int64_t HBT = (p->hid + 31) / 32, OBT = (p->dout + 31) / 32;
     int64_t f = HBT * OBT * 1024;
@@ -5380,7 +5420,7 @@ int32_t nlam_store_bf16_supported(const nlam_mlp_fwd_t* p) {
 
 int32_t nlam_mlp_bwd_dz2_ld(const nlam_mlp_bwd_t* p) {
     if (p == nullptr) return 0;
-    if (bwd_is_wide(p))   // split-bf16 wide kernel with a ragged output width: padded so that the W2 gradient has m % 4 == 0
+    if (mlp_is_wide(p))   // split-bf16 wide kernel with a ragged output width: padded so that the W2 gradient has m % 4 == 0
         return (p->dout % 4 != 0 && bwd_wbf_ns(p) > 0) ? ((p->dout + 31) / 32) * 32 : 0;
     return bwd_ragged_out(p) ? ((p->dout + 31) / 32) * 32 : 0;
 }
@@ -5388,7 +5428,7 @@ int32_t nlam_mlp_bwd_dz2_ld(const nlam_mlp_bwd_t* p) {
 int32_t nlam_mlp_bwd_blocks(const nlam_mlp_bwd_t* p) {
     if (p == nullptr) return 0;
     const long total = (long)p->ntiles * p->batch;
-    if (!bwd_is_wide(p)) return grid_blocks(total);
+    if (!mlp_is_wide(p)) return grid_blocks(total);
     if (bwd_edge_ok(p)) {
         const long ns2 = (long)((p->ntiles + 1) / 2) * p->batch;
         return (int32_t)(ns2 < nlam_detail::chain_cus ? ns2 : nlam_detail::chain_cus);
@@ -5408,13 +5448,13 @@ int32_t nlam_mlp_bwd_blocks(const nlam_mlp_bwd_t* p) {
 // Grouped launches take members of one family (0: nlam_mlp_*_group's narrow kernels, 1: the wide group kernels).
 int32_t nlam_mlp_fwd_family(const nlam_mlp_fwd_t* p) {
     if (p == nullptr) return NLAM_EINVAL;
-    if (!fwd_is_wide(p)) return 0;
+    if (!mlp_is_wide(p)) return 0;
     return fwd_wbf_ns(p) > 0 ? 2 : 1;
 }
 
 int32_t nlam_mlp_bwd_family(const nlam_mlp_bwd_t* p) {
     if (p == nullptr) return NLAM_EINVAL;
-    if (!bwd_is_wide(p)) return 0;
+    if (!mlp_is_wide(p)) return 0;
     return bwd_wbf_ns(p) > 0 ? 2 : 1;
 }
 
@@ -5423,7 +5463,7 @@ int32_t nlam_mlp_bwd_group_blocks(const nlam_mlp_bwd_t* ps, int32_t n, int32_t* 
     if (ps == nullptr || blocks == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
     long tiles[NLAM_MAX_GROUP];
     for (int k = 0; k < n; ++k) tiles[k] = (long)ps[k].ntiles * ps[k].batch;
-    if (!bwd_is_wide(&ps[0])) {
+    if (!mlp_is_wide(&ps[0])) {
         group_blocks(tiles, n, blocks);
         return 0;
     }
@@ -5480,55 +5520,13 @@ int32_t nlam_wgrad_nparts(const nlam_wgrad_t* p) {
     return (int32_t)(np < 1 ? 1 : np);
 }
 
-#define NLAM_LAUNCH_FWD1(HB_, OB_, FAST_, NS_)                                                                        \
-    do {                                                                                                               \
-        const size_t lds = fwd_lds_bytes(p, HB_, OB_, NS_);                                                            \
-        int rc = set_lds(mlp_fwd_kernel<HB_, OB_, FAST_, NS_>, lds);                                                   \
-        if (rc != 0) return rc;                                                                                        \
-        hipLaunchKernelGGL((mlp_fwd_kernel<HB_, OB_, FAST_, NS_>), dim3(blocks), dim3(nwaves * 64), lds, stream, *p);  \
-    } while (0)
-#define NLAM_LAUNCH_FWDBF1(HB_, OB_, NS_, RAG_, RES_)                                                                          \
-    do {                                                                                                                      \
-        const size_t lds = fwd_lds_bytes(p, HB_, OB_, NS_);                                                                   \
-        int rc = set_lds(mlp_fwd_bf_kernel<HB_, OB_, NS_, RAG_, RES_>, lds);                                                  \
-        if (rc != 0) return rc;                                                                                               \
-        hipLaunchKernelGGL((mlp_fwd_bf_kernel<HB_, OB_, NS_, RAG_, RES_>), dim3(blocks), dim3(nwaves * 64), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_FWDBF(HB_, OB_, NS_)                               \
-    do {                                                               \
-        if (ragged) NLAM_LAUNCH_FWDBF1(HB_, OB_, NS_, true, false);    \
-        else if (resid) NLAM_LAUNCH_FWDBF1(HB_, OB_, NS_, false, true); \
-        else NLAM_LAUNCH_FWDBF1(HB_, OB_, NS_, false, false);          \
-    } while (0)
-#define NLAM_LAUNCH_FWDPRE1(HB_, OB_, NS_, RES_)                                                                                \
-    do {                                                                                                                       \
-        const size_t lds = fwd_lds_bytes(p, HB_, OB_, NS_);                                                                    \
-        int rc = set_lds(mlp_fwd_bf_kernel<HB_, OB_, NS_, false, RES_, true>, lds);                                            \
-        if (rc != 0) return rc;                                                                                                \
-        hipLaunchKernelGGL((mlp_fwd_bf_kernel<HB_, OB_, NS_, false, RES_, true>), dim3(blocks), dim3(nwaves * 64), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_FWDPRE(HB_, OB_)                                   \
-    do {                                                               \
-        if (ns == 3) { if (resid) NLAM_LAUNCH_FWDPRE1(HB_, OB_, 3, true); else NLAM_LAUNCH_FWDPRE1(HB_, OB_, 3, false); } \
-        else if (ns == 2) { if (resid) NLAM_LAUNCH_FWDPRE1(HB_, OB_, 2, true); else NLAM_LAUNCH_FWDPRE1(HB_, OB_, 2, false); } \
-        else { if (resid) NLAM_LAUNCH_FWDPRE1(HB_, OB_, 1, true); else NLAM_LAUNCH_FWDPRE1(HB_, OB_, 1, false); } \
-    } while (0)
-#define NLAM_LAUNCH_FWD(HB_, OB_)                            \
-    do {                                                     \
-        if (ns == 3) NLAM_LAUNCH_FWDBF(HB_, OB_, 3);         \
-        else if (ns == 2) NLAM_LAUNCH_FWDBF(HB_, OB_, 2);    \
-        else if (ns == 1) NLAM_LAUNCH_FWDBF(HB_, OB_, 1);    \
-        else if (fast) NLAM_LAUNCH_FWD1(HB_, OB_, true, 0);  \
-        else NLAM_LAUNCH_FWD1(HB_, OB_, false, 0);           \
-    } while (0)
-
 int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_mlp_fwd");
     const int32_t bad = nlam_detail::fwd_check(p);
     if (bad != 0) return bad;
     if (p->rows == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (fwd_is_wide(p)) {
+    if (mlp_is_wide(p)) {
         if (fwd_wbf_ns(p) > 0) return nlam_detail::fwd_wbf(p, stream);   // split-bf16 matrix path (nlam_wbf.inc)
         return nlam_detail::fwd_wide(p, stream);
     }
@@ -5539,118 +5537,102 @@ int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream) {
 #endif
 
 #if NLAM_IN_TU(4)
+namespace {
+// one line of fwd_wbf's plan tables: mlp_fwd_wbf_kernel<NS, NW, FG, FB, RT, RTP, SBF, V4>, V4 from the widths
+template <int NS, int NW, int FG, int FB, int RT, int RTP, bool SBF>
+int32_t launch_fwd_wbf(bool v4, int blocks, size_t lds, hipStream_t stream, const nlam_mlp_fwd_t& p) {
+    return pick_bool(v4, [&](auto v4c) {
+        return launch<mlp_fwd_wbf_kernel<NS, NW, FG, FB, RT, RTP, SBF, v4c>>(dim3(blocks), dim3(NW * 64), lds, stream, p);
+    });
+}
+}  // namespace
+
 int32_t nlam_detail::fwd_wbf(const nlam_mlp_fwd_t* p, hipStream_t stream) {
     const int wns = fwd_wbf_ns(p);
-    {
-            const WbfPlan pl = fwd_wbf_choose(p, wns);
-            if ((p->flags & NLAM_F_WPACK_READY) == 0) {   // else: `wpack` was filled for this step already (nlam_pack_records)
-                packbf_jobs_t jobs;
-                const long most = build_fwd_wbf_jobs(p, wns, jobs);
-                long pblocks = (most + 255) / 256;
-                if (pblocks > 1024) pblocks = 1024;
-                if (wns == 1) hipLaunchKernelGGL(pack_bf_kernel<1>, dim3((int)pblocks, jobs.njobs), dim3(256), 0, stream, jobs);
-                else hipLaunchKernelGGL(pack_bf_kernel<3>, dim3((int)pblocks, jobs.njobs), dim3(256), 0, stream, jobs);
-            }
-            const size_t lds = fwd_wbf_lds(p, wns, pl);
-            const long nsuper = (long)((p->ntiles + pl.nrt - 1) / pl.nrt) * p->batch;
-            // one 8-wave workgroup per CU, or two of 4 waves (ONE 4-wave workgroup per CU, leaving half of every CU to the
-            // weight-gradient kernels of the side streams, measured 20 % slower in the captured cfg3 step: 59.8 vs 49.4 ms)
-            const long wcap = pl.nw == 4 ? 2 * nlam_detail::chain_cus : nlam_detail::chain_cus;
-            const int wblocks = (int)(nsuper < wcap ? (nsuper < 1 ? 1 : nsuper) : wcap);
-            bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0;   // every chunk a whole 16-byte piece: the branch-free chunk accessors
-            for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
-#define NLAM_LAUNCH_FWD_WBF1(NS_, NW_, FG_, FB_, RT_, RTP_, SBF_, V4_)                                                         \
-    do {                                                                                                                      \
-        int rc = set_lds(mlp_fwd_wbf_kernel<NS_, NW_, FG_, FB_, RT_, RTP_, SBF_, V4_>, lds);                                  \
-        if (rc != 0) return rc;                                                                                               \
-        hipLaunchKernelGGL((mlp_fwd_wbf_kernel<NS_, NW_, FG_, FB_, RT_, RTP_, SBF_, V4_>), dim3(wblocks), dim3(NW_ * 64), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_FWD_WBF(NS_, NW_, FG_, FB_, RT_, RTP_)                              \
-    do {                                                                                \
-        if (v4) NLAM_LAUNCH_FWD_WBF1(NS_, NW_, FG_, FB_, RT_, RTP_, false, true);       \
-        else NLAM_LAUNCH_FWD_WBF1(NS_, NW_, FG_, FB_, RT_, RTP_, false, false);         \
-    } while (0)
-#define NLAM_LAUNCH_FWD_WBF_S(NW_, FG_, FB_, RT_, RTP_)                                 \
-    do {                                                                                \
-        if (v4) NLAM_LAUNCH_FWD_WBF1(1, NW_, FG_, FB_, RT_, RTP_, true, true);          \
-        else NLAM_LAUNCH_FWD_WBF1(1, NW_, FG_, FB_, RT_, RTP_, true, false);            \
-    } while (0)
-            // the factorised InteractionNet edge layer of one width -- d = 512 in the one-term mode (cfg5), d = 256 in the fp32-class
-            // mode (cfg3): its own software-pipelined kernel (round 6)
-            if (nlam_detail::wbf_edge != 0 && v4 && (p->flags & NLAM_F_PRE_ADD) && !(p->flags & (NLAM_F_ADD_SRC1 | NLAM_F_NO_ACT)) &&
-                p->nsrc == NLAM_MAX_SRC && p->hid == p->dout && ((wns == 1 && p->hid == 512) || (wns == 3 && p->hid == 256 && !(p->flags & NLAM_F_STORE_BF16))) &&
-                p->src[0].width == p->hid && p->src[1].width == p->hid && p->src[2].width == p->hid && p->ln_w != nullptr && p->ln_b != nullptr &&
-                p->b1 != nullptr && p->b2 != nullptr && p->aggr != nullptr && p->rowptr != nullptr && p->ncat == 0 &&
-                (long)p->ntiles * p->batch >= 2 * 64) {
-                if ((p->flags & NLAM_F_STORE_BF16) && !store_bf16_ok(p)) return NLAM_EUNSUP;
-                const long ns2 = (long)((p->ntiles + 1) / 2) * p->batch;
-                const int eblocks = (int)(ns2 < nlam_detail::chain_cus ? ns2 : nlam_detail::chain_cus);
-#define NLAM_LAUNCH_FWD_EDGE(NS_, D_, SBF_)                                                                               \
-    do {                                                                                                                  \
-        const size_t elds = fwd_edge_lds<NS_, D_>();                                                                       \
-        int rc = set_lds(mlp_fwd_edge_kernel<NS_, D_, SBF_>, elds);                                                        \
-        if (rc != 0) return rc;                                                                                           \
-        hipLaunchKernelGGL((mlp_fwd_edge_kernel<NS_, D_, SBF_>), dim3(eblocks), dim3(512), elds, stream, *p);              \
-    } while (0)
-                // (d = 256 in the one-term mode -- cfg3 under autocast, not a BASELINE configuration -- measured no faster than the
-                // template's 4-wave shape, 103.3 vs 102.5 us on the m2m edges: not instantiated)
-                if (wns == 3) NLAM_LAUNCH_FWD_EDGE(3, 256, false);
-                else if (p->flags & NLAM_F_STORE_BF16) NLAM_LAUNCH_FWD_EDGE(1, 512, true);
-                else NLAM_LAUNCH_FWD_EDGE(1, 512, false);
-                return (int32_t)hipGetLastError();
-            }
-            if (p->flags & NLAM_F_STORE_BF16) {   // z1 / xhat as bf16 rows: one term, whole blocks, the shapes of store_bf16_ok()
-                if (!store_bf16_ok(p)) return NLAM_EUNSUP;
-                if (pl.cfg == 2) NLAM_LAUNCH_FWD_WBF_S(8, 8, 1, 4, 2);
-                else if (pl.cfg == 5) NLAM_LAUNCH_FWD_WBF_S(4, 4, 2, 2, 1);
-                else if (pl.cfg == 6) NLAM_LAUNCH_FWD_WBF_S(4, 4, 4, 1, 1);
-                else if (pl.cfg == 7) NLAM_LAUNCH_FWD_WBF_S(4, 4, 4, 2, 2);
-                else if (pl.cfg == 3) NLAM_LAUNCH_FWD_WBF_S(8, 8, 2, 2, 1);
-                else return NLAM_EUNSUP;
-                return (int32_t)hipGetLastError();
-            }
-            if (wns == 1) {
-                if (pl.cfg == 1) NLAM_LAUNCH_FWD_WBF(1, 8, 4, 1, 4, 2);
-                else if (pl.cfg == 2) NLAM_LAUNCH_FWD_WBF(1, 8, 8, 1, 4, 2);
-                else if (pl.cfg == 4) NLAM_LAUNCH_FWD_WBF(1, 8, 8, 1, 2, 2);
-                else if (pl.cfg == 5) NLAM_LAUNCH_FWD_WBF(1, 4, 4, 2, 2, 1);
-                else if (pl.cfg == 6) NLAM_LAUNCH_FWD_WBF(1, 4, 4, 4, 1, 1);
-                else if (pl.cfg == 7) NLAM_LAUNCH_FWD_WBF(1, 4, 4, 4, 2, 2);
-                else NLAM_LAUNCH_FWD_WBF(1, 8, 8, 2, 2, 1);
-            } else {
-                if (pl.cfg == 1) NLAM_LAUNCH_FWD_WBF(3, 8, 4, 1, 4, 2);
-                else if (pl.cfg == 2) NLAM_LAUNCH_FWD_WBF(3, 8, 8, 1, 4, 2);
-                else if (pl.cfg == 4) NLAM_LAUNCH_FWD_WBF(3, 8, 8, 1, 2, 2);
-                else if (pl.cfg == 5) NLAM_LAUNCH_FWD_WBF(3, 4, 4, 2, 2, 1);
-                else NLAM_LAUNCH_FWD_WBF(3, 8, 8, 2, 2, 1);
-            }
-            return (int32_t)hipGetLastError();
+    const WbfPlan pl = fwd_wbf_choose(p, wns);
+    if ((p->flags & NLAM_F_WPACK_READY) == 0) {   // else: `wpack` was filled for this step already (nlam_pack_records)
+        packbf_jobs_t jobs;
+        const long most = build_fwd_wbf_jobs(p, wns, jobs);
+        launch_pack_bf(jobs, most, wns, stream);
+    }
+    const size_t lds = fwd_wbf_lds(p, wns, pl);
+    const long nsuper = (long)((p->ntiles + pl.nrt - 1) / pl.nrt) * p->batch;
+    // one 8-wave workgroup per CU, or two of 4 waves (ONE 4-wave workgroup per CU, leaving half of every CU to the
+    // weight-gradient kernels of the side streams, measured 20 % slower in the captured cfg3 step: 59.8 vs 49.4 ms)
+    const long wcap = pl.nw == 4 ? 2 * nlam_detail::chain_cus : nlam_detail::chain_cus;
+    const int wblocks = (int)(nsuper < wcap ? (nsuper < 1 ? 1 : nsuper) : wcap);
+    bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0;   // every chunk a whole 16-byte piece: the branch-free chunk accessors
+    for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
+    // the factorised InteractionNet edge layer of one width -- d = 512 in the one-term mode (cfg5), d = 256 in the fp32-class
+    // mode (cfg3): its own software-pipelined kernel (round 6)
+    if (nlam_detail::wbf_edge != 0 && v4 && (p->flags & NLAM_F_PRE_ADD) && !(p->flags & (NLAM_F_ADD_SRC1 | NLAM_F_NO_ACT)) &&
+        p->nsrc == NLAM_MAX_SRC && p->hid == p->dout && ((wns == 1 && p->hid == 512) || (wns == 3 && p->hid == 256 && !(p->flags & NLAM_F_STORE_BF16))) &&
+        p->src[0].width == p->hid && p->src[1].width == p->hid && p->src[2].width == p->hid && p->ln_w != nullptr && p->ln_b != nullptr &&
+        p->b1 != nullptr && p->b2 != nullptr && p->aggr != nullptr && p->rowptr != nullptr && p->ncat == 0 &&
+        (long)p->ntiles * p->batch >= 2 * 64) {
+        if ((p->flags & NLAM_F_STORE_BF16) && !store_bf16_ok(p)) return NLAM_EUNSUP;
+        const long ns2 = (long)((p->ntiles + 1) / 2) * p->batch;
+        const dim3 egrid((int)(ns2 < nlam_detail::chain_cus ? ns2 : nlam_detail::chain_cus)), eblock(512);
+        // (d = 256 in the one-term mode -- cfg3 under autocast, not a BASELINE configuration -- measured no faster than the
+        // template's 4-wave shape, 103.3 vs 102.5 us on the m2m edges: not instantiated)
+        if (wns == 3) return launch<mlp_fwd_edge_kernel<3, 256, false>>(egrid, eblock, fwd_edge_lds<3, 256>(), stream, *p);
+        if (p->flags & NLAM_F_STORE_BF16) return launch<mlp_fwd_edge_kernel<1, 512, true>>(egrid, eblock, fwd_edge_lds<1, 512>(), stream, *p);
+        return launch<mlp_fwd_edge_kernel<1, 512, false>>(egrid, eblock, fwd_edge_lds<1, 512>(), stream, *p);
+    }
+    // pl.cfg -> <NS, NW, FG, FB, RT, RTP, SBF>: the instantiations that exist, one per line
+    if (p->flags & NLAM_F_STORE_BF16) {   // z1 / xhat as bf16 rows: one term, whole blocks, the shapes of store_bf16_ok()
+        if (!store_bf16_ok(p)) return NLAM_EUNSUP;
+        switch (pl.cfg) {
+        case 2: return launch_fwd_wbf<1, 8, 8, 1, 4, 2, true>(v4, wblocks, lds, stream, *p);
+        case 5: return launch_fwd_wbf<1, 4, 4, 2, 2, 1, true>(v4, wblocks, lds, stream, *p);
+        case 6: return launch_fwd_wbf<1, 4, 4, 4, 1, 1, true>(v4, wblocks, lds, stream, *p);
+        case 7: return launch_fwd_wbf<1, 4, 4, 4, 2, 2, true>(v4, wblocks, lds, stream, *p);
+        case 3: return launch_fwd_wbf<1, 8, 8, 2, 2, 1, true>(v4, wblocks, lds, stream, *p);
+        default: return NLAM_EUNSUP;
+        }
+    }
+    if (wns == 1) {
+        switch (pl.cfg) {
+        case 1: return launch_fwd_wbf<1, 8, 4, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+        case 2: return launch_fwd_wbf<1, 8, 8, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+        case 4: return launch_fwd_wbf<1, 8, 8, 1, 2, 2, false>(v4, wblocks, lds, stream, *p);
+        case 5: return launch_fwd_wbf<1, 4, 4, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+        case 6: return launch_fwd_wbf<1, 4, 4, 4, 1, 1, false>(v4, wblocks, lds, stream, *p);
+        case 7: return launch_fwd_wbf<1, 4, 4, 4, 2, 2, false>(v4, wblocks, lds, stream, *p);
+        default: return launch_fwd_wbf<1, 8, 8, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+        }
+    }
+    switch (pl.cfg) {
+    case 1: return launch_fwd_wbf<3, 8, 4, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+    case 2: return launch_fwd_wbf<3, 8, 8, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+    case 4: return launch_fwd_wbf<3, 8, 8, 1, 2, 2, false>(v4, wblocks, lds, stream, *p);
+    case 5: return launch_fwd_wbf<3, 4, 4, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    default: return launch_fwd_wbf<3, 8, 8, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
     }
 }
 #endif
 
 #if NLAM_IN_TU(3)
+namespace {
+// wide_cfg's three workgroup shapes as the template arguments <NWV, FB> of the fp32 wide kernels
+template <typename F>
+int32_t pick_wide(const WideCfg& cfg, F&& f) {
+    if (cfg.nwv == 4) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{});
+    if (cfg.fb == 1) return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
+}
+}  // namespace
+
 int32_t nlam_detail::fwd_wide(const nlam_mlp_fwd_t* p, hipStream_t stream) {
     const WideCfg cfg = wide_cfg(p->hid > p->dout ? p->hid : p->dout);
-    {
-        if ((p->flags & NLAM_F_WPACK_READY) == 0) {
-            pack_jobs_t jobs;
-            build_fwd_wide_jobs(p, jobs);
-            launch_pack(jobs, stream);
-        }
-        const size_t lds = fwd_wide_lds(p, cfg.nwv);
-        const int wblocks = wide_grid((long)p->ntiles * p->batch, lds, cfg.nwv);
-#define NLAM_LAUNCH_FWD_WIDE(NWV_, FB_)                                                                       \
-    do {                                                                                                      \
-        int rc = set_lds(mlp_fwd_wide_kernel<NWV_, FB_>, lds);                                                \
-        if (rc != 0) return rc;                                                                               \
-        hipLaunchKernelGGL((mlp_fwd_wide_kernel<NWV_, FB_>), dim3(wblocks), dim3(NWV_ * 64), lds, stream, *p); \
-    } while (0)
-        if (cfg.nwv == 4) NLAM_LAUNCH_FWD_WIDE(4, 1);
-        else if (cfg.fb == 1) NLAM_LAUNCH_FWD_WIDE(8, 1);
-        else NLAM_LAUNCH_FWD_WIDE(8, 2);
-        return (int32_t)hipGetLastError();
+    if ((p->flags & NLAM_F_WPACK_READY) == 0) {
+        pack_jobs_t jobs;
+        build_fwd_wide_jobs(p, jobs);
+        launch_pack(jobs, stream);
     }
+    const size_t lds = fwd_wide_lds(p, cfg.nwv);
+    const dim3 grid(wide_grid((long)p->ntiles * p->batch, lds, cfg.nwv));
+    return pick_wide(cfg, [&](auto nwv, auto fb) { return launch<mlp_fwd_wide_kernel<nwv, fb>>(grid, dim3(nwv * 64), lds, stream, *p); });
 }
 #endif
 
@@ -5659,8 +5641,7 @@ int32_t nlam_detail::fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream) {
     // launch shape: one persistent workgroup of kFwdWaves waves per CU (fewer workgroups than CUs only when there
     // are fewer tiles than CUs); tiles are dealt to workgroups first, then to waves
     const long ttiles = (long)p->ntiles * p->batch;
-    const int nwaves = kFwdWaves;
-    const int blocks = (int)(ttiles < 1 ? 1 : (ttiles < kMaxGridBlocks ? ttiles : kMaxGridBlocks));
+    const dim3 grid((int)(ttiles < 1 ? 1 : (ttiles < kMaxGridBlocks ? ttiles : kMaxGridBlocks))), block(kFwdWaves * 64);
     const int HB = (p->hid + 31) / 32, OB = (p->dout + 31) / 32;
     // an output width that is not a whole 32-column block runs on the split-bf16 kernels when nothing downstream of GEMM2
     // needs whole blocks: no LayerNorm, no aggregation, no residual (output_map, graph/base.py:322); W2 / b2 are zero-padded
@@ -5694,38 +5675,38 @@ int32_t nlam_detail::fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream) {
             pc.cat_bstride[k] = 0;
             pc.cat_width[k] = 0;
         }
-#define NLAM_LAUNCH_FWDCAT1(HB_, NS_)                                                                                                    \
-    do {                                                                                                                                \
-        const size_t lds = fwd_lds_bytes(p, HB_, HB_, NS_);                                                                             \
-        int rc = set_lds(mlp_fwd_bf_kernel<HB_, HB_, NS_, true, false, false, true>, lds);                                              \
-        if (rc != 0) return rc;                                                                                                         \
-        hipLaunchKernelGGL((mlp_fwd_bf_kernel<HB_, HB_, NS_, true, false, false, true>), dim3(blocks), dim3(nwaves * 64), lds, stream, pc); \
-    } while (0)
-#define NLAM_LAUNCH_FWDCAT(HB_)                       \
-    do {                                              \
-        if (ns == 3) NLAM_LAUNCH_FWDCAT1(HB_, 3);      \
-        else if (ns == 2) NLAM_LAUNCH_FWDCAT1(HB_, 2); \
-        else NLAM_LAUNCH_FWDCAT1(HB_, 1);              \
-    } while (0)
-        if (HB == 1) NLAM_LAUNCH_FWDCAT(1);
-        else NLAM_LAUNCH_FWDCAT(2);
-        return (int32_t)hipGetLastError();
+        return pick_else<2, 1>(HB, [&](auto hb) {
+            return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+                return launch<mlp_fwd_bf_kernel<hb, hb, nsc, true, false, false, true>>(grid, block, fwd_lds_bytes(p, hb, hb, nsc), stream, pc);
+            });
+        });
     }
     if (p->flags & NLAM_F_PRE_ADD) {   // factorised edge MLP: split-bf16 modes, whole 32-column units, addends of width hid
         bool ok = ns > 0 && !ragged && p->nsrc >= 2 && (p->flags & NLAM_F_ADD_SRC1) == 0 && HB == OB;
         for (int s = 1; s < p->nsrc; ++s) ok = ok && p->src[s].width == p->hid;
         if (!ok) return NLAM_EUNSUP;
-        if (HB == 1) NLAM_LAUNCH_FWDPRE(1, 1);
-        else if (HB == 2) NLAM_LAUNCH_FWDPRE(2, 2);
-        else return NLAM_EUNSUP;
-        return (int32_t)hipGetLastError();
+        return pick<1, 2>(HB, [&](auto hb) {
+            return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+                return pick_bool(resid, [&](auto res) {
+                    return launch<mlp_fwd_bf_kernel<hb, hb, nsc, false, res, true>>(grid, block, fwd_lds_bytes(p, hb, hb, nsc), stream, *p);
+                });
+            });
+        });
     }
-    if (HB == 1 && OB == 1) NLAM_LAUNCH_FWD(1, 1);
-    else if (HB == 2 && OB == 1) NLAM_LAUNCH_FWD(2, 1);
-    else if (HB == 1 && OB == 2) NLAM_LAUNCH_FWD(1, 2);
-    else if (HB == 2 && OB == 2) NLAM_LAUNCH_FWD(2, 2);
-    else return NLAM_EUNSUP;
-    return (int32_t)hipGetLastError();
+    return pick<1, 2>(HB, [&](auto hb) {
+        return pick<1, 2>(OB, [&](auto ob) -> int32_t {
+            if (ns == 0)   // fp32 MFMA
+                return pick_bool(fast, [&](auto fs) {
+                    return launch<mlp_fwd_kernel<hb, ob, fs, 0>>(grid, block, fwd_lds_bytes(p, hb, ob, 0), stream, *p);
+                });
+            return pick<3, 2, 1>(ns, [&](auto nsc) {   // <HB, OB, NS, RAG, RES>
+                const size_t lds = fwd_lds_bytes(p, hb, ob, nsc);
+                if (ragged) return launch<mlp_fwd_bf_kernel<hb, ob, nsc, true, false>>(grid, block, lds, stream, *p);
+                if (resid) return launch<mlp_fwd_bf_kernel<hb, ob, nsc, false, true>>(grid, block, lds, stream, *p);
+                return launch<mlp_fwd_bf_kernel<hb, ob, nsc, false, false>>(grid, block, lds, stream, *p);
+            });
+        });
+    });
 }
 #endif
 
@@ -5748,13 +5729,13 @@ int32_t nlam_detail::fwd_check(const nlam_mlp_fwd_t* p) {
             wsum += p->cat_width[k];
         }
         if (wsum != p->src[0].width) return NLAM_EINVAL;
-        if (fwd_is_wide(p) || wsum % 4 != 0 || (p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1 | NLAM_F_PRE_ADD)) != 0 || p->tiles != nullptr)
+        if (mlp_is_wide(p) || wsum % 4 != 0 || (p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1 | NLAM_F_PRE_ADD)) != 0 || p->tiles != nullptr)
             return NLAM_EUNSUP;
         if (p->ncat > 4) return NLAM_EUNSUP;   // the kernel resolves a column among four pieces
         if (p->rows > 0 && p->batch > 0 && ((long)p->rows >= (1L << 31) || p->batch >= (1 << 30))) return NLAM_EUNSUP;
     }
     if (p->rows == 0) return 0;
-    if (fwd_is_wide(p)) {
+    if (mlp_is_wide(p)) {
         if ((p->flags & NLAM_F_PRE_ADD) && fwd_wbf_ns(p) == 0) return NLAM_EUNSUP;   // the fp32 wide kernels have no factorised variant
         const WideCfg cfg = wide_cfg(p->hid > p->dout ? p->hid : p->dout);
         if (cfg.nwv == 0) return NLAM_EUNSUP;
@@ -5780,10 +5761,10 @@ int32_t nlam_detail::bwd_check(const nlam_mlp_bwd_t* p) {
             return NLAM_EINVAL;
     }
     if ((p->flags & NLAM_F_NO_ACT) && (p->flags & (NLAM_F_MM_MASK | NLAM_F_PRE_ADD | NLAM_F_LEAF_WGRAD)) != 0) return NLAM_EUNSUP;
-    if ((p->flags & NLAM_F_STORE_BF16) && !(bwd_is_wide(p) && bwd_wbf_ns(p) == 1)) return NLAM_EUNSUP;
+    if ((p->flags & NLAM_F_STORE_BF16) && !(mlp_is_wide(p) && bwd_wbf_ns(p) == 1)) return NLAM_EUNSUP;
     if (p->rows == 0) return 0;
-    if (bwd_is_wide(p) && (p->flags & NLAM_F_PRE_ADD) && bwd_wbf_ns(p) == 0) return NLAM_EUNSUP;
-    if (bwd_is_wide(p)) {
+    if (mlp_is_wide(p) && (p->flags & NLAM_F_PRE_ADD) && bwd_wbf_ns(p) == 0) return NLAM_EUNSUP;
+    if (mlp_is_wide(p)) {
         const WideCfg cfg = wide_cfg(bwd_wide_maxw(p));
         if (cfg.nwv == 0) return NLAM_EUNSUP;
         const int64_t need = nlam_mlp_bwd_wpack_floats(p);
@@ -5804,7 +5785,7 @@ int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream) {
     if (bad != 0) return bad;
     if (p->rows == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (bwd_is_wide(p)) {
+    if (mlp_is_wide(p)) {
         if (bwd_wbf_ns(p) > 0) return nlam_detail::bwd_wbf(p, stream);   // split-bf16 matrix path (nlam_wbf.inc)
         if (p->flags & NLAM_F_ACC_DSRC0) return NLAM_EUNSUP;
         return nlam_detail::bwd_wide(p, stream);
@@ -5817,77 +5798,56 @@ int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream) {
 #endif
 
 #if NLAM_IN_TU(4)
+namespace {
+// one line of bwd_wbf's plan tables: mlp_bwd_wbf_kernel<NS, NW, FG, FB, RT, SBF, V4>, V4 from the widths
+template <int NS, int NW, int FG, int FB, int RT, bool SBF>
+int32_t launch_bwd_wbf(bool v4, int blocks, size_t lds, hipStream_t stream, const nlam_mlp_bwd_t& p) {
+    return pick_bool(v4, [&](auto v4c) {
+        return launch<mlp_bwd_wbf_kernel<NS, NW, FG, FB, RT, SBF, v4c>>(dim3(blocks), dim3(NW * 64), lds, stream, p);
+    });
+}
+}  // namespace
+
 int32_t nlam_detail::bwd_wbf(const nlam_mlp_bwd_t* p, hipStream_t stream) {
     const int wns = bwd_wbf_ns(p);
-    {
-            const WbfBwdPlan pl = wbf_bwd_choose(bwd_wide_maxw(p));
-            if ((p->flags & NLAM_F_WPACK_READY) == 0) {
-                packbf_jobs_t jobs;
-                const long most = build_bwd_wbf_jobs(p, wns, jobs);
-                long pblocks = (most + 255) / 256;
-                if (pblocks > 1024) pblocks = 1024;
-                if (wns == 1) hipLaunchKernelGGL(pack_bf_kernel<1>, dim3((int)pblocks, jobs.njobs), dim3(256), 0, stream, jobs);
-                else hipLaunchKernelGGL(pack_bf_kernel<3>, dim3((int)pblocks, jobs.njobs), dim3(256), 0, stream, jobs);
-            }
-            if (bwd_edge_ok(p)) {
-                const int eblocks = nlam_mlp_bwd_blocks(p);
-                if (wns == 3) {
-                    const size_t elds = bwd_edge_lds<3, 256>();
-                    int rc = set_lds(mlp_bwd_edge_kernel<3, 256, false>, elds);
-                    if (rc != 0) return rc;
-                    hipLaunchKernelGGL((mlp_bwd_edge_kernel<3, 256, false>), dim3(eblocks), dim3(512), elds, stream, *p);
-                } else if (p->flags & NLAM_F_STORE_BF16) {
-                    const size_t elds = bwd_edge_lds<1, 512>();
-                    int rc = set_lds(mlp_bwd_edge_kernel<1, 512, true>, elds);
-                    if (rc != 0) return rc;
-                    hipLaunchKernelGGL((mlp_bwd_edge_kernel<1, 512, true>), dim3(eblocks), dim3(512), elds, stream, *p);
-                } else {
-                    const size_t elds = bwd_edge_lds<1, 512>();
-                    int rc = set_lds(mlp_bwd_edge_kernel<1, 512, false>, elds);
-                    if (rc != 0) return rc;
-                    hipLaunchKernelGGL((mlp_bwd_edge_kernel<1, 512, false>), dim3(eblocks), dim3(512), elds, stream, *p);
-                }
-                return (int32_t)hipGetLastError();
-            }
-            const size_t lds = bwd_wbf_lds(p, wns, pl);
-            const int wblocks = nlam_mlp_bwd_blocks(p) / pl.rg;
-            bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0 && p->dz2_ld == 0;
-            for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
-#define NLAM_LAUNCH_BWD_WBF1(NS_, NW_, FG_, FB_, RT_, SBF_, V4_)                                                               \
-    do {                                                                                                                      \
-        int rc = set_lds(mlp_bwd_wbf_kernel<NS_, NW_, FG_, FB_, RT_, SBF_, V4_>, lds);                                        \
-        if (rc != 0) return rc;                                                                                               \
-        hipLaunchKernelGGL((mlp_bwd_wbf_kernel<NS_, NW_, FG_, FB_, RT_, SBF_, V4_>), dim3(wblocks), dim3(NW_ * 64), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_BWD_WBF(NS_, NW_, FG_, FB_, RT_)                               \
-    do {                                                                           \
-        if (v4) NLAM_LAUNCH_BWD_WBF1(NS_, NW_, FG_, FB_, RT_, false, true);        \
-        else NLAM_LAUNCH_BWD_WBF1(NS_, NW_, FG_, FB_, RT_, false, false);          \
-    } while (0)
-#define NLAM_LAUNCH_BWD_WBF_S(NW_, FG_, FB_, RT_)                                  \
-    do {                                                                           \
-        if (v4) NLAM_LAUNCH_BWD_WBF1(1, NW_, FG_, FB_, RT_, true, true);           \
-        else NLAM_LAUNCH_BWD_WBF1(1, NW_, FG_, FB_, RT_, true, false);             \
-    } while (0)
-            if (p->flags & NLAM_F_STORE_BF16) {
-                if (wns != 1 || p->hid % 32 != 0 || p->dout % 32 != 0 || p->dz2_ld != 0 || pl.cfg == 1) return NLAM_EUNSUP;
-                if (pl.cfg == 2) NLAM_LAUNCH_BWD_WBF_S(8, 8, 1, 2);
-                else if (pl.cfg == 5) NLAM_LAUNCH_BWD_WBF_S(4, 4, 2, 1);
-                else NLAM_LAUNCH_BWD_WBF_S(8, 8, 2, 1);
-                return (int32_t)hipGetLastError();
-            }
-            if (wns == 1) {
-                if (pl.cfg == 1) NLAM_LAUNCH_BWD_WBF(1, 8, 4, 1, 2);
-                else if (pl.cfg == 2) NLAM_LAUNCH_BWD_WBF(1, 8, 8, 1, 2);
-                else if (pl.cfg == 5) NLAM_LAUNCH_BWD_WBF(1, 4, 4, 2, 1);
-                else NLAM_LAUNCH_BWD_WBF(1, 8, 8, 2, 1);
-            } else {
-                if (pl.cfg == 1) NLAM_LAUNCH_BWD_WBF(3, 8, 4, 1, 2);
-                else if (pl.cfg == 2) NLAM_LAUNCH_BWD_WBF(3, 8, 8, 1, 2);
-                else if (pl.cfg == 5) NLAM_LAUNCH_BWD_WBF(3, 4, 4, 2, 1);
-                else NLAM_LAUNCH_BWD_WBF(3, 8, 8, 2, 1);
-            }
-            return (int32_t)hipGetLastError();
+    const WbfBwdPlan pl = wbf_bwd_choose(bwd_wide_maxw(p));
+    if ((p->flags & NLAM_F_WPACK_READY) == 0) {
+        packbf_jobs_t jobs;
+        const long most = build_bwd_wbf_jobs(p, wns, jobs);
+        launch_pack_bf(jobs, most, wns, stream);
+    }
+    if (bwd_edge_ok(p)) {
+        const dim3 egrid(nlam_mlp_bwd_blocks(p)), eblock(512);
+        if (wns == 3) return launch<mlp_bwd_edge_kernel<3, 256, false>>(egrid, eblock, bwd_edge_lds<3, 256>(), stream, *p);
+        if (p->flags & NLAM_F_STORE_BF16) return launch<mlp_bwd_edge_kernel<1, 512, true>>(egrid, eblock, bwd_edge_lds<1, 512>(), stream, *p);
+        return launch<mlp_bwd_edge_kernel<1, 512, false>>(egrid, eblock, bwd_edge_lds<1, 512>(), stream, *p);
+    }
+    const size_t lds = bwd_wbf_lds(p, wns, pl);
+    const int wblocks = nlam_mlp_bwd_blocks(p) / pl.rg;
+    bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0 && p->dz2_ld == 0;
+    for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
+    // pl.cfg -> <NS, NW, FG, FB, RT, SBF>: the instantiations that exist, one per line
+    if (p->flags & NLAM_F_STORE_BF16) {
+        if (wns != 1 || p->hid % 32 != 0 || p->dout % 32 != 0 || p->dz2_ld != 0 || pl.cfg == 1) return NLAM_EUNSUP;
+        switch (pl.cfg) {
+        case 2: return launch_bwd_wbf<1, 8, 8, 1, 2, true>(v4, wblocks, lds, stream, *p);
+        case 5: return launch_bwd_wbf<1, 4, 4, 2, 1, true>(v4, wblocks, lds, stream, *p);
+        default: return launch_bwd_wbf<1, 8, 8, 2, 1, true>(v4, wblocks, lds, stream, *p);
+        }
+    }
+    if (wns == 1) {
+        switch (pl.cfg) {
+        case 1: return launch_bwd_wbf<1, 8, 4, 1, 2, false>(v4, wblocks, lds, stream, *p);
+        case 2: return launch_bwd_wbf<1, 8, 8, 1, 2, false>(v4, wblocks, lds, stream, *p);
+        case 5: return launch_bwd_wbf<1, 4, 4, 2, 1, false>(v4, wblocks, lds, stream, *p);
+        default: return launch_bwd_wbf<1, 8, 8, 2, 1, false>(v4, wblocks, lds, stream, *p);
+        }
+    }
+    switch (pl.cfg) {
+    case 1: return launch_bwd_wbf<3, 8, 4, 1, 2, false>(v4, wblocks, lds, stream, *p);
+    case 2: return launch_bwd_wbf<3, 8, 8, 1, 2, false>(v4, wblocks, lds, stream, *p);
+    case 5: return launch_bwd_wbf<3, 4, 4, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    default: return launch_bwd_wbf<3, 8, 8, 2, 1, false>(v4, wblocks, lds, stream, *p);
     }
 }
 #endif
@@ -5895,25 +5855,14 @@ int32_t nlam_detail::bwd_wbf(const nlam_mlp_bwd_t* p, hipStream_t stream) {
 #if NLAM_IN_TU(3)
 int32_t nlam_detail::bwd_wide(const nlam_mlp_bwd_t* p, hipStream_t stream) {
     const WideCfg cfg = wide_cfg(bwd_wide_maxw(p));
-    {
-        if ((p->flags & NLAM_F_WPACK_READY) == 0) {
-            pack_jobs_t jobs;
-            build_bwd_wide_jobs(p, jobs);
-            launch_pack(jobs, stream);
-        }
-        const size_t lds = bwd_wide_lds(p, cfg.nwv);
-        const int wblocks = nlam_mlp_bwd_blocks(p);
-#define NLAM_LAUNCH_BWD_WIDE(NWV_, FB_)                                                                       \
-    do {                                                                                                      \
-        int rc = set_lds(mlp_bwd_wide_kernel<NWV_, FB_>, lds);                                                \
-        if (rc != 0) return rc;                                                                               \
-        hipLaunchKernelGGL((mlp_bwd_wide_kernel<NWV_, FB_>), dim3(wblocks), dim3(NWV_ * 64), lds, stream, *p); \
-    } while (0)
-        if (cfg.nwv == 4) NLAM_LAUNCH_BWD_WIDE(4, 1);
-        else if (cfg.fb == 1) NLAM_LAUNCH_BWD_WIDE(8, 1);
-        else NLAM_LAUNCH_BWD_WIDE(8, 2);
-        return (int32_t)hipGetLastError();
+    if ((p->flags & NLAM_F_WPACK_READY) == 0) {
+        pack_jobs_t jobs;
+        build_bwd_wide_jobs(p, jobs);
+        launch_pack(jobs, stream);
     }
+    const size_t lds = bwd_wide_lds(p, cfg.nwv);
+    const dim3 grid(nlam_mlp_bwd_blocks(p));
+    return pick_wide(cfg, [&](auto nwv, auto fb) { return launch<mlp_bwd_wide_kernel<nwv, fb>>(grid, dim3(nwv * 64), lds, stream, *p); });
 }
 #endif
 
@@ -5938,20 +5887,10 @@ int32_t nlam_detail::fwd_wide_group(const nlam_mlp_fwd_t* ps, int n, hipStream_t
     }
     int blocks[NLAM_MAX_GROUP];
     wide_group_blocks(tiles, n, wide_grid(1L << 40, lds, cfg.nwv), blocks);
-    G.n = n;
-    G.first[0] = 0;
-    for (int k = 0; k < n; ++k) G.first[k + 1] = G.first[k] + blocks[k];
-    for (int k = n + 1; k <= NLAM_MAX_GROUP; ++k) G.first[k] = G.first[n];
-#define NLAM_LAUNCH_FWD_WIDE_G(NWV_, FB_)                                                                              \
-    do {                                                                                                               \
-        int rc = set_lds(mlp_fwd_wide_group_kernel<NWV_, FB_>, lds);                                                   \
-        if (rc != 0) return rc;                                                                                        \
-        hipLaunchKernelGGL((mlp_fwd_wide_group_kernel<NWV_, FB_>), dim3(G.first[n]), dim3(NWV_ * 64), lds, stream, G); \
-    } while (0)
-    if (cfg.nwv == 4) NLAM_LAUNCH_FWD_WIDE_G(4, 1);
-    else if (cfg.fb == 1) NLAM_LAUNCH_FWD_WIDE_G(8, 1);
-    else NLAM_LAUNCH_FWD_WIDE_G(8, 2);
-    return (int32_t)hipGetLastError();
+    group_prefix(G, n, blocks);
+    return pick_wide(cfg, [&](auto nwv, auto fb) {
+        return launch<mlp_fwd_wide_group_kernel<nwv, fb>>(dim3(G.first[n]), dim3(nwv * 64), lds, stream, G);
+    });
 }
 
 int32_t nlam_detail::bwd_wide_group(const nlam_mlp_bwd_t* ps, int n, hipStream_t stream) {
@@ -5971,20 +5910,10 @@ int32_t nlam_detail::bwd_wide_group(const nlam_mlp_bwd_t* ps, int n, hipStream_t
         const size_t l = bwd_wide_lds(&ps[k], cfg.nwv);
         if (l > lds) lds = l;
     }
-    G.n = n;
-    G.first[0] = 0;
-    for (int k = 0; k < n; ++k) G.first[k + 1] = G.first[k] + blocks[k];
-    for (int k = n + 1; k <= NLAM_MAX_GROUP; ++k) G.first[k] = G.first[n];
-#define NLAM_LAUNCH_BWD_WIDE_G(NWV_, FB_)                                                                              \
-    do {                                                                                                               \
-        int rc = set_lds(mlp_bwd_wide_group_kernel<NWV_, FB_>, lds);                                                   \
-        if (rc != 0) return rc;                                                                                        \
-        hipLaunchKernelGGL((mlp_bwd_wide_group_kernel<NWV_, FB_>), dim3(G.first[n]), dim3(NWV_ * 64), lds, stream, G); \
-    } while (0)
-    if (cfg.nwv == 4) NLAM_LAUNCH_BWD_WIDE_G(4, 1);
-    else if (cfg.fb == 1) NLAM_LAUNCH_BWD_WIDE_G(8, 1);
-    else NLAM_LAUNCH_BWD_WIDE_G(8, 2);
-    return (int32_t)hipGetLastError();
+    group_prefix(G, n, blocks);
+    return pick_wide(cfg, [&](auto nwv, auto fb) {
+        return launch<mlp_bwd_wide_group_kernel<nwv, fb>>(dim3(G.first[n]), dim3(nwv * 64), lds, stream, G);
+    });
 }
 #endif
 
@@ -6002,7 +5931,7 @@ int32_t nlam_mlp_group_blocks(const int64_t* tiles, int32_t n, int32_t* blocks) 
 int32_t nlam_mlp_fwd_group(const nlam_mlp_fwd_t* ps, int32_t n, void* hip_stream) {
     NLAM_RANGE("nlam_mlp_fwd_group");
     if (ps == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
-    if (fwd_is_wide(&ps[0])) {   // members of the fp32 wide family (the chunks of a SplitMLPs layer at d = 128): any source / flag set, one shape
+    if (mlp_is_wide(&ps[0])) {   // members of the fp32 wide family (the chunks of a SplitMLPs layer at d = 128): any source / flag set, one shape
         for (int k = 0; k < n; ++k) {
             const nlam_mlp_fwd_t& p = ps[k];
             const int32_t bad = nlam_detail::fwd_check(&p);
@@ -6023,7 +5952,7 @@ int32_t nlam_mlp_fwd_group(const nlam_mlp_fwd_t* ps, int32_t n, void* hip_stream
         if (p.W1 == nullptr || p.W2 == nullptr || p.batch < 1 || p.rows < 1 || p.out == nullptr) return NLAM_EINVAL;
         // same kernel instantiation for every member: one source of at most 64 columns, whole output blocks, no residual /
         // aggregation / scatter, the same matrix mode
-        if (p.nsrc != 1 || fwd_is_wide(&p) || p.hid != ps[0].hid || p.dout != ps[0].dout || p.hid % 32 != 0 || p.dout % 32 != 0) return NLAM_EUNSUP;
+        if (p.nsrc != 1 || mlp_is_wide(&p) || p.hid != ps[0].hid || p.dout != ps[0].dout || p.hid % 32 != 0 || p.dout % 32 != 0) return NLAM_EUNSUP;
         if ((p.flags & ~NLAM_F_MM_MASK) != 0 || (p.flags & NLAM_F_MM_MASK) != (ps[0].flags & NLAM_F_MM_MASK)) return NLAM_EUNSUP;
         if (p.aggr != nullptr || p.out_idx != nullptr || p.src[0].idx != nullptr || p.tiles != nullptr) return NLAM_EUNSUP;
         if ((p.ln_w == nullptr) != (ps[0].ln_w == nullptr)) return NLAM_EUNSUP;
@@ -6034,27 +5963,13 @@ int32_t nlam_mlp_fwd_group(const nlam_mlp_fwd_t* ps, int32_t n, void* hip_stream
     }
     int blocks[NLAM_MAX_GROUP];
     group_blocks(tiles, n, blocks);
-    G.n = n;
-    G.first[0] = 0;
-    for (int k = 0; k < n; ++k) G.first[k + 1] = G.first[k] + blocks[k];
-    for (int k = n + 1; k <= NLAM_MAX_GROUP; ++k) G.first[k] = G.first[n];
+    group_prefix(G, n, blocks);
     hipStream_t stream = (hipStream_t)hip_stream;
-#define NLAM_LAUNCH_FWDG(HB_, NS_)                                                                                         \
-    do {                                                                                                                   \
-        int rc = set_lds(mlp_fwd_bf_group_kernel<HB_, HB_, NS_>, lds);                                                     \
-        if (rc != 0) return rc;                                                                                            \
-        hipLaunchKernelGGL((mlp_fwd_bf_group_kernel<HB_, HB_, NS_>), dim3(G.first[n]), dim3(kFwdThreads), lds, stream, G); \
-    } while (0)
-    if (HB == 1) {
-        if (ns == 3) NLAM_LAUNCH_FWDG(1, 3);
-        else if (ns == 2) NLAM_LAUNCH_FWDG(1, 2);
-        else NLAM_LAUNCH_FWDG(1, 1);
-    } else {
-        if (ns == 3) NLAM_LAUNCH_FWDG(2, 3);
-        else if (ns == 2) NLAM_LAUNCH_FWDG(2, 2);
-        else NLAM_LAUNCH_FWDG(2, 1);
-    }
-    return (int32_t)hipGetLastError();
+    return pick_else<2, 1>(HB, [&](auto hb) {
+        return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+            return launch<mlp_fwd_bf_group_kernel<hb, hb, nsc>>(dim3(G.first[n]), dim3(kFwdThreads), lds, stream, G);
+        });
+    });
 }
 
 }  // extern "C"
@@ -6064,7 +5979,7 @@ int32_t nlam_mlp_fwd_group(const nlam_mlp_fwd_t* ps, int32_t n, void* hip_stream
 extern "C" int32_t nlam_mlp_bwd_group(const nlam_mlp_bwd_t* ps, int32_t n, void* hip_stream) {
     NLAM_RANGE("nlam_mlp_bwd_group");
     if (ps == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
-    if (bwd_is_wide(&ps[0])) {   // fp32 wide family: see nlam_mlp_fwd_group
+    if (mlp_is_wide(&ps[0])) {   // fp32 wide family: see nlam_mlp_fwd_group
         if (ps[0].flags & NLAM_F_LEAF_WGRAD) return NLAM_EUNSUP;   // weight gradients inside the kernel: narrow members only
         int blocks[NLAM_MAX_GROUP];
         const int32_t rcb = nlam_mlp_bwd_group_blocks(ps, n, blocks);   // checks the members
@@ -6084,7 +5999,7 @@ extern "C" int32_t nlam_mlp_bwd_group(const nlam_mlp_bwd_t* ps, int32_t n, void*
         const nlam_mlp_bwd_t& p = ps[k];
         if (p.W1 == nullptr || p.W2 == nullptr || p.batch < 1 || p.rows < 1 || p.g_out == nullptr) return NLAM_EINVAL;
         if ((p.flags & NLAM_F_LEAF_WGRAD) ? p.b1 == nullptr : p.z1 == nullptr) return NLAM_EINVAL;   // fused weight gradients: z1 is recomputed
-        if (p.nsrc != 1 || bwd_is_wide(&p) || p.hid != ps[0].hid || p.dout != ps[0].dout || p.hid % 32 != 0 || p.dout % 32 != 0) return NLAM_EUNSUP;
+        if (p.nsrc != 1 || mlp_is_wide(&p) || p.hid != ps[0].hid || p.dout != ps[0].dout || p.hid % 32 != 0 || p.dout % 32 != 0) return NLAM_EUNSUP;
         if ((p.flags & ~(NLAM_F_MM_MASK | NLAM_F_LEAF_WGRAD)) != 0 || (p.flags & (NLAM_F_MM_MASK | NLAM_F_LEAF_WGRAD)) != (ps[0].flags & (NLAM_F_MM_MASK | NLAM_F_LEAF_WGRAD)))
             return NLAM_EUNSUP;
         if ((p.flags & NLAM_F_LEAF_WGRAD) && (p.src[0].width > 4 || p.src[0].ptr == nullptr || p.src[0].idx != nullptr || p.dz2 == nullptr || p.vec_partials == nullptr))
@@ -6097,48 +6012,23 @@ extern "C" int32_t nlam_mlp_bwd_group(const nlam_mlp_bwd_t* ps, int32_t n, void*
         if (l > lds) lds = l;
     }
     group_blocks(tiles, n, blocks);
-    G.n = n;
-    G.first[0] = 0;
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < n; ++k)
         if (ps[k].vec_partials != nullptr && ps[k].vec_partials_rows < blocks[k]) return NLAM_EINVAL;
-        G.first[k + 1] = G.first[k] + blocks[k];
-    }
-    for (int k = n + 1; k <= NLAM_MAX_GROUP; ++k) G.first[k] = G.first[n];
+    group_prefix(G, n, blocks);
     hipStream_t stream = (hipStream_t)hip_stream;
-#define NLAM_LAUNCH_BWDG1(HB_, NS_, LW_)                                                                                            \
-    do {                                                                                                                            \
-        int rc = set_lds(mlp_bwd_fast_group_kernel<HB_, HB_, NS_, LW_>, lds);                                                       \
-        if (rc != 0) return rc;                                                                                                     \
-        hipLaunchKernelGGL((mlp_bwd_fast_group_kernel<HB_, HB_, NS_, LW_>), dim3(G.first[n]), dim3(LW_ ? kLeafWaves * 64 : kBlockThreads), lds, stream, G); \
-    } while (0)
-#define NLAM_LAUNCH_BWDG(HB_, NS_)                            \
-    do {                                                      \
-        if (ps[0].flags & NLAM_F_LEAF_WGRAD) NLAM_LAUNCH_BWDG1(HB_, NS_, true); \
-        else NLAM_LAUNCH_BWDG1(HB_, NS_, false);              \
-    } while (0)
-    if (HB == 1) {
-        if (ns == 3) NLAM_LAUNCH_BWDG(1, 3);
-        else if (ns == 2) NLAM_LAUNCH_BWDG(1, 2);
-        else NLAM_LAUNCH_BWDG(1, 1);
-    } else {
-        if (ns == 3) NLAM_LAUNCH_BWDG(2, 3);
-        else if (ns == 2) NLAM_LAUNCH_BWDG(2, 2);
-        else NLAM_LAUNCH_BWDG(2, 1);
-    }
-    return (int32_t)hipGetLastError();
+    return pick_else<2, 1>(HB, [&](auto hb) {
+        return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+            return pick_bool((ps[0].flags & NLAM_F_LEAF_WGRAD) != 0, [&](auto lw) {
+                return launch<mlp_bwd_fast_group_kernel<hb, hb, nsc, lw>>(dim3(G.first[n]), dim3(lw ? kLeafWaves * 64 : kBlockThreads), lds, stream, G);
+            });
+        });
+    });
 }
 #endif
 
 #if NLAM_IN_TU(2)
-#define NLAM_LAUNCH_BWD(HB_, OB_)                                                                      \
-    do {                                                                                               \
-        const size_t lds = bwd_lds_bytes(p, HB_, OB_);                                                 \
-        int rc = set_lds(mlp_bwd_kernel<HB_, OB_>, lds);                                               \
-        if (rc != 0) return rc;                                                                        \
-        hipLaunchKernelGGL((mlp_bwd_kernel<HB_, OB_>), dim3(blocks), dim3(kBlockThreads), lds, stream, *p); \
-    } while (0)
 int32_t nlam_detail::bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream) {
-    const int blocks = grid_blocks((long)p->ntiles * p->batch);
+    const dim3 grid(grid_blocks((long)p->ntiles * p->batch)), block(kBlockThreads);
     const int HB = (p->hid + 31) / 32, OB = (p->dout + 31) / 32;
     const bool ro = bwd_ragged_out(p);   // output_map: dout not a whole block, no LayerNorm -> split-bf16 fast kernel, dz2 padded to OB * 32 columns
     if ((ro ? OB * 32 : 0) != p->dz2_ld) return NLAM_EINVAL;   // the caller sized dz2 with nlam_mlp_bwd_dz2_ld
@@ -6155,50 +6045,24 @@ int32_t nlam_detail::bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream) {
     }
     if (fast) {
         const int ns = (int)((p->flags & NLAM_F_MM_MASK) >> NLAM_F_MM_SHIFT);
-#define NLAM_LAUNCH_BWDF1(HB_, OB_, NS_)                                                                            \
-    do {                                                                                                            \
-        const size_t lds = bwd_fast_lds_bytes(p, HB_, OB_, NS_);                                                    \
-        int rc = set_lds(mlp_bwd_fast_kernel<HB_, OB_, NS_>, lds);                                                  \
-        if (rc != 0) return rc;                                                                                     \
-        hipLaunchKernelGGL((mlp_bwd_fast_kernel<HB_, OB_, NS_>), dim3(blocks), dim3(kBlockThreads), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_BWDF(HB_, OB_)                     \
-    do {                                               \
-        if (ns == 3) NLAM_LAUNCH_BWDF1(HB_, OB_, 3);      \
-        else if (ns == 2) NLAM_LAUNCH_BWDF1(HB_, OB_, 2); \
-        else if (ns == 1) NLAM_LAUNCH_BWDF1(HB_, OB_, 1); \
-        else NLAM_LAUNCH_BWDF1(HB_, OB_, 0);              \
-    } while (0)
-#define NLAM_LAUNCH_BWDRO1(HB_, OB_, NS_)                                                                                  \
-    do {                                                                                                                  \
-        const size_t lds = bwd_fast_lds_bytes(p, HB_, OB_, NS_);                                                          \
-        int rc = set_lds(mlp_bwd_fast_kernel<HB_, OB_, NS_, true>, lds);                                                  \
-        if (rc != 0) return rc;                                                                                           \
-        hipLaunchKernelGGL((mlp_bwd_fast_kernel<HB_, OB_, NS_, true>), dim3(blocks), dim3(kBlockThreads), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_BWDRO(HB_, OB_)                     \
-    do {                                                \
-        if (ns == 3) NLAM_LAUNCH_BWDRO1(HB_, OB_, 3);      \
-        else if (ns == 2) NLAM_LAUNCH_BWDRO1(HB_, OB_, 2); \
-        else NLAM_LAUNCH_BWDRO1(HB_, OB_, 1);              \
-    } while (0)
-        if (ro) {   // OB == 1 by construction (dout < 32 ... the only shape the reference has: output_map)
-            if (HB == 1) NLAM_LAUNCH_BWDRO(1, 1);
-            else NLAM_LAUNCH_BWDRO(2, 1);
-            return (int32_t)hipGetLastError();
-        }
-        if (HB == 1 && OB == 1) NLAM_LAUNCH_BWDF(1, 1);
-        else if (HB == 2 && OB == 1) NLAM_LAUNCH_BWDF(2, 1);
-        else if (HB == 1 && OB == 2) NLAM_LAUNCH_BWDF(1, 2);
-        else NLAM_LAUNCH_BWDF(2, 2);
-        return (int32_t)hipGetLastError();
+        if (ro)   // OB == 1 by construction (dout < 32 ... the only shape the reference has: output_map)
+            return pick_else<2, 1>(HB, [&](auto hb) {
+                return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+                    return launch<mlp_bwd_fast_kernel<hb, 1, nsc, true>>(grid, block, bwd_fast_lds_bytes(p, hb, 1, nsc), stream, *p);
+                });
+            });
+        const bool listed = (HB == 1 || HB == 2) && (OB == 1 || OB == 2);   // every other pair runs as (2, 2)
+        return pick<1, 2>(listed ? HB : 2, [&](auto hb) {
+            return pick<1, 2>(listed ? OB : 2, [&](auto ob) {
+                return pick_else<0, 3, 2, 1>(ns, [&](auto nsc) {
+                    return launch<mlp_bwd_fast_kernel<hb, ob, nsc>>(grid, block, bwd_fast_lds_bytes(p, hb, ob, nsc), stream, *p);
+                });
+            });
+        });
     }
-    if (HB == 1 && OB == 1) NLAM_LAUNCH_BWD(1, 1);
-    else if (HB == 2 && OB == 1) NLAM_LAUNCH_BWD(2, 1);
-    else if (HB == 1 && OB == 2) NLAM_LAUNCH_BWD(1, 2);
-    else if (HB == 2 && OB == 2) NLAM_LAUNCH_BWD(2, 2);
-    else return NLAM_EUNSUP;
-    return (int32_t)hipGetLastError();
+    return pick<1, 2>(HB, [&](auto hb) {
+        return pick<1, 2>(OB, [&](auto ob) { return launch<mlp_bwd_kernel<hb, ob>>(grid, block, bwd_lds_bytes(p, hb, ob), stream, *p); });
+    });
 }
 #endif
 
@@ -6251,93 +6115,65 @@ int32_t nlam_wgrad_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream) {
 #endif
 
 #if NLAM_IN_TU(4)
+namespace {
+// wgrad_wbf_kernel on 256 x 256 windows (8 waves) or on 128 x 128 windows (4 waves); ABF / SBFS: A / the source stored as bf16
+template <int NS, bool SILU, bool ABF, bool SBFS>
+int32_t launch_wgrad_wbf(bool big, dim3 grid, size_t lds, hipStream_t stream, const nlam_wgrad_t& p) {
+    if (big) return launch<wgrad_wbf_kernel<NS, SILU, 1, 4, 2, 4, ABF, SBFS>>(grid, dim3(4 * 2 * 64), lds, stream, p);
+    return launch<wgrad_wbf_kernel<NS, SILU, 1, 2, 2, 2, ABF, SBFS>>(grid, dim3(2 * 2 * 64), lds, stream, p);
+}
+// wgrad_ldma_kernel: R rows per stage in a ring of NB stages
+template <int NS, bool ABF, bool SBF, bool SILU, int R, int NB>
+int32_t launch_wgrad_ldma(dim3 grid, hipStream_t stream, const nlam_wgrad_t& p) {
+    return launch<wgrad_ldma_kernel<NS, ABF, SBF, SILU, R, NB>>(grid, dim3(512), WgLdma<ABF, SBF, SILU, R, NB>::LDS, stream, p);
+}
+}  // namespace
+
 int32_t nlam_detail::wgrad_wbf(const nlam_wgrad_t* p, int plan, hipStream_t stream) {
-        const int wns = wgrad_wbf_ns(p);
-        // 256 x 256 windows (8 waves) when the output has more than 128 rows, 128 x 128 windows (4 waves) otherwise
-        const bool big = plan != NLAM_WGP_WBF && plan != NLAM_WGP_WBF_B;
-        const int winm = big ? 256 : 128, winn = big ? 256 : 128;
-        const size_t lds = (size_t)2 * ((winm + winn) / 32) * wns * 1024;
-        const dim3 grid(p->nparts, wgrad_windows_of(p, winm, winn));
-#define NLAM_LAUNCH_WG_WBF(NS_, S_, WM_, WN_, NBW_)                                                                       \
-    do {                                                                                                                  \
-        int rc = set_lds(wgrad_wbf_kernel<NS_, S_, 1, WM_, WN_, NBW_>, lds);                                              \
-        if (rc != 0) return rc;                                                                                           \
-        hipLaunchKernelGGL((wgrad_wbf_kernel<NS_, S_, 1, WM_, WN_, NBW_>), grid, dim3(WM_ * WN_ * 64), lds, stream, *p);  \
-    } while (0)
-#define NLAM_LAUNCH_WG_WBF2(NS_, S_)                 \
-    do {                                             \
-        if (big) NLAM_LAUNCH_WG_WBF(NS_, S_, 4, 2, 4); \
-        else NLAM_LAUNCH_WG_WBF(NS_, S_, 2, 2, 2);     \
-    } while (0)
-#define NLAM_LAUNCH_WG_WBF_B(S_, WM_, WN_, NBW_, SB_)                                                                             \
-    do {                                                                                                                          \
-        int rc = set_lds(wgrad_wbf_kernel<1, S_, 1, WM_, WN_, NBW_, true, SB_>, lds);                                              \
-        if (rc != 0) return rc;                                                                                                   \
-        hipLaunchKernelGGL((wgrad_wbf_kernel<1, S_, 1, WM_, WN_, NBW_, true, SB_>), grid, dim3(WM_ * WN_ * 64), lds, stream, *p);  \
-    } while (0)
-#define NLAM_LAUNCH_WG_LDMA(ABF_, SBF_, SILU_, R_, NB_)                                                                   \
-    do {                                                                                                                  \
-        const size_t lds2 = WgLdma<ABF_, SBF_, SILU_, R_, NB_>::LDS;                                                       \
-        int rc = set_lds(wgrad_ldma_kernel<1, ABF_, SBF_, SILU_, R_, NB_>, lds2);                                          \
-        if (rc != 0) return rc;                                                                                           \
-        hipLaunchKernelGGL((wgrad_ldma_kernel<1, ABF_, SBF_, SILU_, R_, NB_>), grid, dim3(512), lds2, stream, *p);         \
-    } while (0)
-#define NLAM_LAUNCH_WG_LDMA3(SILU_, NB_)                                                                                  \
-    do {                                                                                                                  \
-        const size_t lds2 = WgLdma<false, false, SILU_, 16, NB_>::LDS;                                                     \
-        int rc = set_lds(wgrad_ldma_kernel<3, false, false, SILU_, 16, NB_>, lds2);                                        \
-        if (rc != 0) return rc;                                                                                           \
-        hipLaunchKernelGGL((wgrad_ldma_kernel<3, false, false, SILU_, 16, NB_>), grid, dim3(512), lds2, stream, *p);       \
-    } while (0)
-        const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
-        // operands stored as bf16 (layers running with NLAM_F_STORE_BF16): dW1 = dz1^T [fp32 sources] with A bf16, dW2 =
-        // dz2^T silu(z1) with A and the single un-gathered source bf16 (sb)
-        const bool sb = (p->flags & NLAM_F_S_BF16) != 0;
-        const int var = nlam_detail::wgrad_ldma_var;   // (rows per stage, ring depth) variants for A/B runs (NLAM_TUNE_WGRAD_LDMA_VAR)
-        switch (plan) {
-        case NLAM_WGP_LDMA_B:
-            if (sb) {
-                if (var == 1) NLAM_LAUNCH_WG_LDMA(true, true, true, 32, 5);
-                else if (var == 2) NLAM_LAUNCH_WG_LDMA(true, true, true, 16, 6);
-                else if (var == 3) NLAM_LAUNCH_WG_LDMA(true, true, true, 16, 8);
-                else NLAM_LAUNCH_WG_LDMA(true, true, true, 32, 4);
-            } else {
-                if (var == 1) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 4);
-                else if (var == 2) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 5);
-                else if (var == 3) NLAM_LAUNCH_WG_LDMA(true, false, false, 16, 6);
-                else NLAM_LAUNCH_WG_LDMA(true, false, false, 32, 3);
-            }
-            break;
-        case NLAM_WGP_WBF_B_BIG:
-            if (sb) NLAM_LAUNCH_WG_WBF_B(true, 4, 2, 4, true);
-            else NLAM_LAUNCH_WG_WBF_B(false, 4, 2, 4, false);
-            break;
-        case NLAM_WGP_WBF_B:
-            if (sb) NLAM_LAUNCH_WG_WBF_B(true, 2, 2, 2, true);
-            else NLAM_LAUNCH_WG_WBF_B(false, 2, 2, 2, false);
-            break;
-        case NLAM_WGP_LDMA_1:   // fp32 operands, one term (autocast launches without bf16 storage)
-            if (silu) {
-                if (var >= 1) NLAM_LAUNCH_WG_LDMA(false, false, true, 16, 5);
-                else NLAM_LAUNCH_WG_LDMA(false, false, true, 16, 4);
-            } else {
-                if (var == 1) NLAM_LAUNCH_WG_LDMA(false, false, false, 16, 4);
-                else if (var >= 2) NLAM_LAUNCH_WG_LDMA(false, false, false, 16, 5);
-                else NLAM_LAUNCH_WG_LDMA(false, false, false, 16, 3);
-            }
-            break;
-        case NLAM_WGP_LDMA_3:   // fp32 class: three terms on the LDS-DMA kernel
-            if (silu) NLAM_LAUNCH_WG_LDMA3(true, 4);
-            else NLAM_LAUNCH_WG_LDMA3(false, 4);
-            break;
-        default:   // NLAM_WGP_WBF / NLAM_WGP_WBF_BIG
-            if (wns == 1 && silu) NLAM_LAUNCH_WG_WBF2(1, true);
-            else if (wns == 1) NLAM_LAUNCH_WG_WBF2(1, false);
-            else if (silu) NLAM_LAUNCH_WG_WBF2(3, true);
-            else NLAM_LAUNCH_WG_WBF2(3, false);
+    const int wns = wgrad_wbf_ns(p);
+    // 256 x 256 windows (8 waves) when the output has more than 128 rows, 128 x 128 windows (4 waves) otherwise
+    const bool big = plan != NLAM_WGP_WBF && plan != NLAM_WGP_WBF_B;
+    const int winm = big ? 256 : 128, winn = big ? 256 : 128;
+    const size_t lds = (size_t)2 * ((winm + winn) / 32) * wns * 1024;
+    const dim3 grid(p->nparts, wgrad_windows_of(p, winm, winn));
+    const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
+    // operands stored as bf16 (layers running with NLAM_F_STORE_BF16): dW1 = dz1^T [fp32 sources] with A bf16, dW2 =
+    // dz2^T silu(z1) with A and the single un-gathered source bf16 (sb)
+    const bool sb = (p->flags & NLAM_F_S_BF16) != 0;
+    const int var = nlam_detail::wgrad_ldma_var;   // (rows per stage, ring depth) variants for A/B runs (NLAM_TUNE_WGRAD_LDMA_VAR)
+    switch (plan) {
+    case NLAM_WGP_LDMA_B:   // <NS, ABF, SBF, SILU, R, NB>
+        if (sb) {
+            if (var == 1) return launch_wgrad_ldma<1, true, true, true, 32, 5>(grid, stream, *p);
+            if (var == 2) return launch_wgrad_ldma<1, true, true, true, 16, 6>(grid, stream, *p);
+            if (var == 3) return launch_wgrad_ldma<1, true, true, true, 16, 8>(grid, stream, *p);
+            return launch_wgrad_ldma<1, true, true, true, 32, 4>(grid, stream, *p);
         }
-        return (int32_t)hipGetLastError();
+        if (var == 1) return launch_wgrad_ldma<1, true, false, false, 16, 4>(grid, stream, *p);
+        if (var == 2) return launch_wgrad_ldma<1, true, false, false, 16, 5>(grid, stream, *p);
+        if (var == 3) return launch_wgrad_ldma<1, true, false, false, 16, 6>(grid, stream, *p);
+        return launch_wgrad_ldma<1, true, false, false, 32, 3>(grid, stream, *p);
+    case NLAM_WGP_WBF_B_BIG:
+    case NLAM_WGP_WBF_B:
+        if (sb) return launch_wgrad_wbf<1, true, true, true>(big, grid, lds, stream, *p);
+        return launch_wgrad_wbf<1, false, true, false>(big, grid, lds, stream, *p);
+    case NLAM_WGP_LDMA_1:   // fp32 operands, one term (autocast launches without bf16 storage)
+        if (silu) {
+            if (var >= 1) return launch_wgrad_ldma<1, false, false, true, 16, 5>(grid, stream, *p);
+            return launch_wgrad_ldma<1, false, false, true, 16, 4>(grid, stream, *p);
+        }
+        if (var == 1) return launch_wgrad_ldma<1, false, false, false, 16, 4>(grid, stream, *p);
+        if (var >= 2) return launch_wgrad_ldma<1, false, false, false, 16, 5>(grid, stream, *p);
+        return launch_wgrad_ldma<1, false, false, false, 16, 3>(grid, stream, *p);
+    case NLAM_WGP_LDMA_3:   // fp32 class: three terms on the LDS-DMA kernel
+        if (silu) return launch_wgrad_ldma<3, false, false, true, 16, 4>(grid, stream, *p);
+        return launch_wgrad_ldma<3, false, false, false, 16, 4>(grid, stream, *p);
+    default:   // NLAM_WGP_WBF / NLAM_WGP_WBF_BIG
+        return pick_else<3, 1>(wns, [&](auto ns) {
+            return pick_bool(silu, [&](auto sl) { return launch_wgrad_wbf<ns, sl, false, false>(big, grid, lds, stream, *p); });
+        });
     }
+}
 #endif
 
 #if NLAM_IN_TU(4)
@@ -6349,48 +6185,30 @@ int32_t nlam_detail::wgrad_wbf_group(const nlam_wgrad_t* ps, int n, hipStream_t 
     const int winm = big ? 256 : 128, winn = big ? 256 : 128;
     const size_t lds = (size_t)2 * ((winm + winn) / 32) * wns * 1024;
     wgrad_group_t G;
-    G.n = n;
-    G.first[0] = 0;
+    int parts[NLAM_MAX_GROUP];
     for (int k = 0; k < n; ++k) {
         G.g[k] = ps[k];
-        G.first[k + 1] = G.first[k] + ps[k].nparts;
+        parts[k] = ps[k].nparts;
     }
-    for (int k = n + 1; k <= NLAM_MAX_GROUP; ++k) G.first[k] = G.first[n];
+    group_prefix(G, n, parts);
     const dim3 grid(G.first[n], wgrad_windows_of(p, winm, winn));
-#define NLAM_LAUNCH_WG_WBF_G(NS_, S_, WM_, WN_, NBW_)                                                                       \
-    do {                                                                                                                    \
-        int rc = set_lds(wgrad_wbf_group_kernel<NS_, S_, WM_, WN_, NBW_>, lds);                                             \
-        if (rc != 0) return rc;                                                                                             \
-        hipLaunchKernelGGL((wgrad_wbf_group_kernel<NS_, S_, WM_, WN_, NBW_>), grid, dim3(WM_ * WN_ * 64), lds, stream, G);  \
-    } while (0)
-#define NLAM_LAUNCH_WG_WBF_G2(NS_, S_)                   \
-    do {                                                 \
-        if (big) NLAM_LAUNCH_WG_WBF_G(NS_, S_, 4, 2, 4); \
-        else NLAM_LAUNCH_WG_WBF_G(NS_, S_, 2, 2, 2);     \
-    } while (0)
     const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
-    if (wns == 1 && silu) NLAM_LAUNCH_WG_WBF_G2(1, true);
-    else if (wns == 1) NLAM_LAUNCH_WG_WBF_G2(1, false);
-    else if (silu) NLAM_LAUNCH_WG_WBF_G2(3, true);
-    else NLAM_LAUNCH_WG_WBF_G2(3, false);
-    return (int32_t)hipGetLastError();
+    return pick_else<3, 1>(wns, [&](auto ns) {
+        return pick_bool(silu, [&](auto sl) -> int32_t {
+            if (big) return launch<wgrad_wbf_group_kernel<ns, sl, 4, 2, 4>>(grid, dim3(4 * 2 * 64), lds, stream, G);
+            return launch<wgrad_wbf_group_kernel<ns, sl, 2, 2, 2>>(grid, dim3(2 * 2 * 64), lds, stream, G);
+        });
+    });
 }
 #endif
 
 #if NLAM_IN_TU(3)
 int32_t nlam_detail::wgrad_wide(const nlam_wgrad_t* p, hipStream_t stream) {
-        const size_t lds = (size_t)4 * kWWTile * sizeof(float);
-        if (p->flags & NLAM_F_SILU_B) {
-            int rc = set_lds(wgrad_wide_kernel<true>, lds);
-            if (rc != 0) return rc;
-            hipLaunchKernelGGL(wgrad_wide_kernel<true>, dim3(p->nparts, wgrad_windows(p)), dim3(kWgradThreads), lds, stream, *p);
-        } else {
-            int rc = set_lds(wgrad_wide_kernel<false>, lds);
-            if (rc != 0) return rc;
-            hipLaunchKernelGGL(wgrad_wide_kernel<false>, dim3(p->nparts, wgrad_windows(p)), dim3(kWgradThreads), lds, stream, *p);
-        }
-        return (int32_t)hipGetLastError();
-    }
+    const size_t lds = (size_t)4 * kWWTile * sizeof(float);
+    return pick_bool((p->flags & NLAM_F_SILU_B) != 0, [&](auto silu) {
+        return launch<wgrad_wide_kernel<silu>>(dim3(p->nparts, wgrad_windows(p)), dim3(kWgradThreads), lds, stream, *p);
+    });
+}
 #endif
 
 #if NLAM_IN_TU(2)
@@ -6405,39 +6223,21 @@ int32_t nlam_detail::wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t s
         const int nblocks = ((p->m + 31) / 32) * nb_total;
         const int nbw = (nblocks + 3) / 4;
         const size_t lds = (size_t)2 * (1 + p->nsrc) * kWgTile * sizeof(float);
-#define NLAM_LAUNCH_WGD1(N_, S_)                                                                              \
-    do {                                                                                                      \
-        int rc = set_lds(wgrad_dma_kernel<N_, S_>, lds);                                                      \
-        if (rc != 0) return rc;                                                                               \
-        hipLaunchKernelGGL((wgrad_dma_kernel<N_, S_>), dim3(p->nparts), dim3(kWgradThreads), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_WGD(N_)                                        \
-    do {                                                           \
-        if (p->flags & NLAM_F_SILU_B) NLAM_LAUNCH_WGD1(N_, true);  \
-        else NLAM_LAUNCH_WGD1(N_, false);                          \
-    } while (0)
-        if (nbw <= 1) NLAM_LAUNCH_WGD(1);
-        else if (nbw <= 2) NLAM_LAUNCH_WGD(2);
-        else if (nbw <= 3) NLAM_LAUNCH_WGD(3);
-        else return NLAM_EUNSUP;
-        return (int32_t)hipGetLastError();
+        return pick<1, 2, 3>(nbw < 1 ? 1 : nbw, [&](auto nb) {
+            return pick_bool((p->flags & NLAM_F_SILU_B) != 0, [&](auto silu) {
+                return launch<wgrad_dma_kernel<nb, silu>>(dim3(p->nparts), dim3(kWgradThreads), lds, stream, *p);
+            });
+        });
     }
     const int MP = (p->m + 31) / 32 * 32, NP = (p->n + 31) / 32 * 32;
     const int nblocks = (MP / 32) * (NP / 32);
     const size_t lds = (size_t)kWgradRows * (MP + 4 + NP + 4) * sizeof(float);
     const int nbw = (nblocks + 3) / 4;
     const int ywin = (nblocks + 11) / 12;   // blockIdx.y windows of 12 blocks when one workgroup cannot hold them all
-#define NLAM_LAUNCH_WG(N_, Y_)                                                                                \
-    do {                                                                                                      \
-        int rc = set_lds(wgrad_kernel<N_>, lds);                                                              \
-        if (rc != 0) return rc;                                                                               \
-        hipLaunchKernelGGL((wgrad_kernel<N_>), dim3(p->nparts, Y_), dim3(kWgradThreads), lds, stream, *p);    \
-    } while (0)
-    if (nbw <= 1) NLAM_LAUNCH_WG(1, 1);
-    else if (nbw <= 2) NLAM_LAUNCH_WG(2, 1);
-    else if (nbw <= 3) NLAM_LAUNCH_WG(3, 1);
-    else NLAM_LAUNCH_WG(3, ywin);
-    return (int32_t)hipGetLastError();
+    const dim3 grid(p->nparts, nbw > 3 ? ywin : 1);
+    return pick<1, 2, 3>(nbw < 1 ? 1 : (nbw > 3 ? 3 : nbw), [&](auto nb) {
+        return launch<wgrad_kernel<nb>>(grid, dim3(kWgradThreads), lds, stream, *p);
+    });
 }
 #endif
 
@@ -6525,7 +6325,7 @@ int32_t nlam_pre_add_supported(const nlam_mlp_fwd_t* p) {
     if (ns == 0 || p->hid % 32 != 0 || p->dout % 32 != 0 || p->src[0].width % 32 != 0) return 0;
     for (int s = 1; s < p->nsrc; ++s)
         if (p->src[s].width != p->hid) return 0;
-    if (!fwd_is_wide(p)) return p->hid == p->dout && (p->src[0].width == 32 || p->src[0].width == 64) ? 1 : 0;
+    if (!mlp_is_wide(p)) return p->hid == p->dout && (p->src[0].width == 32 || p->src[0].width == 64) ? 1 : 0;
     if (fwd_wbf_ns(p) == 0) return 0;
     nlam_mlp_bwd_t q = {};
     q.nsrc = p->nsrc;
@@ -6539,9 +6339,12 @@ int32_t nlam_pre_add_supported(const nlam_mlp_fwd_t* p) {
     return (k % 64 == 0 && p->hid % 64 == 0) ? 1 : 0;
 }
 
+}  // extern "C"
+
+namespace {
 // operand layout the LDS-tiled GEMM can read: 1 = along K (ldk == 1, 16-byte aligned rows: the forward product), 2 = transposed
 // (ldn == 1: the data-gradient product), 0 = neither (the strip kernel reads any strides)
-static int lin_gemm_layout(const nlam_linear_t* p) {
+int lin_gemm_layout(const nlam_linear_t* p) {
     auto ok = [&](const float* W) {
         if (p->ldk == 1) return (p->ldn % 4 == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0) ? 1 : 0;
         return p->ldn == 1 ? 2 : 0;
@@ -6550,6 +6353,17 @@ static int lin_gemm_layout(const nlam_linear_t* p) {
     if (p->W2 != nullptr && ok(p->W2) != a) return 0;
     return a;
 }
+
+// linear_gemm_kernel<NS, WN, TA, SK>: TA = the transposed layout
+template <int NS, int WN, int SK>
+int32_t launch_lin_gemm(bool ta, dim3 grid, hipStream_t stream, const nlam_linear_t& p) {
+    return pick_bool(ta, [&](auto tac) {
+        return launch<linear_gemm_kernel<NS, WN, tac, SK>>(grid, dim3(kLinGemmThreads), lin_gemm_lds_bytes<NS, WN, SK>(), stream, p);
+    });
+}
+}  // namespace
+
+extern "C" {
 
 int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_linear");
@@ -6565,29 +6379,20 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
     const int blocks = (int)(ntiles < kMaxGridBlocks ? ntiles : kMaxGridBlocks);
     const size_t lds = (size_t)ns * MB * 2 * KB * 64 * 16 + (size_t)kFwdWaves * 32 * kStgStride * sizeof(float);
     hipStream_t stream = (hipStream_t)hip_stream;
-#define NLAM_LAUNCH_LIN1(KB_, MB_, NS_)                                                                          \
-    do {                                                                                                        \
-        int rc = set_lds(linear_bf_kernel<KB_, MB_, NS_>, lds);                                                 \
-        if (rc != 0) return rc;                                                                                 \
-        hipLaunchKernelGGL((linear_bf_kernel<KB_, MB_, NS_>), dim3(blocks), dim3(kFwdThreads), lds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_LIN(KB_, MB_)                         \
-    do {                                                  \
-        if (ns == 3) NLAM_LAUNCH_LIN1(KB_, MB_, 3);       \
-        else if (ns == 2) NLAM_LAUNCH_LIN1(KB_, MB_, 2);  \
-        else NLAM_LAUNCH_LIN1(KB_, MB_, 1);               \
-    } while (0)
-    if (KB == 1 && MB == 1) NLAM_LAUNCH_LIN(1, 1);
-    else if (KB == 2 && MB == 1) NLAM_LAUNCH_LIN(2, 1);
-    else if (KB == 1 && MB == 2) NLAM_LAUNCH_LIN(1, 2);
-    else if (KB == 2 && MB == 2) NLAM_LAUNCH_LIN(2, 2);
-    else if (nlam_detail::lin_gemm != 0 && p->n % 128 == 0 && p->k <= kMaxWide && p->n <= kMaxWide && lin_gemm_layout(p) != 0 &&
-             // where it wins (profiles/round5/linear_bench.log, isolated launches): one term everywhere (1.3-2.1x); two / three terms
-             // -- 114 KB of LDS, one workgroup per CU -- on the mesh-level products up to K = 256 (1.4-1.5x) and on the grid-level
-             // ones from K = 512 (1.1x); the strip kernel keeps three-term 63 784 x 256 (0.9x) and 6 561 x 512 (0.9x).
-             // nlam_set_tuning(NLAM_TUNE_LIN_GEMM, 2) forces it everywhere it applies (tests).
-             (ns == 1 || nlam_detail::lin_gemm == 2 ||
-              (p->rows >= nlam_detail::lin_gemm_big_rows ? p->k >= 512 : p->k <= 256))) {
+    if (KB <= 2 && MB <= 2)
+        return pick<1, 2>(KB, [&](auto kb) {
+            return pick<1, 2>(MB, [&](auto mb) {
+                return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+                    return launch<linear_bf_kernel<kb, mb, nsc>>(dim3(blocks), dim3(kFwdThreads), lds, stream, *p);
+                });
+            });
+        });
+    if (nlam_detail::lin_gemm != 0 && p->n % 128 == 0 && p->k <= kMaxWide && p->n <= kMaxWide && lin_gemm_layout(p) != 0 &&
+        // where it wins (profiles/round5/linear_bench.log, isolated launches): one term everywhere (1.3-2.1x); two / three terms
+        // -- 114 KB of LDS, one workgroup per CU -- on the mesh-level products up to K = 256 (1.4-1.5x) and on the grid-level
+        // ones from K = 512 (1.1x); the strip kernel keeps three-term 63 784 x 256 (0.9x) and 6 561 x 512 (0.9x).
+        // nlam_set_tuning(NLAM_TUNE_LIN_GEMM, 2) forces it everywhere it applies (tests).
+        (ns == 1 || nlam_detail::lin_gemm == 2 || (p->rows >= nlam_detail::lin_gemm_big_rows ? p->k >= 512 : p->k <= 256))) {
         // LDS-tiled GEMM (linear_gemm_kernel): 128 x 128 tiles from 32 768 rows, 64-row tiles below
         const bool ta = lin_gemm_layout(p) == 2;
         const bool big = p->rows >= nlam_detail::lin_gemm_big_rows;
@@ -6596,31 +6401,14 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
         const long nftt = (long)(p->n / 128) * (p->W2 != nullptr ? 2 : 1);
         const long nwg = (nrt + 7) / 8 * 8 * nftt;
         if (nwg > 0x7fffffffL) return NLAM_EUNSUP;
-#define NLAM_LAUNCH_LING1(NS_, WN_, TA_, SK_)                                                                        \
-    do {                                                                                                             \
-        const size_t glds = lin_gemm_lds_bytes<NS_, WN_, SK_>();                                                     \
-        int rc = set_lds(linear_gemm_kernel<NS_, WN_, TA_, SK_>, glds);                                              \
-        if (rc != 0) return rc;                                                                                      \
-        hipLaunchKernelGGL((linear_gemm_kernel<NS_, WN_, TA_, SK_>), dim3((unsigned)nwg), dim3(kLinGemmThreads), glds, stream, *p); \
-    } while (0)
-#define NLAM_LAUNCH_LING(NS_, WN_)                       \
-    do {                                                 \
-        if (ta) NLAM_LAUNCH_LING1(NS_, WN_, true, 2);    \
-        else NLAM_LAUNCH_LING1(NS_, WN_, false, 2);      \
-    } while (0)
-        if (big) {
-            if (ns == 3) NLAM_LAUNCH_LING(3, 2);
-            else if (ns == 2) NLAM_LAUNCH_LING(2, 2);
-            else NLAM_LAUNCH_LING(1, 2);
-        } else {
-            if (ns == 3) NLAM_LAUNCH_LING(3, 1);
-            else if (ns == 2) NLAM_LAUNCH_LING(2, 1);
-            else if (p->k % 64 == 0 && NLAM_LIN_SK == 4) {   // one term, 64-row tiles: 64-column chunks (66 KB of LDS, two workgroups per CU)
-                if (ta) NLAM_LAUNCH_LING1(1, 1, true, 4);
-                else NLAM_LAUNCH_LING1(1, 1, false, 4);
-            } else NLAM_LAUNCH_LING(1, 1);
-        }
-    } else if (p->k % 64 == 0 && p->n % 64 == 0 && p->k <= kMaxWide && p->n <= kMaxWide) {
+        const dim3 grid((unsigned)nwg);
+        if (big) return pick_else<1, 3, 2>(ns, [&](auto nsc) { return launch_lin_gemm<nsc, 2, 2>(ta, grid, stream, *p); });
+        if (ns == 3 || ns == 2) return pick<3, 2>(ns, [&](auto nsc) { return launch_lin_gemm<nsc, 1, 2>(ta, grid, stream, *p); });
+        // one term, 64-row tiles: 64-column chunks (66 KB of LDS, two workgroups per CU)
+        if (p->k % 64 == 0 && NLAM_LIN_SK == 4) return launch_lin_gemm<1, 1, 4>(ta, grid, stream, *p);
+        return launch_lin_gemm<1, 1, 2>(ta, grid, stream, *p);
+    }
+    if (p->k % 64 == 0 && p->n % 64 == 0 && p->k <= kMaxWide && p->n <= kMaxWide) {
         // 64 x 64 weight blocks streamed through two LDS buffers (linear_bfw_kernel)
         const int kc_all = p->k / 64;
         const bool resident = kc_all <= kLinResidentChunks && nlam_detail::lin_resident_wgs > 0;   // the output pair's whole weight strip stays in LDS
@@ -6633,17 +6421,11 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
         const long cap = resident ? nlam_detail::lin_resident_wgs : 4 * kNumCUs;
         if (wbx * wby > cap) wbx = (cap + wby - 1) / wby;
         if (wbx < 1) wbx = 1;
-#define NLAM_LAUNCH_LINW(NS_)                                                                              \
-    do {                                                                                                   \
-        int rc = set_lds(linear_bfw_kernel<NS_>, wlds);                                                    \
-        if (rc != 0) return rc;                                                                            \
-        hipLaunchKernelGGL((linear_bfw_kernel<NS_>), dim3(wbx, wby), dim3(kFwdThreads), wlds, stream, q);  \
-    } while (0)
-        if (ns == 3) NLAM_LAUNCH_LINW(3);
-        else if (ns == 2) NLAM_LAUNCH_LINW(2);
-        else NLAM_LAUNCH_LINW(1);
-    } else return NLAM_EUNSUP;
-    return (int32_t)hipGetLastError();
+        return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+            return launch<linear_bfw_kernel<nsc>>(dim3(wbx, wby), dim3(kFwdThreads), wlds, stream, q);
+        });
+    }
+    return NLAM_EUNSUP;
 }
 
 }  // extern "C"
@@ -6675,16 +6457,15 @@ int32_t loss_launch(const nlam_loss_t& p, bool bwd, hipStream_t stream) {
     return (int32_t)hipGetLastError();
 }
 
+// the NLAM_LOSS_* kind as the template argument of f
+template <typename F>
+int32_t pick_loss(int32_t kind, F&& f) {
+    if (!loss_kind_valid(kind)) return NLAM_EINVAL;
+    return pick<NLAM_LOSS_MSE, NLAM_LOSS_MAE, NLAM_LOSS_WMSE, NLAM_LOSS_WMAE, NLAM_LOSS_NLL, NLAM_LOSS_CRPS_GAUSS>(kind, f);
+}
+
 int32_t loss_dispatch(const nlam_loss_t& p, bool bwd, hipStream_t stream) {
-    switch (p.kind) {
-        case NLAM_LOSS_MSE: return loss_launch<NLAM_LOSS_MSE>(p, bwd, stream);
-        case NLAM_LOSS_MAE: return loss_launch<NLAM_LOSS_MAE>(p, bwd, stream);
-        case NLAM_LOSS_WMSE: return loss_launch<NLAM_LOSS_WMSE>(p, bwd, stream);
-        case NLAM_LOSS_WMAE: return loss_launch<NLAM_LOSS_WMAE>(p, bwd, stream);
-        case NLAM_LOSS_NLL: return loss_launch<NLAM_LOSS_NLL>(p, bwd, stream);
-        case NLAM_LOSS_CRPS_GAUSS: return loss_launch<NLAM_LOSS_CRPS_GAUSS>(p, bwd, stream);
-        default: return NLAM_EINVAL;
-    }
+    return pick_loss(p.kind, [&](auto kind) { return loss_launch<kind>(p, bwd, stream); });
 }
 
 // the checks both directions share: kind, pointers, sizes; NLAM_EUNSUP for a per-variable std wider than the LDS table
@@ -7057,17 +6838,6 @@ int32_t nlam_loss_bwd(const nlam_loss_t* p, void* hip_stream) {
     return loss_dispatch(*p, true, (hipStream_t)hip_stream);
 }
 
-#define NLAM_LOSS_SWITCH(kind, CALL)                                 \
-    switch (kind) {                                                  \
-        case NLAM_LOSS_MSE: CALL(NLAM_LOSS_MSE); break;               \
-        case NLAM_LOSS_MAE: CALL(NLAM_LOSS_MAE); break;               \
-        case NLAM_LOSS_WMSE: CALL(NLAM_LOSS_WMSE); break;             \
-        case NLAM_LOSS_WMAE: CALL(NLAM_LOSS_WMAE); break;             \
-        case NLAM_LOSS_NLL: CALL(NLAM_LOSS_NLL); break;               \
-        case NLAM_LOSS_CRPS_GAUSS: CALL(NLAM_LOSS_CRPS_GAUSS); break; \
-        default: return NLAM_EINVAL;                                 \
-    }
-
 int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* prev, const float* truth, const float* target,
                                 const float* dstd, const float* dmean, const float* bmask, const float* var_std,
                                 const float* row_weight, float scale, float* pred, float* partials, int32_t nparts, int64_t rows,
@@ -7078,12 +6848,11 @@ int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* p
         return NLAM_EINVAL;
     if (rows < 1 || nodes < 1 || width < 1 || nparts < 1 || rows % nodes != 0) return NLAM_EINVAL;
     if (width > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
-#define NLAM_STL_FWD(K)                                                                                                     \
-    step_tail_loss_fwd_launch<K>(delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, \
-                                 nparts, (long)rows * width, nodes, width, (hipStream_t)hip_stream)
-    NLAM_LOSS_SWITCH(kind, NLAM_STL_FWD)
-#undef NLAM_STL_FWD
-    return (int32_t)hipGetLastError();
+    return pick_loss(kind, [&](auto k) {
+        step_tail_loss_fwd_launch<k>(delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, nparts,
+                                     (long)rows * width, nodes, width, (hipStream_t)hip_stream);
+        return (int32_t)hipGetLastError();
+    });
 }
 
 int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target,
@@ -7095,29 +6864,24 @@ int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* 
         return NLAM_EINVAL;
     if ((d_delta == nullptr && d_prev == nullptr) || rows < 1 || nodes < 1 || width < 1 || rows % nodes != 0) return NLAM_EINVAL;
     if (width > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
-#define NLAM_STL_BWD(K)                                                                                                    \
-    step_tail_loss_bwd_launch<K>(g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, \
-                                 (long)rows * width, nodes, width, (hipStream_t)hip_stream)
-    NLAM_LOSS_SWITCH(kind, NLAM_STL_BWD)
-#undef NLAM_STL_BWD
-    return (int32_t)hipGetLastError();
+    return pick_loss(kind, [&](auto k) {
+        step_tail_loss_bwd_launch<k>(g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev,
+                                     (long)rows * width, nodes, width, (hipStream_t)hip_stream);
+        return (int32_t)hipGetLastError();
+    });
 }
 
 int32_t nlam_eval_metrics(const nlam_eval_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_eval_metrics");
     if (const int32_t rc = eval_check(p)) return rc;
     const hipStream_t stream = (hipStream_t)hip_stream;
-#define NLAM_EVAL(K) return eval_launch<K>(*p, stream)
-    NLAM_LOSS_SWITCH(p->kind, NLAM_EVAL)
-#undef NLAM_EVAL
-    return NLAM_EINVAL;
+    return pick_loss(p->kind, [&](auto kind) { return eval_launch<kind>(*p, stream); });
 }
 
 int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, int32_t nvars) {
     if (batch < 1 || steps < 1 || nodes < 1 || nvars < 1 || nvars > NLAM_EVAL_MAX_VARS) return NLAM_EINVAL;
     return (int64_t)batch * steps * eval_nchunks(nodes, nvars) * (3L * nvars + 1);
 }
-#undef NLAM_LOSS_SWITCH
 
 }  // extern "C"
 #endif

@@ -1318,10 +1318,11 @@ int fwd_wbf_ns(const nlam_mlp_fwd_t* p) {
 // 32-column blocks of hid and dout, and shapes whose backward and weight gradients take the one-term split-bf16 kernels too --
 // the same tiles / batch put the backward above its own (lower) super-tile threshold, widths above 64 and multiples of 4 make
 // both weight gradients wide, and a source of <= kSmallN columns (the streaming weight-gradient kernel) is excluded.
-bool fwd_is_wide(const nlam_mlp_fwd_t* p);   // nlam_hip.hip
+template <typename P>
+bool mlp_is_wide(const P* p);   // nlam_hip.hip
 
 bool store_bf16_ok(const nlam_mlp_fwd_t* p) {
-    if (p->ncat != 0 || !fwd_is_wide(p) || fwd_wbf_ns(p) != 1) return false;
+    if (p->ncat != 0 || !mlp_is_wide(p) || fwd_wbf_ns(p) != 1) return false;
     if (p->hid % 32 != 0 || p->dout % 32 != 0 || p->hid <= 64 || p->dout <= 64) return false;
     if (((p->dout + 31) / 32) & 1) return false;   // the backward's W2^T phase is padded for odd counts, but keep to tested shapes
     if (p->flags & NLAM_F_NO_ACT) return false;
