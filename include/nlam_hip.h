@@ -59,6 +59,9 @@
  *       the global gradient norm, and the AdamW update with clipping by that norm, a closed-form learning-rate schedule
  *       and the skip of a non-finite step decided on the device (what Lightning's gradient_clip_val and LR scheduler
  *       give the reference's loop), in launches whose arguments do not depend on the step.
+ *   nlam_accum_begin, nlam_adamw_step_accum
+ *       Lightning's accumulate_grad_batches: the zero of the gradient and the controlled update gated on the device by the
+ *       index of the micro-batch, so that one recorded step serves every micro-step of a window.
  */
 #ifndef NLAM_HIP_H
 #define NLAM_HIP_H
@@ -866,6 +869,34 @@ typedef struct {
     int32_t skip_nonfinite;
 } nlam_optctl_t;
 int32_t nlam_adamw_step_controlled(const nlam_optctl_t* p, void* hip_stream);
+
+/* Gradient accumulation over K micro-batches with ONE recorded step: the head and the tail of the step decide on the device
+ * whether a call opens or closes a window, so no launch argument depends on the micro-step.
+ * accum: NLAM_ACCUM_WORDS 4-byte words, zero before the first step:
+ *   [0] int32 index of the next micro-batch in the window (0 .. K-1)   [1] int32 hold flag (1: the last call only accumulated)
+ *   [2] float running loss sum of the open window                      [3] float mean loss of the last completed window
+ * nlam_accum_begin: the zero of the flat gradient in front of forward + backward, in place of a memset: `grad[0 .. n)` is
+ *   zeroed when accum[0] == 0 and left alone otherwise.  Any 4-byte aligned `grad`, any n >= 0 (16-byte stores on the aligned
+ *   interior, single elements in front of and behind it).
+ * nlam_adamw_step_accum: the three launches of nlam_adamw_step_controlled, each gated:
+ *   1. the sum of squares runs only when accum[0] == steps - 1 (the micro-batch that completes the window);
+ *   2. one wave adds loss[0] (0 for a null `loss`) to the running sum -- restarted at accum[0] == 0, fp32, in call order --
+ *      and, the window not being complete, advances accum[0], raises the hold flag and stops: the control block keeps the
+ *      values of the last completed window.  Otherwise accum[0] = 0, the hold flag is cleared, accum[3] = sum / (float)steps
+ *      and the decisions of nlam_adamw_step_controlled follow, from the same code (grad_scale should hold the 1 / steps of
+ *      the mean).  A window whose norm is not finite is skipped as there and is closed all the same, so the next
+ *      nlam_accum_begin clears the gradient;
+ *   3. the update touches nothing while the hold flag or the skip flag is up.
+ * steps == 1 gives the bits of nlam_adamw_step_controlled.  NLAM_EINVAL: null or misaligned accum, steps < 1, and whatever
+ * nlam_adamw_step_controlled rejects. */
+#define NLAM_ACCUM_WORDS 4
+typedef struct {
+    int32_t* accum;                  /* NLAM_ACCUM_WORDS words on the device */
+    const float* loss;               /* this micro-batch's loss on the device, or null */
+    int32_t steps;                   /* K >= 1 */
+} nlam_accum_t;
+int32_t nlam_accum_begin(float* grad, int64_t n, const int32_t* accum, void* hip_stream);
+int32_t nlam_adamw_step_accum(const nlam_optctl_t* p, const nlam_accum_t* a, void* hip_stream);
 
 #ifdef __cplusplus
 }

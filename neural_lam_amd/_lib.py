@@ -50,6 +50,9 @@ SCHED_KINDS = {"constant": 1, "warmup_cosine": 2, "warmup_linear": 3}
 SCHED_NONE = 0
 OPTCTL_WORDS = 8
 OPTCTL_LR, OPTCTL_COEF, OPTCTL_NORM, OPTCTL_SKIP, OPTCTL_SKIPPED = range(5)
+# the words of nlam_accum_t.accum (gradient accumulation: nlam_accum_begin, nlam_adamw_step_accum)
+ACCUM_WORDS = 4
+ACCUM_INDEX, ACCUM_HOLD, ACCUM_LOSS_SUM, ACCUM_WINDOW_LOSS = range(4)
 
 EXPORTS = [
     "nlam_abi_version",
@@ -117,6 +120,8 @@ EXPORTS = [
     "nlam_grad_sumsq_workspace_doubles",
     "nlam_grad_sumsq",
     "nlam_adamw_step_controlled",
+    "nlam_accum_begin",
+    "nlam_adamw_step_accum",
 ]
 
 
@@ -471,6 +476,11 @@ class OptCtl(C.Structure):
     ]
 
 
+class Accum(C.Structure):
+    """nlam_accum_t: the device block that gates the step's head and tail, this micro-batch's loss, the window length K."""
+    _fields_ = [("accum", C.c_void_p), ("loss", C.c_void_p), ("steps", C.c_int32)]
+
+
 class PackRec(C.Structure):
     _fields_ = [("bytes", C.c_ubyte * 64)]
 
@@ -607,6 +617,10 @@ def load():
     lib.nlam_grad_sumsq.restype = i32
     lib.nlam_adamw_step_controlled.argtypes = [C.POINTER(OptCtl), vp]
     lib.nlam_adamw_step_controlled.restype = i32
+    lib.nlam_accum_begin.argtypes = [vp, i64, vp, vp]
+    lib.nlam_accum_begin.restype = i32
+    lib.nlam_adamw_step_accum.argtypes = [C.POINTER(OptCtl), C.POINTER(Accum), vp]
+    lib.nlam_adamw_step_accum.restype = i32
     lib.nlam_mlp_group_blocks.argtypes = [C.POINTER(C.c_int64), i32, C.POINTER(C.c_int32)]
     lib.nlam_mlp_group_blocks.restype = i32
     lib.nlam_mlp_fwd_group.argtypes = [C.POINTER(MlpFwd), i32, vp]

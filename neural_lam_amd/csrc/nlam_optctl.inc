@@ -11,6 +11,14 @@
 //                         NLAM_OPTCTL_WORDS words that the host may read later.
 //   adamw_ctl_kernel      adamw_kernel's arithmetic with lr and the clip coefficient read from that block; returns before
 //                         touching anything when the skip flag is up.
+// Gradient accumulation over K micro-batches (nlam_accum_begin, nlam_adamw_step_accum): the same launches, each gated by a
+// block of NLAM_ACCUM_WORDS words on the device, so one recorded step serves every micro-step of a window.
+//   accum_begin_kernel          the zero of the flat gradient in front of the step: only when word 0 (the index of the
+//                               micro-batch) is 0; 16-byte stores on the aligned interior, single elements around it.
+//   grad_sumsq_accum_kernel     grad_sumsq_kernel's body; every workgroup returns unless word 0 is K - 1.
+//   adamw_control_accum_kernel  adds the micro-batch loss to the window's sum and either holds (advance word 0, raise the
+//                               hold flag) or closes the window and decides as adamw_control_kernel does (one shared body).
+//   adamw_ctl_accum_kernel      adamw_ctl_kernel's body behind the hold flag and the skip flag.
 // Included from nlam_hip.hip inside NLAM_IN_TU(5).
 
 namespace {
@@ -31,7 +39,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(kSumsqThreads) void grad_sumsq_kernel(const float* g, long n, double* partials) {
+__device__ __forceinline__ void grad_sumsq_body(const float* g, long n, double* partials) {
     __shared__ double red[kSumsqThreads / 64];
     const int tid = threadIdx.x;
     // elements in front of the first 16-byte boundary and behind the last whole quad: lanes 0-2 / 3-5 of workgroup 0
@@ -84,6 +92,17 @@ __global__ __launch_bounds__(kSumsqThreads) void grad_sumsq_kernel(const float* 
     }
 }
 
+__global__ __launch_bounds__(kSumsqThreads) void grad_sumsq_kernel(const float* g, long n, double* partials) {
+    grad_sumsq_body(g, n, partials);
+}
+
+// the norm is wanted on the micro-step that closes a window only (accum[0] is uniform: the whole grid takes one side)
+__global__ __launch_bounds__(kSumsqThreads) void grad_sumsq_accum_kernel(const float* g, long n, double* partials, const int32_t* accum,
+                                                                         int last) {
+    if (accum[0] != last) return;
+    grad_sumsq_body(g, n, partials);
+}
+
 // the partials in a fixed order, by one wave: lane l adds l, l + 64, ... in order, then the butterfly
 __device__ __forceinline__ double partials_sum(const double* partials, int nparts) {
     double s = 0.0;
@@ -118,9 +137,8 @@ struct OptCtlArgs {
     int kind, warmup, total, skip_nonfinite;
 };
 
-__global__ __launch_bounds__(64) void adamw_control_kernel(const OptCtlArgs a) {
-    const double sum = partials_sum(a.partials, a.nparts);
-    if (threadIdx.x != 0) return;
+// lane 0 of the control wave, with the sum of the partials: everything the update launch reads
+__device__ __forceinline__ void optctl_decide(const OptCtlArgs a, double sum) {
     const float norm = (float)((double)a.grad_scale * sqrt(sum));
     const bool finite = fabsf(norm) <= 3.402823466e+38f;   // false for inf and nan
     a.ctl_f[2] = norm;
@@ -147,6 +165,36 @@ __global__ __launch_bounds__(64) void adamw_control_kernel(const OptCtlArgs a) {
     a.ctl_i[3] = 0;
 }
 
+__global__ __launch_bounds__(64) void adamw_control_kernel(const OptCtlArgs a) {
+    const double sum = partials_sum(a.partials, a.nparts);
+    if (threadIdx.x != 0) return;
+    optctl_decide(a, sum);
+}
+
+// acc: the NLAM_ACCUM_WORDS block ([0] micro-batch index, [1] hold flag, [2] running loss sum, [3] mean loss of the last
+// closed window).  The loss is added in fp32 in call order, from 0 at the first micro-batch of a window.  A window that is
+// not complete holds: word 0 advances, the flag goes up, the control block keeps the last closed window's values.  The last
+// micro-batch closes the window -- also when the decision below is to skip, so that the next gated zero clears the gradient.
+__global__ __launch_bounds__(64) void adamw_control_accum_kernel(const OptCtlArgs a, int32_t* acc, const float* loss, int steps) {
+    const int k = acc[0];
+    const bool closing = k == steps - 1;
+    double sum = 0.0;
+    if (closing) sum = partials_sum(a.partials, a.nparts);   // (the partials are stale on a holding micro-step)
+    if (threadIdx.x != 0) return;
+    float* acc_f = reinterpret_cast<float*>(acc);
+    const float run = (k == 0 ? 0.f : acc_f[2]) + (loss != nullptr ? loss[0] : 0.f);
+    acc_f[2] = run;
+    if (!closing) {
+        acc[0] = k + 1;
+        acc[1] = 1;
+        return;
+    }
+    acc[0] = 0;
+    acc[1] = 0;
+    acc_f[3] = run / (float)steps;
+    optctl_decide(a, sum);
+}
+
 // One element of adamw_kernel with the roundings of the code the compiler makes of it: it fuses 1 - lr * wd into one fma (hoisted
 // here as `decay`) and nothing else, so every other product and sum is rounded on its own.  Contraction is switched off and the
 // one fma written out, because what the compiler fuses is its choice per kernel (it fused more in this one's unrolled quads):
@@ -165,10 +213,10 @@ __device__ __forceinline__ void adamw_ctl_one(float& pv, float gr, float& mo, fl
 }
 
 // nq quads from 16-byte aligned bases, then the n - 4 nq elements behind them
-__global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const float* grad, float* m, float* v, long n, long nq, float b1,
-                                                        float b2, float eps, float wd, float gscale, const float* bias_corr,
-                                                        const float* ctl_f, const int32_t* ctl_i) {
-    if (ctl_i[3] != 0) return;   // a non-finite step: parameters and moments stay as they are
+// (first / stride: the caller's (long)blockIdx.x * blockDim.x + threadIdx.x and (long)gridDim.x * blockDim.x)
+__device__ __forceinline__ void adamw_ctl_body(float* param, const float* grad, float* m, float* v, long n, long nq, float b1, float b2,
+                                               float eps, float wd, float gscale, const float* bias_corr, const float* ctl_f,
+                                               long first, long stride) {
     const float lr = ctl_f[0], coef = ctl_f[1];
     const float bc1 = bias_corr[0], bc2_sqrt = bias_corr[1];
     const float decay = fmaf(-lr, wd, 1.f), step = lr / bc1;   // torch.optim.AdamW: decoupled decay first
@@ -176,8 +224,7 @@ __global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const floa
     const f32x4* g4 = reinterpret_cast<const f32x4*>(grad);
     f32x4* m4 = reinterpret_cast<f32x4*>(m);
     f32x4* v4 = reinterpret_cast<f32x4*>(v);
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += stride) {
+    for (long i = first; i < nq; i += stride) {
         f32x4 pv = p4[i], mo = m4[i], vo = v4[i];
         const f32x4 gr = g4[i];
 #pragma unroll
@@ -192,7 +239,7 @@ __global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const floa
         v4[i] = vo;
         p4[i] = pv;
     }
-    for (long idx = 4 * nq + (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
+    for (long idx = 4 * nq + first; idx < n; idx += stride) {
         float pk = param[idx], mk = m[idx], vk = v[idx];
         adamw_ctl_one(pk, grad[idx], mk, vk, decay, step, b1, b2, eps, bc2_sqrt, gscale, coef);
         m[idx] = mk;
@@ -201,13 +248,111 @@ __global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const floa
     }
 }
 
-int32_t sumsq_launch(const float* grad, int64_t n, double* partials, int64_t workspace_doubles, hipStream_t stream, int* nparts) {
+__global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const float* grad, float* m, float* v, long n, long nq, float b1,
+                                                        float b2, float eps, float wd, float gscale, const float* bias_corr,
+                                                        const float* ctl_f, const int32_t* ctl_i) {
+    if (ctl_i[3] != 0) return;   // a non-finite step: parameters and moments stay as they are
+    adamw_ctl_body(param, grad, m, v, n, nq, b1, b2, eps, wd, gscale, bias_corr, ctl_f,
+                   (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+// ... and while a window is open (hold flag acc[1]) nothing is touched either
+__global__ __launch_bounds__(256) void adamw_ctl_accum_kernel(float* param, const float* grad, float* m, float* v, long n, long nq,
+                                                              float b1, float b2, float eps, float wd, float gscale,
+                                                              const float* bias_corr, const float* ctl_f, const int32_t* ctl_i,
+                                                              const int32_t* acc) {
+    if (acc[1] != 0 || ctl_i[3] != 0) return;
+    adamw_ctl_body(param, grad, m, v, n, nq, b1, b2, eps, wd, gscale, bias_corr, ctl_f,
+                   (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+constexpr int kZeroThreads = 256;
+constexpr int kZeroMaxBlocks = 256 * 8;   // adamw_ctl_kernel's cap
+
+// The gated memset of the flat gradient.  head / tail as in grad_sumsq_kernel: the elements in front of the first 16-byte
+// boundary and behind the last whole quad go one by one (lanes 0-2 / 3-5 of workgroup 0), the quads between them with one
+// 16-byte store each, grid-stride.
+__global__ __launch_bounds__(kZeroThreads) void accum_begin_kernel(float* g, long n, const int32_t* accum) {
+    if (accum[0] != 0) return;   // inside a window: the gradient keeps accumulating
+    const int tid = threadIdx.x;
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const long nq = (n - head) >> 2;
+    const long tail0 = head + 4 * nq;
+    f32x4* q = reinterpret_cast<f32x4*>(g + head);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const long stride = (long)gridDim.x * kZeroThreads;
+    for (long i = (long)blockIdx.x * kZeroThreads + tid; i < nq; i += stride) q[i] = zero;
+    if (blockIdx.x == 0) {
+        if (tid < head)
+            g[tid] = 0.f;
+        else if (tid >= 3 && tid < 6 && tail0 + (tid - 3) < n)
+            g[tail0 + (tid - 3)] = 0.f;
+    }
+}
+
+int32_t sumsq_launch(const float* grad, int64_t n, double* partials, int64_t workspace_doubles, hipStream_t stream, int* nparts,
+                     const int32_t* accum = nullptr, int last = 0) {
     if (grad == nullptr || partials == nullptr || n < 0) return NLAM_EINVAL;
     if ((reinterpret_cast<uintptr_t>(grad) & 3) != 0 || (reinterpret_cast<uintptr_t>(partials) & 7) != 0) return NLAM_EINVAL;
     const int blocks = sumsq_blocks((long)n);
     if (workspace_doubles < blocks) return NLAM_EINVAL;
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(kSumsqThreads), 0, stream, grad, (long)n, partials);
+    if (accum == nullptr)
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(kSumsqThreads), 0, stream, grad, (long)n, partials);
+    else
+        hipLaunchKernelGGL(grad_sumsq_accum_kernel, dim3(blocks), dim3(kSumsqThreads), 0, stream, grad, (long)n, partials, accum, last);
     *nparts = blocks;
+    return (int32_t)hipGetLastError();
+}
+
+// the three launches of nlam_adamw_step_controlled; with `acc` each of them behind its gate
+int32_t optctl_launch(const nlam_optctl_t* p, const nlam_accum_t* acc, hipStream_t stream) {
+    if (p == nullptr || p->param == nullptr || p->grad == nullptr || p->exp_avg == nullptr || p->exp_avg_sq == nullptr ||
+        p->step_count_dev == nullptr || p->bias_corr_dev == nullptr || p->control == nullptr || p->n < 0)
+        return NLAM_EINVAL;
+    if (p->schedule < NLAM_SCHED_NONE || p->schedule > NLAM_SCHED_WARMUP_LINEAR || p->warmup_steps < 0 || p->total_steps < 0 ||
+        !(p->min_ratio >= 0.f && p->min_ratio <= 1.f) || p->max_grad_norm != p->max_grad_norm)
+        return NLAM_EINVAL;
+    if (p->schedule == NLAM_SCHED_NONE && p->warmup_steps != 0) return NLAM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(p->control) & 3) != 0) return NLAM_EINVAL;
+    int nparts = 0;
+    if (acc == nullptr) {
+        if (const int32_t rc = sumsq_launch(p->grad, p->n, p->partials, p->partials_doubles, stream, &nparts)) return rc;
+    } else {
+        if (const int32_t rc = sumsq_launch(p->grad, p->n, p->partials, p->partials_doubles, stream, &nparts, acc->accum, acc->steps - 1))
+            return rc;
+    }
+    OptCtlArgs a;
+    a.partials = p->partials;
+    a.step_count = p->step_count_dev;
+    a.bias_corr = p->bias_corr_dev;
+    a.ctl_f = reinterpret_cast<float*>(p->control);
+    a.ctl_i = reinterpret_cast<int32_t*>(p->control);
+    a.nparts = nparts;
+    a.lr = p->lr, a.b1 = p->beta1, a.b2 = p->beta2, a.grad_scale = p->grad_scale;
+    a.max_norm = p->max_grad_norm, a.min_ratio = p->min_ratio;
+    a.kind = p->schedule, a.warmup = p->warmup_steps, a.total = p->total_steps, a.skip_nonfinite = p->skip_nonfinite != 0;
+    if (acc == nullptr)
+        hipLaunchKernelGGL(adamw_control_kernel, dim3(1), dim3(64), 0, stream, a);
+    else
+        hipLaunchKernelGGL(adamw_control_accum_kernel, dim3(1), dim3(64), 0, stream, a, acc->accum, acc->loss, (int)acc->steps);
+    if (p->n == 0) return (int32_t)hipGetLastError();
+    // quads only where all four buffers sit on a 16-byte boundary (the flat buffers do); element by element otherwise
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(p->param) | reinterpret_cast<uintptr_t>(p->grad) |
+                           reinterpret_cast<uintptr_t>(p->exp_avg) | reinterpret_cast<uintptr_t>(p->exp_avg_sq);
+    const long nq = (bits & 15) == 0 ? (long)(p->n >> 2) : 0L;
+    const long work = nq > 0 ? nq : (long)p->n;
+    long blocks = (work + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    if (acc == nullptr)
+        hipLaunchKernelGGL(adamw_ctl_kernel, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg, p->exp_avg_sq,
+                           (long)p->n, nq, p->beta1, p->beta2, p->eps, p->weight_decay, p->grad_scale, (const float*)p->bias_corr_dev,
+                           (const float*)a.ctl_f, (const int32_t*)a.ctl_i);
+    else
+        hipLaunchKernelGGL(adamw_ctl_accum_kernel, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg,
+                           p->exp_avg_sq, (long)p->n, nq, p->beta1, p->beta2, p->eps, p->weight_decay, p->grad_scale,
+                           (const float*)p->bias_corr_dev, (const float*)a.ctl_f, (const int32_t*)a.ctl_i,
+                           (const int32_t*)acc->accum);
     return (int32_t)hipGetLastError();
 }
 
@@ -233,39 +378,24 @@ int32_t nlam_grad_sumsq(const float* grad, int64_t n, double* partials, int64_t 
 
 int32_t nlam_adamw_step_controlled(const nlam_optctl_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_adamw_step_controlled");
-    if (p == nullptr || p->param == nullptr || p->grad == nullptr || p->exp_avg == nullptr || p->exp_avg_sq == nullptr ||
-        p->step_count_dev == nullptr || p->bias_corr_dev == nullptr || p->control == nullptr || p->n < 0)
-        return NLAM_EINVAL;
-    if (p->schedule < NLAM_SCHED_NONE || p->schedule > NLAM_SCHED_WARMUP_LINEAR || p->warmup_steps < 0 || p->total_steps < 0 ||
-        !(p->min_ratio >= 0.f && p->min_ratio <= 1.f) || p->max_grad_norm != p->max_grad_norm)
-        return NLAM_EINVAL;
-    if (p->schedule == NLAM_SCHED_NONE && p->warmup_steps != 0) return NLAM_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p->control) & 3) != 0) return NLAM_EINVAL;
-    const hipStream_t stream = (hipStream_t)hip_stream;
-    int nparts = 0;
-    if (const int32_t rc = sumsq_launch(p->grad, p->n, p->partials, p->partials_doubles, stream, &nparts)) return rc;
-    OptCtlArgs a;
-    a.partials = p->partials;
-    a.step_count = p->step_count_dev;
-    a.bias_corr = p->bias_corr_dev;
-    a.ctl_f = reinterpret_cast<float*>(p->control);
-    a.ctl_i = reinterpret_cast<int32_t*>(p->control);
-    a.nparts = nparts;
-    a.lr = p->lr, a.b1 = p->beta1, a.b2 = p->beta2, a.grad_scale = p->grad_scale;
-    a.max_norm = p->max_grad_norm, a.min_ratio = p->min_ratio;
-    a.kind = p->schedule, a.warmup = p->warmup_steps, a.total = p->total_steps, a.skip_nonfinite = p->skip_nonfinite != 0;
-    hipLaunchKernelGGL(adamw_control_kernel, dim3(1), dim3(64), 0, stream, a);
-    if (p->n == 0) return (int32_t)hipGetLastError();
-    // quads only where all four buffers sit on a 16-byte boundary (the flat buffers do); element by element otherwise
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(p->param) | reinterpret_cast<uintptr_t>(p->grad) |
-                           reinterpret_cast<uintptr_t>(p->exp_avg) | reinterpret_cast<uintptr_t>(p->exp_avg_sq);
-    const long nq = (bits & 15) == 0 ? (long)(p->n >> 2) : 0L;
-    const long work = nq > 0 ? nq : (long)p->n;
-    long blocks = (work + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(adamw_ctl_kernel, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg, p->exp_avg_sq,
-                       (long)p->n, nq, p->beta1, p->beta2, p->eps, p->weight_decay, p->grad_scale, (const float*)p->bias_corr_dev,
-                       (const float*)a.ctl_f, (const int32_t*)a.ctl_i);
+    return optctl_launch(p, nullptr, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_adamw_step_accum(const nlam_optctl_t* p, const nlam_accum_t* a, void* hip_stream) {
+    NLAM_RANGE("nlam_adamw_step_accum");
+    if (a == nullptr || a->accum == nullptr || a->steps < 1) return NLAM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(a->accum) & 3) != 0 || (reinterpret_cast<uintptr_t>(a->loss) & 3) != 0) return NLAM_EINVAL;
+    return optctl_launch(p, a, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_accum_begin(float* grad, int64_t n, const int32_t* accum, void* hip_stream) {
+    NLAM_RANGE("nlam_accum_begin");
+    if (grad == nullptr || accum == nullptr || n < 0) return NLAM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(grad) & 3) != 0 || (reinterpret_cast<uintptr_t>(accum) & 3) != 0) return NLAM_EINVAL;
+    if (n == 0) return 0;
+    long blocks = ((long)(n >> 2) + kZeroThreads - 1) / kZeroThreads;
+    blocks = blocks < 1 ? 1 : (blocks > kZeroMaxBlocks ? kZeroMaxBlocks : blocks);
+    hipLaunchKernelGGL(accum_begin_kernel, dim3((int)blocks), dim3(kZeroThreads), 0, (hipStream_t)hip_stream, grad, (long)n, accum);
     return (int32_t)hipGetLastError();
 }
 

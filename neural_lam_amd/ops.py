@@ -2763,10 +2763,19 @@ class AdamWFlat:
     * ``lr_schedule``: an ``LRSchedule`` evaluated from the resident step count (``lr`` stays the base rate);
     * ``skip_nonfinite``: a step whose gradient norm is inf / nan changes nothing -- parameters, moments, step count and bias
       corrections stay -- and is counted in ``skipped_steps``.  The host mirror ``t`` then counts attempts, not updates:
-      ``step_count()`` reads the truth from the device."""
+      ``step_count()`` reads the truth from the device;
+    * ``accumulate`` = K > 1 (Lightning's ``accumulate_grad_batches``): a call is one micro-batch and every K-th call
+      updates.  The caller does ``begin()``; add its gradient into ``flat_grad``; ``step(grad_scale / K, loss=...)``.  Both ends
+      are decided ON THE DEVICE from a block of ``NLAM_ACCUM_WORDS`` words: ``begin()`` zeroes the gradient only in front of
+      the first micro-batch of a window, and ``step`` (``nlam_adamw_step_accum``: the same three launches, each gated) holds
+      until the last one -- the norm is that of the whole window's gradient.  The launches are the same on every call, so a
+      step recorded once serves all of them.  ``micro_step`` is the host mirror of the index within the window, ``t``
+      advances on the closing call only, and ``grad_norm`` / ``last_lr`` / ``clip_coef`` keep the last closed window's values
+      while a window is open.  A window skipped for a non-finite norm is closed all the same: the next ``begin()`` clears
+      the poisoned gradient."""
 
     def __init__(self, flat_param, flat_grad, lr=1e-3, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 lr_schedule=None, skip_nonfinite=False):
+                 lr_schedule=None, skip_nonfinite=False, accumulate=1):
         self.p, self.g = flat_param, flat_grad
         self.m = torch.zeros_like(flat_param)
         self.v = torch.zeros_like(flat_param)
@@ -2783,7 +2792,17 @@ class AdamWFlat:
         # launch constants of the control kernel, fixed here (read-only properties below): a captured step carries them
         self._max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self._lr_schedule, self._skip_nonfinite = lr_schedule, bool(skip_nonfinite)
-        self._controlled = self._max_grad_norm is not None or lr_schedule is not None or self._skip_nonfinite
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"accumulate must be a count of micro-batches >= 1, not {accumulate!r}")
+        self._accumulate = int(accumulate)
+        self._controlled = (self._max_grad_norm is not None or lr_schedule is not None or self._skip_nonfinite
+                            or self._accumulate > 1)
+        self.micro_step = 0   # host mirror of word 0 of ``acc``: calls mod K
+        self._window_loss = None
+        if self._accumulate > 1:
+            # the device block of nlam_accum_t.accum (index in the window, hold flag as words; loss sum, window loss as floats)
+            self.acc = torch.zeros((L.ACCUM_WORDS,), device=flat_param.device, dtype=torch.int32)
+            self._acc_f = self.acc.view(torch.float32)
         if self.controlled:
             # the device block of nlam_optctl_t.control (lr_t, coefficient, norm as floats; skip flag, skipped steps as words)
             self.ctl = torch.zeros((L.OPTCTL_WORDS,), device=flat_param.device, dtype=torch.int32)
@@ -2798,9 +2817,28 @@ class AdamWFlat:
     lr_schedule = property(lambda self: self._lr_schedule)
     skip_nonfinite = property(lambda self: self._skip_nonfinite)
     controlled = property(lambda self: self._controlled)
+    accumulate = property(lambda self: self._accumulate)
 
-    def step(self, grad_scale: float = 1.0):
-        """One update (eager or inside a stream capture).  A caller that REPLAYS a captured step calls ``note_replayed``."""
+    def begin(self):
+        """The head of a step, in front of forward + backward: the gradient is zeroed -- with ``accumulate`` > 1 by a launch
+        that does so only when the device says a window opens here (``nlam_accum_begin``), so it can be captured."""
+        if self._accumulate == 1:
+            self.g.zero_()
+            return
+        L.check(L.load().nlam_accum_begin(_ptr(self.g), self.g.numel(), _ptr(self.acc), _stream()), "nlam_accum_begin")
+
+    def _advance(self):
+        self.micro_step = (self.micro_step + 1) % self._accumulate
+        if self.micro_step == 0:   # this call closed a window
+            self.t += 1
+
+    def step(self, grad_scale: float = 1.0, loss=None):
+        """One update (eager or inside a stream capture).  A caller that REPLAYS a captured step calls ``note_replayed``.
+        With ``accumulate`` > 1: one micro-batch; ``loss`` (a 0-dim fp32 device tensor) is averaged over the window on the
+        device (``window_loss``)."""
+        if self._accumulate > 1:
+            self._advance()
+            return self._step_controlled(grad_scale, loss)
         self.t += 1
         if self.controlled:
             return self._step_controlled(grad_scale)
@@ -2810,7 +2848,8 @@ class AdamWFlat:
         )
         L.check(rc, "nlam_adamw_step_resident")
 
-    def _step_controlled(self, grad_scale):
+    def _optctl(self, grad_scale):
+        """The nlam_optctl_t of this optimizer's controlled launches."""
         c, sch = L.OptCtl(), self.lr_schedule
         c.param, c.grad, c.exp_avg, c.exp_avg_sq = _ptr(self.p), _ptr(self.g), _ptr(self.m), _ptr(self.v)
         c.step_count_dev, c.bias_corr_dev = _ptr(self.t_dev), _ptr(self.bc_dev)
@@ -2824,7 +2863,33 @@ class AdamWFlat:
         else:
             c.schedule = L.SCHED_NONE
         c.skip_nonfinite = int(self.skip_nonfinite)
-        L.check(L.load().nlam_adamw_step_controlled(C.byref(c), _stream()), "nlam_adamw_step_controlled")
+        return c
+
+    def _step_controlled(self, grad_scale, loss=None):
+        c = self._optctl(grad_scale)
+        if self._accumulate == 1:
+            L.check(L.load().nlam_adamw_step_controlled(C.byref(c), _stream()), "nlam_adamw_step_controlled")
+            return
+        a = L.Accum()
+        a.accum, a.steps = _ptr(self.acc), self._accumulate
+        if loss is not None and loss.dim() == 0 and loss.dtype == torch.float32 and loss.device == self.acc.device:
+            a.loss = _ptr(loss)
+            self._window_loss = self._acc_f[L.ACCUM_WINDOW_LOSS]
+        L.check(L.load().nlam_adamw_step_accum(C.byref(c), C.byref(a), _stream()), "nlam_adamw_step_accum")
+
+    @property
+    def window_loss(self):
+        """The mean of the micro-batch losses of the last closed window: a 0-dim device tensor, read without a synchronise (a
+        view of the accumulation block).  Exists once ``step`` has been handed a 0-dim fp32 device loss."""
+        if self._window_loss is None:
+            raise AttributeError("window_loss exists with accumulate > 1, after a step(..., loss=<0-dim fp32 device tensor>)")
+        return self._window_loss
+
+    def reset_window(self):
+        """Back to a window boundary (a checkpoint was loaded): the next call is the first micro-batch of a window."""
+        self.micro_step = 0
+        if self._accumulate > 1:
+            self.acc.zero_()
 
     def _control_word(self, k, as_float):
         if not self.controlled:
@@ -2870,4 +2935,7 @@ class AdamWFlat:
     capturable = True
 
     def note_replayed(self):
-        self.t += 1
+        if self._accumulate > 1:
+            self._advance()
+        else:
+            self.t += 1

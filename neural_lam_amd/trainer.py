@@ -60,6 +60,9 @@ class FlatParams:
 
     def zero_grad(self):
         self.grad.zero_()
+        self.reattach()
+
+    def reattach(self):
         for i, p in enumerate(self.params):  # autograd may have replaced .grad; re-attach the views
             o, n = self.offsets[i], p.numel()
             if p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * o:
@@ -406,12 +409,27 @@ class Trainer:
                  bucket_bytes: int = 32 << 20, optimizer_factory=None, group=None, use_graph: bool = False,
                  overlap_wgrad: bool = True, early_leaf_backward: bool | None = None, grad_comm_dtype=None,
                  executor: str | None = None, forks_per_segment: int | None = None, max_grad_norm=None, lr_schedule=None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, accumulate_grad_batches: int = 1):
         """``max_grad_norm`` / ``lr_schedule`` (an ``ops.LRSchedule``) / ``skip_nonfinite``: the optimizer controls of
         ``ops.AdamWFlat``, decided on the device inside the captured step.  A schedule given here never re-records anything
-        and never evicts the optimizer from the graph; setting ``opt.lr`` by hand keeps doing both (see ``_optimizer_changed``)."""
+        and never evicts the optimizer from the graph; setting ``opt.lr`` by hand keeps doing both (see ``_optimizer_changed``).
+
+        ``accumulate_grad_batches`` = K (Lightning's ``Trainer(accumulate_grad_batches=K)``): every ``step`` / ``step_from``
+        call is one micro-batch and returns that micro-batch's loss; the gradients of K calls are averaged (``1 / (world * K)``
+        folded into the AdamW launch) and every K-th call updates, so ``global_step`` counts updates.  Micro-batches of unequal
+        size are averaged as a mean of their means, as under Lightning.  With the built-in optimizer the DEVICE decides whether a
+        call opens or closes a window (``AdamWFlat(accumulate=K)``): the recorded step is the same for every micro-step, nothing
+        is re-recorded, and eager and replayed micro-steps may mix inside a window.  The host decides only where the gradient
+        exchange goes out (world > 1: on the closing micro-step) -- and everything for an ``optimizer_factory`` optimizer,
+        which has no device gate and therefore needs ``use_graph=False``."""
         import os
 
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be a count of micro-batches >= 1, not {accumulate_grad_batches!r}")
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        if self.accumulate_grad_batches > 1 and optimizer_factory is not None and use_graph:
+            raise ValueError("accumulate_grad_batches > 1 inside a captured step needs the built-in AdamWFlat, which gates the "
+                             "step on the device: with an optimizer_factory pass use_graph=False")
         self.module = module
         self.use_graph = use_graph
         if os.environ.get("NLAM_OVERLAP_WGRAD") in ("0", "1"):   # A/B runs: the whole step on one stream (0)
@@ -445,13 +463,57 @@ class Trainer:
             from .ops import AdamWFlat
 
             self.opt = AdamWFlat(self.fp.flat, self.fp.grad, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                 max_grad_norm=max_grad_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
+                                 max_grad_norm=max_grad_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite,
+                                 accumulate=self.accumulate_grad_batches)
+            self._device_gate = self.accumulate_grad_batches > 1
         else:
             if max_grad_norm is not None or lr_schedule is not None or skip_nonfinite:
                 raise ValueError("max_grad_norm / lr_schedule / skip_nonfinite are options of the built-in AdamWFlat: an "
                                  "optimizer_factory builds its own optimizer")
             self.opt = optimizer_factory(self.fp.flat, self.fp.grad)
         self._built_hyper = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)   # restored by restore_opt=False
+
+    # ---- gradient accumulation ----
+    _device_gate = False   # accumulate_grad_batches > 1 under the built-in optimizer: the device opens and closes the windows
+    _micro = 0             # calls mod K where the host decides (an optimizer_factory optimizer)
+
+    @property
+    def micro_step(self) -> int:
+        """Index of the next call's micro-batch in its window (calls mod ``accumulate_grad_batches``)."""
+        return self.opt.micro_step if self._device_gate else self._micro
+
+    def _closing(self) -> bool:
+        """The call being made is the last micro-batch of its window: the one that exchanges gradients and updates."""
+        return self.micro_step == self.accumulate_grad_batches - 1
+
+    def _grad_scale(self) -> float:
+        """The mean over ranks and micro-batches, folded into the AdamW launch."""
+        return 1.0 / (self.world * self.accumulate_grad_batches)
+
+    def _zero_head(self):
+        """The head of a recorded step: the zero of the flat gradient, gated on the device inside an accumulation window."""
+        if self._device_gate:
+            self.opt.begin()
+        else:
+            self.fp.grad.zero_()
+
+    def _opt_step(self, loss=None):
+        if self._device_gate:
+            self.opt.step(self._grad_scale(), loss=loss)
+        else:
+            self.opt.step(self._grad_scale())
+
+    def _opt_mirror(self):
+        """The optimizer's host mirrors of device counters: a capture records launches without running them, so whatever
+        they advanced is put back."""
+        return getattr(self.opt, "t", None), getattr(self.opt, "micro_step", None)
+
+    def _restore_mirror(self, mirror):
+        t, micro = mirror
+        if t is not None:
+            self.opt.t = t
+        if micro is not None:
+            self.opt.micro_step = micro
 
     @staticmethod
     def _pick_executor(module) -> str:
@@ -563,6 +625,16 @@ class Trainer:
             self._static_in = [b.clone() for b in batch]
         self._static_sig = [(tuple(b.shape), b.dtype) for b in batch]
         self.buckets.enabled = False
+        # a step recorded in the middle of an accumulation window (opt.lr was assigned): the warm-up passes write into the
+        # flat gradient, which holds the window's sum so far -- it is put back behind the capture
+        held = self.fp.grad.clone() if self.accumulate_grad_batches > 1 else None
+        try:
+            self._warm_up_and_record()
+        finally:
+            if held is not None:
+                self.fp.grad.copy_(held)
+
+    def _warm_up_and_record(self):
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):   # warm-up outside capture: lazy CSR builds, LDS-size attributes, allocator pool
@@ -573,9 +645,9 @@ class Trainer:
         torch.cuda.synchronize()
         # the warm-up's autograd graph (and its AccumulateGrad nodes, bound to the side stream) is gone here, so the
         # capture creates its own on the capture stream and accumulates in place into the flat gradient views
-        t_before = getattr(self.opt, "t", None)
+        mirror = self._opt_mirror()
         if self.executor == "segments" and self.overlap_wgrad:
-            self._capture_segments(t_before)
+            self._capture_segments(mirror)
             return
         self._graph = torch.cuda.CUDAGraph()
         # thread_local: the RCCL watchdog thread may query events while this thread captures
@@ -586,14 +658,13 @@ class Trainer:
         self._tail_graph = None
         try:
             with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-                self.fp.grad.zero_()
+                self._zero_head()
                 self._static_loss = self._fwd_bwd()
                 if self._opt_in_graph:
-                    self.opt.step(1.0)
+                    self._opt_step(self._static_loss)
             self._capture_tail()
         finally:
-            if t_before is not None:
-                self.opt.t = t_before   # the capture recorded the launches without running them (also when it failed half way)
+            self._restore_mirror(mirror)   # the capture recorded the launches without running them (also when it failed half way)
         self._opt_sig = self._opt_signature()
 
     _tail_graph = None
@@ -604,14 +675,13 @@ class Trainer:
         corrections live on the device) -- no per-step launch arguments, one replay instead of two eager launches."""
         self._tail_graph = None
         if self.world > 1 and bool(getattr(self.opt, "capturable", False)) and not self._opt_eager:
-            t_before = getattr(self.opt, "t", None)
+            mirror = self._opt_mirror()
             g = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self.opt.step(1.0 / self.world)
+                    self._opt_step(self._static_loss)
             finally:
-                if t_before is not None:
-                    self.opt.t = t_before
+                self._restore_mirror(mirror)
             self._tail_graph = g
 
     _chain_stream = None
@@ -620,7 +690,7 @@ class Trainer:
     _opt_eager = False     # the optimizer's hyper-parameters keep changing (a schedule): it runs behind the replay, uncaptured
     _bucket_plan = None
 
-    def _capture_segments(self, t_before):
+    def _capture_segments(self, mirror):
         """Record the step as a _SegmentedStep (see its docstring): chain segments on one stream, one
         weight-gradient graph per (segment, side stream), the optimizer as a last graph behind the join."""
         import os
@@ -648,7 +718,7 @@ class Trainer:
                 # reductions a chain launch did itself)
                 self.buckets.chain_recorder = seg.chain_params
                 try:
-                    self.fp.grad.zero_()
+                    self._zero_head()
                     self._static_loss = self._fwd_bwd()   # ops.OVERLAP.end() -> seg.finish(): every graph but the optimizer's
                 except BaseException:
                     seg.abort()
@@ -660,12 +730,11 @@ class Trainer:
                     seg.tail = torch.cuda.CUDAGraph()
                     seg.tail.capture_begin(pool=seg.pool, capture_error_mode=seg.mode)
                     try:
-                        self.opt.step(1.0 / self.world)
+                        self._opt_step(self._static_loss)
                     finally:
                         seg.tail.capture_end()
         finally:
-            if t_before is not None:
-                self.opt.t = t_before
+            self._restore_mirror(mirror)
         torch.cuda.current_stream().wait_stream(cs)
         self._graph = seg
         self._bucket_plan = self._plan_buckets(seg) if self.world > 1 else None
@@ -734,18 +803,17 @@ class Trainer:
                 else:
                     self._graph = None
                 return
-            t_before = getattr(self.opt, "t", None)
+            mirror = self._opt_mirror()
             try:
                 with torch.cuda.stream(self._chain_stream):
                     seg.tail = torch.cuda.CUDAGraph()
                     seg.tail.capture_begin(pool=seg.pool, capture_error_mode=seg.mode)
                     try:
-                        self.opt.step(1.0 / self.world)
+                        self._opt_step(self._static_loss)
                     finally:
                         seg.tail.capture_end()
             finally:
-                if t_before is not None:
-                    self.opt.t = t_before   # the capture recorded the launches without running them (also when it failed)
+                self._restore_mirror(mirror)   # the capture recorded the launches without running them (also when it failed)
             self._opt_sig = self._opt_signature()
         finally:
             if was_enabled:
@@ -796,7 +864,7 @@ class Trainer:
             g.replay()
             self._after_replay()
             return
-        if self.world > 1:
+        if self.world > 1 and self._closing():   # (inside an accumulation window the gradient stays local)
             # bucket collectives are launched from a communication stream that waits, on the device, for the chain segment and
             # the weight-gradient graphs completing the bucket; the chain goes on meanwhile.  RCCL calls stay outside every
             # capture: a communicator fault can never poison a graph.
@@ -829,7 +897,7 @@ class Trainer:
         if self._opt_in_graph:
             self.opt.note_replayed()
         else:
-            self.opt.step(1.0 / self.world)
+            self._opt_step(self._static_loss)
 
     def _after_replay(self):
         """One-graph executor: gradient exchange + optimizer behind the replay (the optimizer is part of the graph when
@@ -837,23 +905,49 @@ class Trainer:
         if self._opt_in_graph:
             self.opt.note_replayed()
             return
-        if self.world > 1:   # one flat buffer: a single collective (0.86 MB at cfg2, 20.6 MB at cfg3; half of that with bf16 exchange)
+        if self.world > 1 and self._closing():   # one flat buffer: a single collective (0.86 MB at cfg2, 20.6 MB at cfg3; half of that with bf16 exchange)
             self.buckets.all_reduce_whole()
         if self._tail_graph is not None:
             self._tail_graph.replay()
             self.opt.note_replayed()
         else:
-            self.opt.step(1.0 / self.world)
+            self._opt_step(self._static_loss)
 
     def step(self, *batch):
         if self.use_graph:
             return self._graph_step(*batch)
+        if self.accumulate_grad_batches > 1:
+            return self._accumulating_step(batch)
         self.buckets.enabled = True
         self.fp.zero_grad()
         self.buckets.begin_step()
         loss = self._fwd_bwd_on(batch)
         self.buckets.finish_step()
         self.opt.step(1.0 / self.world)
+        return loss
+
+    def _accumulating_step(self, batch):
+        """The eager step of one micro-batch.  Built-in optimizer: the same gated head and tail as the recorded step, so eager
+        and replayed micro-steps mix inside a window (a batch of another shape falls through to here).  The gradient exchange
+        belongs to the closing micro-step alone: the bucket hooks are armed for that backward only."""
+        closing = self._closing()
+        self.buckets.enabled = closing
+        if self._device_gate:
+            self.opt.begin()
+            self.fp.reattach()
+        elif self._micro == 0:
+            self.fp.zero_grad()
+        if closing:
+            self.buckets.begin_step()
+        loss = self._fwd_bwd_on(batch)
+        if closing:
+            self.buckets.finish_step()
+        if self._device_gate:
+            self.opt.step(self._grad_scale(), loss=loss)
+        else:
+            if closing:
+                self.opt.step(self._grad_scale())
+            self._micro = (self._micro + 1) % self.accumulate_grad_batches
         return loss
 
     def step_from(self, dataset, indices, standardize=True):
@@ -898,6 +992,11 @@ class Trainer:
         return self.opt.last_lr
 
     @property
+    def window_loss(self):
+        """accumulate_grad_batches > 1: the mean loss of the last completed window (device tensor, no synchronise)."""
+        return self.opt.window_loss
+
+    @property
     def skipped_steps(self) -> int:
         return self.opt.skipped_steps
 
@@ -927,6 +1026,10 @@ class Trainer:
         from .checkpoint import NAMESPACE, export_flat_state, module_state_to_cpu
 
         opt = self._flat_adamw()
+        if self.micro_step != 0:
+            raise RuntimeError(f"state_dict() inside an accumulation window (micro-batch {self.micro_step} of "
+                               f"{self.accumulate_grad_batches}): a checkpoint is taken at a window boundary, the reference "
+                               "layout has no place for half a window")
         names, shapes, offsets = self._layout()
         t = int(opt.t_dev.item())   # the device counter is the truth; ``t`` mirrors it
         hyper = dict(lr=opt.scheduled_lr(t), betas=opt.betas, eps=opt.eps, weight_decay=opt.wd)
@@ -939,6 +1042,8 @@ class Trainer:
             out[NAMESPACE] = {"optimizer_controls": {
                 "base_lr": opt.lr, "lr_schedule": None if opt.lr_schedule is None else opt.lr_schedule.state_dict(),
                 "max_grad_norm": opt.max_grad_norm, "skip_nonfinite": opt.skip_nonfinite, "skipped_steps": opt.skipped_steps}}
+            if self.accumulate_grad_batches > 1:
+                out[NAMESPACE]["optimizer_controls"]["accumulate_grad_batches"] = self.accumulate_grad_batches
         return out
 
     def load_state_dict(self, ckpt: dict, restore_opt: bool = True, strict: bool = True):
@@ -988,6 +1093,14 @@ class Trainer:
 
                 warnings.warn(f"the checkpoint was written under the learning-rate schedule {controls.get('lr_schedule')}, this "
                               f"trainer runs {mine}: the run continues under this trainer's")
+        saved_k = int(controls.get("accumulate_grad_batches", 1)) if controls is not None else None
+        if saved_k is not None and saved_k != self.accumulate_grad_batches:
+            import warnings
+
+            warnings.warn(f"the checkpoint was written with accumulate_grad_batches={saved_k}, this trainer runs "
+                          f"{self.accumulate_grad_batches}: the run continues under this trainer's")
+        opt.reset_window()   # a checkpoint is a window boundary
+        self._micro = 0
         if getattr(opt, "controlled", False):
             opt.set_skipped_steps(int(controls.get("skipped_steps", 0)) if controls is not None else 0)
         if self._graph is not None and (self._opt_in_graph or self._tail_graph is not None) and self._opt_signature() != self._opt_sig:
