@@ -43,7 +43,8 @@
  *   nlam_loss_fwd / nlam_loss_bwd, nlam_step_tail_loss_fwd / nlam_step_tail_loss_bwd
  *       the other losses of --loss (train_model.py:271-276): metrics.mse / mae / wmae / nll / crps_gauss
  *       (and wmse), per-variable or per-entry (predicted) std, the same reduction; the step-tail pair fuses
- *       them into the AR step's state update as nlam_step_tail_* does for wmse.
+ *       them into the AR step's state update: the kernels of nlam_step_tail_fwd / _bwd, instantiated on the kind's
+ *       loss term and its std where those two take inv_var = 1 / std^2.
  *   nlam_eval_metrics, nlam_eval_workspace_floats
  *       the evaluation tensors of validation_step / test_step (models/module.py:546-576, :607-681): per-step loss,
  *       per-variable masked MSE / MAE / mean std, per-node loss maps; one pass over the rollout + a fixed-order reduction.
@@ -631,7 +632,8 @@ int32_t nlam_loss_fwd(const nlam_loss_t* p, void* hip_stream);
 int32_t nlam_loss_bwd(const nlam_loss_t* p, void* hip_stream);
 /* nlam_step_tail_fwd / _bwd with the loss term of any NLAM_LOSS_* kind for a per-variable std (`var_std`, may be NULL for mse /
  * mae) instead of inv_var:  loss += scale * row_weight[n] * entry(pred - target, var_std[f]),
- *   G = g_pred + scale * gloss * row_weight[n] * d entry / d pred.  Still one pass each way per AR step. */
+ *   G = g_pred + scale * gloss * row_weight[n] * d entry / d pred.  Still one pass each way per AR step: one kernel template
+ * serves both pairs.  This pair asks for rows % nodes == 0 and width <= NLAM_LOSS_MAX_VARS (NLAM_EUNSUP above). */
 int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* prev, const float* truth, const float* target,
                                 const float* dstd, const float* dmean, const float* bmask, const float* var_std,
                                 const float* row_weight, float scale, float* pred, float* partials, int32_t nparts, int64_t rows,

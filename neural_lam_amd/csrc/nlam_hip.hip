@@ -37,9 +37,12 @@
 #include <string.h>
 
 // ---------------------------------------------------------------------------
-// Translation-unit slices.  Every kernel here is a template that is instantiated only where a launcher names it, so
-// the same source can be compiled several times with -DNLAM_TU=k, each time emitting one family's launchers (and with
-// them that family's kernels): the objects build in parallel and link into one library (neural_lam_amd/_lib.py).
+// Translation-unit slices.  The same source is compiled several times with -DNLAM_TU=k, each time emitting one family's
+// launchers and with them that family's kernels: the objects build in parallel and link into one library
+// (neural_lam_amd/_lib.py).  A kernel template is instantiated only where a launcher names it and needs no guard.  A kernel
+// that is no template is emitted wherever it is defined, so it sits inside the #if NLAM_IN_TU(k) of the slice whose launcher
+// names it (a launcher in another slice then does not compile): every kernel exists once, and the kernel counts of the six
+// slices add up to the count of the single translation unit.
 // NLAM_TU undefined or 0 = everything in one translation unit (the one-command build of INTEGRATION.md, and the
 // -DNLAM_TIMING build, whose counters live in one device variable).
 //   1  C-ABI entry points, argument checks, HBM-bound helper kernels, narrow (d <= 64) forward
@@ -2893,6 +2896,7 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_kernel(const nlam_wgrad_t
 // reduction: lane = column m of A, every wave walks rows, B's few values are broadcast loads.
 // HBM-bound (reads A once).  partials layout as the MFMA kernels: (nparts, m, n).
 constexpr int kSmallN = 8;
+#if NLAM_IN_TU(2)   // a kernel that is no template is emitted wherever it is defined: in the slice of its launcher only
 // m % 4 == 0: lane -> (row of the pass, 4 columns of A): one coalesced 16-B load per lane covers 64 / (m/4) rows
 __global__ __launch_bounds__(256) void wgrad_smalln_kernel(const nlam_wgrad_t p) {
     __shared__ float red[256 * 4 * kSmallN];
@@ -2964,10 +2968,12 @@ __global__ __launch_bounds__(256) void wgrad_smalln_kernel(const nlam_wgrad_t p)
         __syncthreads();
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // small HBM-bound kernels
 // ---------------------------------------------------------------------------
+#if NLAM_IN_TU(1)   // split_combine, segment_sum*, reduce_partials, reduce_jobs
 // buf[b, dst[s], :] = sum over the pieces src[ptr[s] .. ptr[s+1]) of buf[b, piece, :], pieces in list order.  The second pass of
 // the deterministic reduction of receivers that are cut over several tiles (graph.build_tile_schedule, "virtual" split): their
 // pieces reduce into virtual rows behind the real ones with plain stores, this sums them up -- a handful of rows per layer.
@@ -3220,6 +3226,7 @@ __global__ __launch_bounds__(kRedWaves * 64) void reduce_jobs_kernel(const nlam_
         __syncthreads();
     }
 }
+#endif
 
 // element e of a (.., nodes, width) tensor -> (row e / width, node row % nodes); 32-bit divisions whenever the tensor has
 // fewer than 2^31 elements (a 64-bit division is ~100 instructions: per element it kept these passes at ~1 TB/s)
@@ -3234,12 +3241,27 @@ __device__ __forceinline__ void row_and_node(long e, int width, int nodes, bool 
     }
 }
 
+// partials[block] = scale * (sum of s over the 256 threads of the block): shuffle reduction inside each wave, the four waves
+// meet in LDS and are added as ((r0 + r1) + (r2 + r3)) -- the order is part of every loss this feeds.  Only lane 0 of a wave
+// needs the last addition of the shuffle tree: written inside its branch, where the compiler sinks it anyway, the function
+// inlines into the very instructions of the epilogue that each kernel used to spell out.  (`s += __shfl_xor(s, 1, 64)` in
+// front of the branch is equally correct and gives the same sums; with this compiler it moves one shift across a wait.)
+__device__ __forceinline__ void block_sum_to_partial(float s, float scale, float* partials) {
+    __shared__ float red[4];
+#pragma unroll
+    for (int o = 32; o > 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float t = __shfl_xor(s, 1, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s + t;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+}
+
+#if NLAM_IN_TU(1)   // wmse_fwd, affine_mix, standardize
 // masked, weighted MSE (metrics.wmse + mask_and_reduce_metric + the batch / time means of
 // training_step) as one HBM-bound pass: partial[block] = sum rw[row % nodes] * inv_var[v] * (pred - target)^2
 __global__ __launch_bounds__(256) void wmse_fwd_kernel(const float* pred, const float* target, const float* inv_var,
                                                        const float* row_weight, long total, int nodes, int nvars, float scale,
                                                        float* partials) {
-    __shared__ float red[4];
     float s = 0.f;
     const bool small = total < (1L << 31);
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
@@ -3253,11 +3275,7 @@ __global__ __launch_bounds__(256) void wmse_fwd_kernel(const float* pred, const 
             s += w * inv_var[v] * d * d;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+    block_sum_to_partial(s, scale, partials);
 }
 
 // out = a[node] * x + c[node] * (y + z * s[var] + m[var]); every term optional (see nlam_affine_mix)
@@ -3285,7 +3303,7 @@ __global__ void standardize_kernel(const nlam_std_jobs_t jobs) {
     if ((int)blockIdx.y >= jobs.njobs) return;
     const nlam_std_job_t jb = jobs.job[blockIdx.y];
     const long total = jb.rows * jb.width;
-    const bool small = total < (1L << 31);   // 32-bit modulo (see step_tail_fwd_kernel)
+    const bool small = total < (1L << 31);   // 32-bit modulo (see row_and_node)
     if ((total & 3) == 0 && small && ((reinterpret_cast<uintptr_t>(jb.x) | reinterpret_cast<uintptr_t>(jb.out)) & 15) == 0) {
         // four consecutive elements per thread (16-byte accesses), one modulo per four, the column counter advances
         const unsigned nq = (unsigned)(total >> 2), nthr = gridDim.x * blockDim.x;
@@ -3310,98 +3328,7 @@ __global__ void standardize_kernel(const nlam_std_jobs_t jobs) {
         jb.out[e] = __fdiv_rn(__fsub_rn(jb.x[e], jb.mean[f]), jb.std[f]);
     }
 }
-
-// one AR step's elementwise tail (nlam_step_tail_fwd / _bwd): state update, boundary overwrite and the masked weighted
-// MSE partial sums in one pass over the (rows, width) state; the backward in one more
-__global__ __launch_bounds__(256) void step_tail_fwd_kernel(const float* __restrict__ delta, const float* __restrict__ prev,
-                                                            const float* __restrict__ truth, const float* __restrict__ target,
-                                                            const float* __restrict__ dstd, const float* __restrict__ dmean,
-                                                            const float* __restrict__ bmask, const float* __restrict__ inv_var,
-                                                            const float* __restrict__ row_weight, float scale, float* __restrict__ pred,
-                                                            float* __restrict__ partials, long total, int nodes, int width) {
-    __shared__ float red[4];
-    float s = 0.f;
-    const bool small = total < (1L << 31);
-    // four consecutive elements per thread as 16-byte accesses: one (row, node) division per four elements, the variable /
-    // node counters advance incrementally (the scalar loop below is the general path)
-    const bool vec = (total & 3) == 0 && small &&
-                     ((reinterpret_cast<uintptr_t>(delta) | reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(truth) |
-                       reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(pred)) & 15) == 0;
-    if (vec) {
-        const unsigned nq = (unsigned)(total >> 2), nthr = gridDim.x * blockDim.x;
-        for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += nthr) {
-            const unsigned e = 4 * q;
-            unsigned r = e / (unsigned)width;
-            int f = (int)(e - r * (unsigned)width);
-            int n = (int)(r % (unsigned)nodes);
-            const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + e), pr = *reinterpret_cast<const f32x4*>(prev + e);
-            const f32x4 tr = *reinterpret_cast<const f32x4*>(truth + e), tg = *reinterpret_cast<const f32x4*>(target + e);
-            f32x4 pv4;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float nw = pr[c] + (dstd != nullptr ? dl[c] * dstd[f] : dl[c]);
-                if (dmean != nullptr) nw += dmean[f];
-                const float bm = bmask[n];
-                const float pv = bm * tr[c] + (1.f - bm) * nw;
-                pv4[c] = pv;
-                const float w = row_weight[n];
-                if (w != 0.f) {
-                    const float d = pv - tg[c];
-                    s += w * inv_var[f] * d * d;
-                }
-                if (++f == width) {
-                    f = 0;
-                    if (++n == nodes) n = 0;
-                }
-            }
-            *reinterpret_cast<f32x4*>(pred + e) = pv4;
-        }
-    }
-    for (long e0 = vec ? total : (long)blockIdx.x * blockDim.x; e0 < total; e0 += (long)gridDim.x * blockDim.x) {
-        const long e = e0 + threadIdx.x;
-        if (e < total) {
-            long r;
-            int n;
-            row_and_node(e, width, nodes, small, r, n);
-            const int f = (int)(e - r * width);
-            float nw = prev[e] + (dstd != nullptr ? delta[e] * dstd[f] : delta[e]);
-            if (dmean != nullptr) nw += dmean[f];
-            const float bm = bmask[n];
-            const float pv = bm * truth[e] + (1.f - bm) * nw;
-            pred[e] = pv;
-            const float w = row_weight[n];
-            if (w != 0.f) {
-                const float d = pv - target[e];
-                s += w * inv_var[f] * d * d;
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
-}
-
-__global__ void step_tail_bwd_kernel(const float* __restrict__ g_pred, const float* __restrict__ gloss, const float* __restrict__ pred,
-                                     const float* __restrict__ target, const float* __restrict__ dstd, const float* __restrict__ bmask,
-                                     const float* __restrict__ inv_var, const float* __restrict__ row_weight, float scale,
-                                     float* __restrict__ d_delta, float* __restrict__ d_prev, long total, int nodes, int width) {
-    const float g2 = 2.f * scale * gloss[0];
-    const bool small = total < (1L << 31);
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        long r;
-        int n;
-        row_and_node(e, width, nodes, small, r, n);
-        const int f = (int)(e - r * width);
-        const float w = row_weight[n];
-        float G = g_pred != nullptr ? g_pred[e] : 0.f;
-        if (w != 0.f) G += g2 * w * inv_var[f] * (pred[e] - target[e]);
-        G *= 1.f - bmask[n];
-        if (d_prev != nullptr) d_prev[e] = G;
-        if (d_delta != nullptr) d_delta[e] = dstd != nullptr ? G * dstd[f] : G;
-    }
-}
+#endif
 
 // ---------------------------------------------------------------------------
 // the --loss kinds of metrics.py (nlam_loss_fwd / _bwd, nlam_step_tail_loss_fwd / _bwd; KIND = NLAM_LOSS_*).  The std enters
@@ -3481,7 +3408,6 @@ template <int KIND, bool PER_ENTRY>
 __global__ __launch_bounds__(256) void loss_fwd_kernel(const nlam_loss_t p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float2* lc = reinterpret_cast<float2*>(smem);
-    __shared__ float red[4];
     if constexpr (!PER_ENTRY) stage_loss_consts<KIND>(p.var_std, p.nvars, lc);
     const int nodes = p.nodes, width = p.nvars;
     const long total = p.rows * width;
@@ -3533,11 +3459,7 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const nlam_loss_t p) {
             if (w != 0.f) s += w * entry(p.pred[e], p.target[e], PER_ENTRY ? p.std[e] : 0.f, f);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) p.partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * p.scale;
+    block_sum_to_partial(s, p.scale, p.partials);
 }
 
 // dpred = g * row_weight * d entry / d pred, dstd = g * row_weight * d entry / d s (per-entry std), g = scale * gscalar[0]
@@ -3609,21 +3531,54 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const nlam_loss_t p) {
     }
 }
 
-// step_tail_fwd_kernel with the loss term of KIND (per-variable std: constants in LDS)
+// The loss term of the step tail below, as a policy: what one element adds to the loss, and its gradient factor.
+//   InvVarTerm    the default wmse with consts = inv_var = 1 / std^2 handed in (nlam_step_tail_fwd / _bwd): read from global
+//                 memory where it is used, no LDS, no barrier
+//   KindTerm<K>   any NLAM_LOSS_* kind with consts = var_std (nlam_step_tail_loss_fwd / _bwd): (c0, c1) staged in dynamic LDS
+// Each term keeps its own association of the products -- (w * inv_var) * d * d and 2 * scale * gloss here, w * entry(d) and
+// scale * gloss there.  The loss bits of the default configuration and the three-step AdamW trajectory tests are those of the
+// InvVarTerm form: do not "unify" the two expressions.
+struct InvVarTerm {
+    const float* __restrict__ inv_var;
+    __device__ __forceinline__ InvVarTerm(const float* consts, int) : inv_var(consts) {}
+    static size_t lds_bytes(int) { return 0; }
+    __device__ __forceinline__ float entry(float w, float d, int f) const { return w * inv_var[f] * d * d; }
+    __device__ __forceinline__ static float bwd_factor(float scale, float gloss) { return 2.f * scale * gloss; }
+    __device__ __forceinline__ float dpred(float g, float w, float d, int f) const { return g * w * inv_var[f] * d; }
+};
+
 template <int KIND>
-__global__ __launch_bounds__(256) void step_tail_loss_fwd_kernel(const float* __restrict__ delta, const float* __restrict__ prev,
-                                                                 const float* __restrict__ truth, const float* __restrict__ target,
-                                                                 const float* __restrict__ dstd, const float* __restrict__ dmean,
-                                                                 const float* __restrict__ bmask, const float* __restrict__ var_std,
-                                                                 const float* __restrict__ row_weight, float scale,
-                                                                 float* __restrict__ pred, float* __restrict__ partials, long total,
-                                                                 int nodes, int width) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* lc = reinterpret_cast<float2*>(smem);
-    __shared__ float red[4];
-    stage_loss_consts<KIND>(var_std, width, lc);
+struct KindTerm {
+    const float2* lc;
+    __device__ __forceinline__ KindTerm(const float* consts, int width) {
+        extern __shared__ __attribute__((aligned(16))) float smem[];
+        float2* const staged = reinterpret_cast<float2*>(smem);
+        stage_loss_consts<KIND>(consts, width, staged);
+        lc = staged;
+    }
+    static size_t lds_bytes(int width) { return (size_t)width * sizeof(float2); }
+    __device__ __forceinline__ float entry(float w, float d, int f) const {
+        const float2 k = lc[f];
+        return w * loss_entry<KIND>(d, k.x, k.y);
+    }
+    __device__ __forceinline__ static float bwd_factor(float scale, float gloss) { return scale * gloss; }
+    __device__ __forceinline__ float dpred(float g, float w, float d, int f) const { return g * w * loss_dpred<KIND>(d, lc[f].x); }
+};
+
+// one AR step's elementwise tail: state update, boundary overwrite and the masked, weighted partial sums of TERM in one pass
+// over the (rows, width) state; the backward in one more
+template <typename TERM>
+__global__ __launch_bounds__(256) void step_tail_fwd_kernel(const float* __restrict__ delta, const float* __restrict__ prev,
+                                                            const float* __restrict__ truth, const float* __restrict__ target,
+                                                            const float* __restrict__ dstd, const float* __restrict__ dmean,
+                                                            const float* __restrict__ bmask, const float* __restrict__ consts,
+                                                            const float* __restrict__ row_weight, float scale, float* __restrict__ pred,
+                                                            float* __restrict__ partials, long total, int nodes, int width) {
+    const TERM term(consts, width);
     float s = 0.f;
     const bool small = total < (1L << 31);
+    // four consecutive elements per thread as 16-byte accesses: one (row, node) division per four elements, the variable /
+    // node counters advance incrementally (the scalar loop below is the general path)
     const bool vec = (total & 3) == 0 && small &&
                      ((reinterpret_cast<uintptr_t>(delta) | reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(truth) |
                        reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(pred)) & 15) == 0;
@@ -3645,10 +3600,7 @@ __global__ __launch_bounds__(256) void step_tail_loss_fwd_kernel(const float* __
                 const float pv = bm * tr[c] + (1.f - bm) * nw;
                 pv4[c] = pv;
                 const float w = row_weight[n];
-                if (w != 0.f) {
-                    const float2 k = lc[f];
-                    s += w * loss_entry<KIND>(pv - tg[c], k.x, k.y);
-                }
+                if (w != 0.f) s += term.entry(w, pv - tg[c], f);
                 if (++f == width) {
                     f = 0;
                     if (++n == nodes) n = 0;
@@ -3670,30 +3622,21 @@ __global__ __launch_bounds__(256) void step_tail_loss_fwd_kernel(const float* __
             const float pv = bm * truth[e] + (1.f - bm) * nw;
             pred[e] = pv;
             const float w = row_weight[n];
-            if (w != 0.f) {
-                const float2 k = lc[f];
-                s += w * loss_entry<KIND>(pv - target[e], k.x, k.y);
-            }
+            if (w != 0.f) s += term.entry(w, pv - target[e], f);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+    block_sum_to_partial(s, scale, partials);
 }
 
-template <int KIND>
-__global__ __launch_bounds__(256) void step_tail_loss_bwd_kernel(const float* __restrict__ g_pred, const float* __restrict__ gloss,
-                                                                 const float* __restrict__ pred, const float* __restrict__ target,
-                                                                 const float* __restrict__ dstd, const float* __restrict__ bmask,
-                                                                 const float* __restrict__ var_std, const float* __restrict__ row_weight,
-                                                                 float scale, float* __restrict__ d_delta, float* __restrict__ d_prev,
-                                                                 long total, int nodes, int width) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* lc = reinterpret_cast<float2*>(smem);
-    stage_loss_consts<KIND>(var_std, width, lc);
-    const float g = scale * gloss[0];
+template <typename TERM>
+__global__ __launch_bounds__(256) void step_tail_bwd_kernel(const float* __restrict__ g_pred, const float* __restrict__ gloss,
+                                                            const float* __restrict__ pred, const float* __restrict__ target,
+                                                            const float* __restrict__ dstd, const float* __restrict__ bmask,
+                                                            const float* __restrict__ consts, const float* __restrict__ row_weight,
+                                                            float scale, float* __restrict__ d_delta, float* __restrict__ d_prev,
+                                                            long total, int nodes, int width) {
+    const TERM term(consts, width);
+    const float g = TERM::bwd_factor(scale, gloss[0]);
     const bool small = total < (1L << 31);
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         long r;
@@ -3702,7 +3645,7 @@ __global__ __launch_bounds__(256) void step_tail_loss_bwd_kernel(const float* __
         const int f = (int)(e - r * width);
         const float w = row_weight[n];
         float G = g_pred != nullptr ? g_pred[e] : 0.f;
-        if (w != 0.f) G += g * w * loss_dpred<KIND>(pred[e] - target[e], lc[f].x);
+        if (w != 0.f) G += term.dpred(g, w, pred[e] - target[e], f);
         G *= 1.f - bmask[n];
         if (d_prev != nullptr) d_prev[e] = G;
         if (d_delta != nullptr) d_delta[e] = dstd != nullptr ? G * dstd[f] : G;
@@ -3831,6 +3774,7 @@ __global__ __launch_bounds__(256) void eval_partials_kernel(const nlam_eval_t p,
     }
 }
 
+#if NLAM_IN_TU(1)
 // the chunks of one (batch, step) per workgroup into the requested outputs: lane -> column of the partials, the four waves
 // split the chunks (eight loads in flight each), combined in wave order (fixed summation order: deterministic)
 __global__ __launch_bounds__(256) void eval_finish_kernel(const nlam_eval_t p, int nchunks) {
@@ -3861,9 +3805,9 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const nlam_eval_t p, i
     }
 }
 
-// row-wise concatenation (nlam_concat): a workgroup owns 64 consecutive rows; every source's 64 x w_k block is one
-// contiguous span in memory (read coalesced into the LDS row image), and so is the 64 x wtot output block
-constexpr int kCatRows = 64;
+#endif
+
+#if NLAM_IN_TU(5)   // window_batch, window_batch_ens
 // nlam_window_batch: blockIdx.z = sample of the batch, blockIdx.y = row: 0 .. 1 + ar_steps -> one (nodes x d_state) block
 // of the state series (a contiguous copy), then ar_steps rows of windowed forcing (a (window x d_forcing) ->
 // (d_forcing x window) transpose per node: consecutive lanes write consecutive floats, their reads walk `window`
@@ -4060,6 +4004,12 @@ __global__ __launch_bounds__(256) void window_batch_ens_kernel(const nlam_window
     }
 }
 
+#endif
+
+#if NLAM_IN_TU(1)   // concat, wmse_bwd, adamw_prep, adamw
+// row-wise concatenation (nlam_concat): a workgroup owns 64 consecutive rows; every source's 64 x w_k block is one
+// contiguous span in memory (read coalesced into the LDS row image), and so is the 64 x wtot output block
+constexpr int kCatRows = 64;
 __global__ __launch_bounds__(256) void concat_kernel(const nlam_cat_t p, int wtot) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const long ntile = ((long)p.nodes + kCatRows - 1) / kCatRows;
@@ -4130,6 +4080,7 @@ __global__ void adamw_kernel(float* param, const float* grad, float* m, float* v
         param[idx] = pv - (lr / bc1) * (mi / denom);
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // node-level products of the factorised edge MLP (nlam_linear):
@@ -4704,6 +4655,7 @@ __device__ __forceinline__ void pack_piece(const nlam_pack_job_t& j, const PackS
     else pack_item_store<1>(dst, it);
 }
 
+#if NLAM_IN_TU(1)
 __global__ __launch_bounds__(256) void mlp_pack_kernel(const nlam_pack_job_t* jobs) {
     const nlam_pack_job_t j = jobs[blockIdx.y];
     const PackShape sh = pack_shape(j);
@@ -4712,6 +4664,7 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(const nlam_pack_job_t* jo
     const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x), nthr = (int)(gridDim.x * blockDim.x);
     for (int idx = tid; idx < 512; idx += nthr) pack_piece(j, sh, (int)blockIdx.z, idx);
 }
+#endif
 
 #include "nlam_wide.inc"
 #include "nlam_wbf.inc"
@@ -4884,6 +4837,7 @@ int wide_grid(long total_tiles, size_t lds, int nwv) {
     return (int)(g < 1 ? 1 : g);
 }
 
+#if NLAM_IN_TU(3)   // with pack_a_kernel
 void launch_pack(const pack_jobs_t& jobs, hipStream_t stream) {
     long most = 0;
     for (int k = 0; k < jobs.njobs; ++k) {
@@ -4896,6 +4850,7 @@ void launch_pack(const pack_jobs_t& jobs, hipStream_t stream) {
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(pack_a_kernel, dim3((int)blocks, jobs.njobs), dim3(256), 0, stream, jobs);
 }
+#endif
 
 #if NLAM_IN_TU(4)   // naming pack_bf_kernel<> emits it: in the slice of its callers only
 // the split-bf16 pack of build_fwd_wbf_jobs / build_bwd_wbf_jobs (`most`: lane items of their largest job)
@@ -5130,6 +5085,7 @@ void build_bwd_wide_jobs(const nlam_mlp_bwd_t* p, pack_jobs_t& jobs) {
 // by ONE launch per step (nlam_pack_records) instead of a pack launch in front of each of its forward / backward launches
 static_assert(sizeof(pack_job_t) <= 64 && sizeof(packbf_job_t) <= 64, "pack records are 64 bytes");
 
+#if NLAM_IN_TU(1)
 __global__ void pack_a_table_kernel(const nlam_pack_rec_t* recs) {
     const pack_job_t jb = *reinterpret_cast<const pack_job_t*>(recs + blockIdx.y);
     const int ng = round_up((jb.Kw + 7) >> 3, 4);
@@ -5150,6 +5106,7 @@ __global__ void pack_a_table_kernel(const nlam_pack_rec_t* recs) {
         *reinterpret_cast<f32x4*>(&jb.dst[(((size_t)mb * jb.T + jb.t0 + t) * 64 + lane) * 4]) = v;
     }
 }
+#endif
 
 template <int NS>
 __global__ void pack_bf_table_kernel(const nlam_pack_rec_t* recs) {
@@ -6433,13 +6390,14 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
 
 #if NLAM_IN_TU(1)
 namespace {
-// nlam_loss_fwd / _bwd and nlam_step_tail_loss_fwd / _bwd: the NLAM_LOSS_* kind as a template argument (arguments validated)
+// nlam_loss_fwd / _bwd and the four nlam_step_tail_* entry points: the NLAM_LOSS_* kind as a template argument (arguments validated)
 bool loss_kind_valid(int32_t kind) { return kind >= NLAM_LOSS_MSE && kind <= NLAM_LOSS_CRPS_GAUSS; }
 bool loss_reads_std(int32_t kind) { return kind != NLAM_LOSS_MSE && kind != NLAM_LOSS_MAE; }
 
-long loss_bwd_blocks(long total) {
+// workgroups of 256 threads for a grid-stride pass over total elements, at most cap of them
+int elementwise_blocks(long total, long cap) {
     const long blocks = (total + 255) / 256;
-    return blocks > 2048 ? 2048 : blocks;
+    return (int)(blocks > cap ? cap : blocks);
 }
 
 template <int KIND>
@@ -6450,9 +6408,9 @@ int32_t loss_launch(const nlam_loss_t& p, bool bwd, hipStream_t stream) {
         if (per_entry) hipLaunchKernelGGL((loss_fwd_kernel<KIND, true>), dim3(p.nparts), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((loss_fwd_kernel<KIND, false>), dim3(p.nparts), dim3(256), lds, stream, p);
     } else {
-        const long blocks = loss_bwd_blocks((long)p.rows * p.nvars);
-        if (per_entry) hipLaunchKernelGGL((loss_bwd_kernel<KIND, true>), dim3((int)blocks), dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((loss_bwd_kernel<KIND, false>), dim3((int)blocks), dim3(256), lds, stream, p);
+        const int blocks = elementwise_blocks((long)p.rows * p.nvars, 2048);
+        if (per_entry) hipLaunchKernelGGL((loss_bwd_kernel<KIND, true>), dim3(blocks), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((loss_bwd_kernel<KIND, false>), dim3(blocks), dim3(256), lds, stream, p);
     }
     return (int32_t)hipGetLastError();
 }
@@ -6478,22 +6436,57 @@ int32_t loss_check(const nlam_loss_t* p) {
     return 0;
 }
 
+// nlam_step_tail_fwd / _bwd (kind = kInvVarTerm, consts = inv_var) and nlam_step_tail_loss_fwd / _bwd (a valid NLAM_LOSS_* kind,
+// consts = var_std, NULL where the kind reads no std) share one check and one launch per direction.  Only the kinds ask for whole
+// (nodes, width) blocks and a width that fits their LDS table.  pick_term hands f the kind k of StepTailTerm<k>.
+constexpr int32_t kInvVarTerm = 0;   // no NLAM_LOSS_* kind has this value (nlam_step_tail_loss_* reject it as a kind)
+static_assert(kInvVarTerm < NLAM_LOSS_MSE, "the inv_var term shares pick<>'s value space with the NLAM_LOSS_* kinds");
 template <int KIND>
-void step_tail_loss_fwd_launch(const float* delta, const float* prev, const float* truth, const float* target, const float* dstd,
-                               const float* dmean, const float* bmask, const float* var_std, const float* row_weight, float scale,
-                               float* pred, float* partials, int32_t nparts, long total, int32_t nodes, int32_t width,
-                               hipStream_t stream) {
-    hipLaunchKernelGGL((step_tail_loss_fwd_kernel<KIND>), dim3(nparts), dim3(256), (size_t)width * sizeof(float2), stream, delta,
-                       prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, total, nodes, width);
+using StepTailTerm = std::conditional_t<KIND == kInvVarTerm, InvVarTerm, KindTerm<KIND>>;
+
+template <typename F>
+int32_t pick_term(int32_t kind, F&& f) {
+    return pick<kInvVarTerm, NLAM_LOSS_MSE, NLAM_LOSS_MAE, NLAM_LOSS_WMSE, NLAM_LOSS_WMAE, NLAM_LOSS_NLL, NLAM_LOSS_CRPS_GAUSS>(kind, f);
 }
 
-template <int KIND>
-void step_tail_loss_bwd_launch(const float* g_pred, const float* gloss, const float* pred, const float* target, const float* dstd,
-                               const float* bmask, const float* var_std, const float* row_weight, float scale, float* d_delta,
-                               float* d_prev, long total, int32_t nodes, int32_t width, hipStream_t stream) {
-    hipLaunchKernelGGL((step_tail_loss_bwd_kernel<KIND>), dim3((int)loss_bwd_blocks(total)), dim3(256), (size_t)width * sizeof(float2),
-                       stream, g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, total, nodes,
-                       width);
+int32_t step_tail_sizes_check(int32_t kind, bool consts_given, int64_t rows, int32_t nodes, int32_t width) {
+    const bool kinds = kind != kInvVarTerm;
+    if (!consts_given && (!kinds || loss_reads_std(kind))) return NLAM_EINVAL;
+    if (rows < 1 || nodes < 1 || width < 1 || (kinds && rows % nodes != 0)) return NLAM_EINVAL;
+    return kinds && width > NLAM_LOSS_MAX_VARS ? NLAM_EUNSUP : 0;
+}
+
+int32_t step_tail_fwd(int32_t kind, const float* delta, const float* prev, const float* truth, const float* target, const float* dstd,
+                      const float* dmean, const float* bmask, const float* consts, const float* row_weight, float scale, float* pred,
+                      float* partials, int32_t nparts, int64_t rows, int32_t nodes, int32_t width, void* hip_stream) {
+    if (delta == nullptr || prev == nullptr || truth == nullptr || target == nullptr || bmask == nullptr || row_weight == nullptr ||
+        pred == nullptr || partials == nullptr || nparts < 1)
+        return NLAM_EINVAL;
+    if (const int32_t rc = step_tail_sizes_check(kind, consts != nullptr, rows, nodes, width)) return rc;
+    return pick_term(kind, [&](auto k) {
+        using TERM = StepTailTerm<k>;
+        hipLaunchKernelGGL(step_tail_fwd_kernel<TERM>, dim3(nparts), dim3(256), TERM::lds_bytes(width), (hipStream_t)hip_stream, delta,
+                           prev, truth, target, dstd, dmean, bmask, consts, row_weight, scale, pred, partials, (long)rows * width, nodes,
+                           width);
+        return (int32_t)hipGetLastError();
+    });
+}
+
+int32_t step_tail_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target, const float* dstd,
+                      const float* bmask, const float* consts, const float* row_weight, float scale, float* d_delta, float* d_prev,
+                      int64_t rows, int32_t nodes, int32_t width, void* hip_stream) {
+    if (gloss == nullptr || pred == nullptr || target == nullptr || bmask == nullptr || row_weight == nullptr ||
+        (d_delta == nullptr && d_prev == nullptr))
+        return NLAM_EINVAL;
+    if (const int32_t rc = step_tail_sizes_check(kind, consts != nullptr, rows, nodes, width)) return rc;
+    const long total = (long)rows * width;
+    return pick_term(kind, [&](auto k) {
+        using TERM = StepTailTerm<k>;
+        hipLaunchKernelGGL(step_tail_bwd_kernel<TERM>, dim3(elementwise_blocks(total, 2048)), dim3(256), TERM::lds_bytes(width),
+                           (hipStream_t)hip_stream, g_pred, gloss, pred, target, dstd, bmask, consts, row_weight, scale, d_delta, d_prev,
+                           total, nodes, width);
+        return (int32_t)hipGetLastError();
+    });
 }
 
 // nlam_eval_metrics: the chunks of a (batch, step) and the argument checks (before any launch)
@@ -6597,21 +6590,17 @@ static int32_t segment_sum_launch(const float* in, int64_t in_bstride, const int
     const long rows = in_bstride > 0 ? in_bstride / width : 0;
     if ((width & 3) == 0 && w4 <= 32 && 64 % w4 == 0 && rows >= 16L * nseg) {
         const int S = w4 <= 16 ? 4 : 2;
-        const long tot = (long)batch * nseg * S * w4;
-        long blk = (tot + 255) / 256;
-        if (blk > 256 * 16) blk = 256 * 16;
+        const int blk = elementwise_blocks((long)batch * nseg * S * w4, 256 * 16);
         if (S == 4)
-            hipLaunchKernelGGL(segment_sum_split_kernel<4>, dim3((int)blk), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
+            hipLaunchKernelGGL(segment_sum_split_kernel<4>, dim3(blk), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
                                order, scale, out, nseg, width, batch, accumulate, extra);
         else
-            hipLaunchKernelGGL(segment_sum_split_kernel<2>, dim3((int)blk), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
+            hipLaunchKernelGGL(segment_sum_split_kernel<2>, dim3(blk), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
                                order, scale, out, nseg, width, batch, accumulate, extra);
         return (int32_t)hipGetLastError();
     }
-    const long total = (long)batch * nseg * ((width + 3) / 4);
-    long blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(segment_sum_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride,
+    const int blocks = elementwise_blocks((long)batch * nseg * ((width + 3) / 4), 256 * 16);
+    hipLaunchKernelGGL(segment_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride,
                        ptr, order, scale, out, nseg, width, batch, accumulate, extra);
     return (int32_t)hipGetLastError();
 }
@@ -6628,10 +6617,8 @@ int32_t nlam_segment_sum_bf16(const uint16_t* in, int64_t in_bstride, const int3
     if (in == nullptr || ptr == nullptr || out == nullptr || nseg < 0 || width < 8 || batch < 1) return NLAM_EINVAL;
     if (width % 8 != 0) return NLAM_EUNSUP;
     if (nseg == 0) return 0;
-    const long total = (long)batch * nseg * (width / 8);
-    long blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(segment_sum_bf16_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
+    const int blocks = elementwise_blocks((long)batch * nseg * (width / 8), 256 * 16);
+    hipLaunchKernelGGL(segment_sum_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
                        order, scale, out, nseg, width, batch);
     return (int32_t)hipGetLastError();
 }
@@ -6707,10 +6694,8 @@ int32_t nlam_wmse_bwd(const float* pred, const float* target, const float* inv_v
         return NLAM_EINVAL;
     if (rows < 1 || nodes < 1 || nvars < 1) return NLAM_EINVAL;
     const long total = (long)rows * nvars;
-    long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wmse_bwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)hip_stream, pred, target, inv_var, row_weight,
-                       gscalar, total, nodes, nvars, scale, dpred);
+    hipLaunchKernelGGL(wmse_bwd_kernel, dim3(elementwise_blocks(total, 2048)), dim3(256), 0, (hipStream_t)hip_stream, pred, target,
+                       inv_var, row_weight, gscalar, total, nodes, nvars, scale, dpred);
     return (int32_t)hipGetLastError();
 }
 
@@ -6721,10 +6706,8 @@ int32_t nlam_affine_mix(const float* x, const float* a, const float* y, const fl
     if ((x == nullptr) != (a == nullptr) || (z == nullptr) != (s == nullptr)) return NLAM_EINVAL;
     if (x == nullptr && y == nullptr && z == nullptr && m == nullptr) return NLAM_EINVAL;
     const long total = (long)rows * width;
-    long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(affine_mix_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)hip_stream, x, a, y, c, z, s, m, out, total,
-                       nodes, width);
+    hipLaunchKernelGGL(affine_mix_kernel, dim3(elementwise_blocks(total, 4096)), dim3(256), 0, (hipStream_t)hip_stream, x, a, y, c, z,
+                       s, m, out, total, nodes, width);
     return (int32_t)hipGetLastError();
 }
 
@@ -6733,28 +6716,16 @@ int32_t nlam_step_tail_fwd(const float* delta, const float* prev, const float* t
                            float* pred, float* partials, int32_t nparts, int64_t rows, int32_t nodes, int32_t width,
                            void* hip_stream) {
     NLAM_RANGE("nlam_step_tail_fwd");
-    if (delta == nullptr || prev == nullptr || truth == nullptr || target == nullptr || bmask == nullptr || inv_var == nullptr ||
-        row_weight == nullptr || pred == nullptr || partials == nullptr)
-        return NLAM_EINVAL;
-    if (rows < 1 || nodes < 1 || width < 1 || nparts < 1) return NLAM_EINVAL;
-    hipLaunchKernelGGL(step_tail_fwd_kernel, dim3(nparts), dim3(256), 0, (hipStream_t)hip_stream, delta, prev, truth, target, dstd,
-                       dmean, bmask, inv_var, row_weight, scale, pred, partials, (long)rows * width, nodes, width);
-    return (int32_t)hipGetLastError();
+    return step_tail_fwd(kInvVarTerm, delta, prev, truth, target, dstd, dmean, bmask, inv_var, row_weight, scale, pred, partials, nparts,
+                         rows, nodes, width, hip_stream);
 }
 
 int32_t nlam_step_tail_bwd(const float* g_pred, const float* gloss, const float* pred, const float* target, const float* dstd,
                            const float* bmask, const float* inv_var, const float* row_weight, float scale, float* d_delta,
                            float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream) {
     NLAM_RANGE("nlam_step_tail_bwd");
-    if (gloss == nullptr || pred == nullptr || target == nullptr || bmask == nullptr || inv_var == nullptr || row_weight == nullptr)
-        return NLAM_EINVAL;
-    if ((d_delta == nullptr && d_prev == nullptr) || rows < 1 || nodes < 1 || width < 1) return NLAM_EINVAL;
-    const long total = (long)rows * width;
-    long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(step_tail_bwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)hip_stream, g_pred, gloss, pred, target,
-                       dstd, bmask, inv_var, row_weight, scale, d_delta, d_prev, total, nodes, width);
-    return (int32_t)hipGetLastError();
+    return step_tail_bwd(kInvVarTerm, g_pred, gloss, pred, target, dstd, bmask, inv_var, row_weight, scale, d_delta, d_prev, rows, nodes,
+                         width, hip_stream);
 }
 
 int32_t nlam_concat(const nlam_cat_t* p, void* hip_stream) {
@@ -6784,9 +6755,8 @@ int32_t nlam_standardize(const nlam_std_jobs_t* jobs, void* hip_stream) {
         if (j.rows * j.width > most) most = j.rows * j.width;
     }
     if (most == 0) return 0;
-    long blocks = (most + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(standardize_kernel, dim3((int)blocks, jobs->njobs), dim3(256), 0, (hipStream_t)hip_stream, *jobs);
+    hipLaunchKernelGGL(standardize_kernel, dim3(elementwise_blocks(most, 2048), jobs->njobs), dim3(256), 0, (hipStream_t)hip_stream,
+                       *jobs);
     return (int32_t)hipGetLastError();
 }
 
@@ -6799,9 +6769,7 @@ int32_t nlam_adamw_step(float* param, const float* grad, float* exp_avg, float* 
     if (n == 0) return 0;
     const float bc1 = 1.f - powf(beta1, (float)step_count);
     const float bc2 = 1.f - powf(beta2, (float)step_count);
-    long blocks = (n + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(adamw_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)hip_stream, param, grad, exp_avg,
+    hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_blocks(n, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, param, grad, exp_avg,
                        exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale, (const float*)nullptr);
     return (int32_t)hipGetLastError();
 }
@@ -6816,10 +6784,8 @@ int32_t nlam_adamw_step_resident(float* param, const float* grad, float* exp_avg
     hipStream_t stream = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(adamw_prep_kernel, dim3(1), dim3(64), 0, stream, step_count_dev, bias_corr_dev, beta1, beta2);
     if (n == 0) return (int32_t)hipGetLastError();
-    long blocks = (n + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(adamw_kernel, dim3((int)blocks), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, (long)n, lr, beta1,
-                       beta2, eps, weight_decay, 1.f, 1.f, grad_scale, (const float*)bias_corr_dev);
+    hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_blocks(n, 256 * 8)), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq,
+                       (long)n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale, (const float*)bias_corr_dev);
     return (int32_t)hipGetLastError();
 }
 
@@ -6843,32 +6809,18 @@ int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* p
                                 const float* row_weight, float scale, float* pred, float* partials, int32_t nparts, int64_t rows,
                                 int32_t nodes, int32_t width, void* hip_stream) {
     NLAM_RANGE("nlam_step_tail_loss_fwd");
-    if (!loss_kind_valid(kind) || delta == nullptr || prev == nullptr || truth == nullptr || target == nullptr || bmask == nullptr ||
-        row_weight == nullptr || pred == nullptr || partials == nullptr || (loss_reads_std(kind) && var_std == nullptr))
-        return NLAM_EINVAL;
-    if (rows < 1 || nodes < 1 || width < 1 || nparts < 1 || rows % nodes != 0) return NLAM_EINVAL;
-    if (width > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
-    return pick_loss(kind, [&](auto k) {
-        step_tail_loss_fwd_launch<k>(delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, nparts,
-                                     (long)rows * width, nodes, width, (hipStream_t)hip_stream);
-        return (int32_t)hipGetLastError();
-    });
+    if (!loss_kind_valid(kind)) return NLAM_EINVAL;
+    return step_tail_fwd(kind, delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale, pred, partials, nparts, rows,
+                         nodes, width, hip_stream);
 }
 
 int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target,
                                 const float* dstd, const float* bmask, const float* var_std, const float* row_weight, float scale,
                                 float* d_delta, float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream) {
     NLAM_RANGE("nlam_step_tail_loss_bwd");
-    if (!loss_kind_valid(kind) || gloss == nullptr || pred == nullptr || target == nullptr || bmask == nullptr ||
-        row_weight == nullptr || (loss_reads_std(kind) && var_std == nullptr))
-        return NLAM_EINVAL;
-    if ((d_delta == nullptr && d_prev == nullptr) || rows < 1 || nodes < 1 || width < 1 || rows % nodes != 0) return NLAM_EINVAL;
-    if (width > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
-    return pick_loss(kind, [&](auto k) {
-        step_tail_loss_bwd_launch<k>(g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev,
-                                     (long)rows * width, nodes, width, (hipStream_t)hip_stream);
-        return (int32_t)hipGetLastError();
-    });
+    if (!loss_kind_valid(kind)) return NLAM_EINVAL;
+    return step_tail_bwd(kind, g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, rows, nodes, width,
+                         hip_stream);
 }
 
 int32_t nlam_eval_metrics(const nlam_eval_t* p, void* hip_stream) {

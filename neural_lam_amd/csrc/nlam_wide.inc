@@ -37,6 +37,7 @@ struct pack_jobs_t {
     int njobs;
 };
 
+#if NLAM_IN_TU(3)   // no template: emitted where it is defined, so only in the slice of launch_pack
 // dst[((mb * T + t0 + t) * 64 + lane) * 4 + c] = A[mb*32 + (lane & 31)][8t + 4(lane >> 5) + c]
 // for t < round_up(ceil(Kw / 8), 4); zero outside M x Kw.
 __global__ void pack_a_kernel(const pack_jobs_t jobs) {
@@ -60,6 +61,7 @@ __global__ void pack_a_kernel(const pack_jobs_t jobs) {
         *reinterpret_cast<f32x4*>(&jb.dst[(((size_t)mb * jb.T + jb.t0 + t) * 64 + lane) * 4]) = v;
     }
 }
+#endif
 
 template <typename P>
 __device__ __forceinline__ nlam_src_t get_src(const P& p, int s) {

@@ -584,8 +584,8 @@ class ARForecaster(nn.Module):
         ``scale * sum_t sum_n,f row_weight * inv_var * (pred - target)^2`` as a third value, with each step's state
         update + boundary overwrite + loss term fused into one pass (ops.StepTailFunction) when the predictor's tail is
         the plain rescale (no clamping / predicted std).  ``loss_spec = (target_states, var_std (F,), row_weight (N,), scale,
-        kind)`` with a ``_lib.LOSS_*`` kind: the same for that loss with the per-variable std ``var_std``
-        (ops.StepTailLossFunction); the third value is None where the tail cannot be fused."""
+        kind)`` with a ``_lib.LOSS_*`` kind: the same for that loss with the per-variable std ``var_std`` (the same
+        Function, ``kind`` given); the third value is None where the tail cannot be fused."""
         prev_prev_state, prev_state = init_states[:, 0], init_states[:, 1]
         preds, stds = [], []
         cache = self.predictor.static_cache() if hasattr(self.predictor, "static_cache") else contextlib.nullcontext()
@@ -595,19 +595,13 @@ class ARForecaster(nn.Module):
         with cache:
             for i in range(forcing_features.shape[1]):
                 if fused_tail:
-                    from .ops import StepTailFunction, StepTailLossFunction
+                    from .ops import StepTailFunction
 
                     delta, _ = self.predictor(prev_state, prev_prev_state, forcing_features[:, i], raw_delta=True)
-                    if len(loss_spec) == 4:
-                        target, inv_var, row_weight, scale = loss_spec
-                        new_state, loss_t = StepTailFunction.apply(
-                            delta.float(), prev_state, boundary_states[:, i], target[:, i], self.predictor.diff_std,
-                            self.predictor.diff_mean, self.boundary_mask.reshape(-1), inv_var, row_weight, scale)
-                    else:
-                        target, var_std, row_weight, scale, kind = loss_spec
-                        new_state, loss_t = StepTailLossFunction.apply(
-                            delta.float(), prev_state, boundary_states[:, i], target[:, i], self.predictor.diff_std,
-                            self.predictor.diff_mean, self.boundary_mask.reshape(-1), var_std, row_weight, scale, kind)
+                    target, consts, row_weight, scale, kind = loss_spec if len(loss_spec) == 5 else (*loss_spec, None)
+                    new_state, loss_t = StepTailFunction.apply(
+                        delta.float(), prev_state, boundary_states[:, i], target[:, i], self.predictor.diff_std,
+                        self.predictor.diff_mean, self.boundary_mask.reshape(-1), consts, row_weight, scale, kind)
                     preds.append(new_state)
                     losses.append(loss_t)
                     prev_prev_state, prev_state = prev_state, new_state
@@ -657,7 +651,7 @@ def wmse(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
 
 
 # The other metrics of metrics.DEFINED_METRICS as plain torch formulas, for evaluation code; training runs them on
-# ops.LossFunction / ops.StepTailLossFunction (ForecasterStep(loss=...)).
+# ops.LossFunction / ops.StepTailFunction (ForecasterStep(loss=...)).
 def mse(pred, target, pred_std, mask=None, average_grid=True, sum_vars=True):
     """metrics.py:140-182: wmse with the std replaced by ones."""
     return wmse(pred, target, torch.ones_like(pred_std), mask, average_grid, sum_vars)
@@ -740,7 +734,9 @@ class ForecasterStep(nn.Module):
         if name not in LOSS_KINDS:
             raise ValueError(f"unknown loss {loss!r}: expected one of {', '.join(LOSS_KINDS)}")
         self.loss_name, self.loss_kind = name, LOSS_KINDS[name]
-        self.default_loss = self.loss_kind == LOSS_WMSE   # wmse keeps its own kernels (StepTailFunction, WmseLossFunction)
+        # wmse takes inv_var = 1 / std^2 where the kinds take the std: StepTailFunction with kind=None (the same kernels on another
+        # loss term), and WmseLossFunction on the unfused route
+        self.default_loss = self.loss_kind == LOSS_WMSE
         self.forecaster = forecaster
         self.standardize_inputs = bool(standardize)
         bm = torch.tensor(datastore.boundary_mask.values, dtype=torch.float32)
@@ -828,7 +824,7 @@ class ForecasterStep(nn.Module):
         return prediction, torch.mean(time_step_loss)
 
     def _forward_loss(self, init_states, target_states, forcing):
-        """Every ``loss`` but wmse: the fused step tail (ops.StepTailLossFunction) where the predictor can return its raw delta,
+        """Every ``loss`` but wmse: the fused step tail (ops.StepTailFunction with the kind) where the predictor can return its raw delta,
         the one-pass ops.LossFunction on the rollout otherwise (clamped or predicted-std models)."""
         from ._lib import LOSS_MAE, LOSS_MSE
         from .ops import LossFunction

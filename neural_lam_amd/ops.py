@@ -2190,6 +2190,24 @@ class NodeLinearPairFunction(torch.autograd.Function):
         return dx, dW, None, None, None
 
 
+def _cont(t):
+    return None if t is None else t.contiguous()
+
+
+_LOSS_NPARTS = 512   # workgroups (= partial sums) of a loss pass
+
+
+def _scalar_from_partials(device, launch, what):
+    """The scalar a loss pass leaves behind: ``launch(partials address, nparts)`` writes one partial sum per workgroup,
+    nlam_reduce_partials adds them in a fixed order."""
+    lib = L.load()
+    partials = torch.empty((_LOSS_NPARTS,), device=device, dtype=torch.float32)
+    L.check(launch(_ptr(partials), _LOSS_NPARTS), what)
+    out = torch.empty((), device=device, dtype=torch.float32)
+    L.check(lib.nlam_reduce_partials(_ptr(partials), _LOSS_NPARTS, 1, 1, _ptr(out), 0, _stream()), "nlam_reduce_partials")
+    return out
+
+
 class WmseLossFunction(torch.autograd.Function):
     """``mean_t mean_b wmse(pred, target, per_var_std, interior mask)`` as one pass (nlam_wmse_fwd / _bwd).
 
@@ -2202,13 +2220,10 @@ class WmseLossFunction(torch.autograd.Function):
         _require_gpu(pred, target, inv_var, row_weight)
         B, T, N, V = pred.shape
         predc, targc = pred.contiguous(), target.contiguous()
-        nparts = 512
-        partials = torch.empty((nparts,), device=pred.device, dtype=torch.float32)
         scale = 1.0 / (B * T)
-        L.check(lib.nlam_wmse_fwd(_ptr(predc), _ptr(targc), _ptr(inv_var), _ptr(row_weight), B * T * N, N, V, scale,
-                                  _ptr(partials), nparts, _stream()), "nlam_wmse_fwd")
-        out = torch.empty((), device=pred.device, dtype=torch.float32)
-        L.check(lib.nlam_reduce_partials(_ptr(partials), nparts, 1, 1, _ptr(out), 0, _stream()), "nlam_reduce_partials")
+        out = _scalar_from_partials(pred.device, lambda partials, nparts: lib.nlam_wmse_fwd(
+            _ptr(predc), _ptr(targc), _ptr(inv_var), _ptr(row_weight), B * T * N, N, V, scale, partials, nparts, _stream()),
+            "nlam_wmse_fwd")
         ctx.save_for_backward(predc, targc, inv_var, row_weight)
         ctx.scale = scale
         return out
@@ -2250,8 +2265,7 @@ class AffineMixFunction(torch.autograd.Function):
         like = y if y is not None else z
         tens = [t for t in (x, a, y, c, z, s, m) if t is not None]
         _require_gpu(*tens)
-        cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
-        x, a, y, c, z, s, m = map(cont, (x, a, y, c, z, s, m))
+        x, a, y, c, z, s, m = map(_cont, (x, a, y, c, z, s, m))
         ctx.save_for_backward(c, s)
         return _affine_mix(x, a, y, c, z, s, m, like)
 
@@ -2268,56 +2282,58 @@ class AffineMixFunction(torch.autograd.Function):
 
 
 class StepTailFunction(torch.autograd.Function):
-    """The elementwise tail of one AR step in one pass each way (nlam_step_tail_fwd / _bwd):
+    """The elementwise tail of one AR step in one pass each way:
 
         new = prev + delta * diff_std + diff_mean ; pred = bmask * truth + (1 - bmask) * new ;
-        loss_t = scale * sum_n,f row_weight[n] * inv_var[f] * (pred - target)^2
+        loss_t = scale * sum_n,f row_weight[n] * entry(pred - target; consts[f])
 
-    i.e. ``step_predictors/graph/base.py:331-343`` + ``forecasters/autoregressive.py:128-131`` + this step's term of
-    ``metrics.wmse`` / ``module.py:463-510`` (three elementwise launches + the loss pass in the reference's formulation,
-    and as many again in backward).  forward(delta, prev, truth, target, dstd, dmean, bmask (N,), inv_var (F,),
-    row_weight (N,), scale) -> (pred (B, N, F), loss_t scalar)."""
-
-    NPARTS = 512
+    i.e. ``step_predictors/graph/base.py:331-343`` + ``forecasters/autoregressive.py:128-131`` + this step's term of the
+    loss (``metrics.py`` / ``module.py:463-510``; three elementwise launches + the loss pass in the reference's formulation,
+    and as many again in backward).  ``kind=None`` is the default wmse with ``consts = inv_var = 1 / std^2`` handed in
+    (nlam_step_tail_fwd / _bwd); a ``_lib.LOSS_*`` kind takes ``consts = var_std``, the per-variable std, None for mse /
+    mae (nlam_step_tail_loss_fwd / _bwd).  forward(delta, prev, truth, target, dstd, dmean, bmask (N,), consts (F,),
+    row_weight (N,), scale, kind) -> (pred (B, N, F), loss_t scalar)."""
 
     @staticmethod
-    def forward(ctx, delta, prev, truth, target, dstd, dmean, bmask, inv_var, row_weight, scale: float):
-        lib = L.load()
-        _require_gpu(delta, prev, truth, target, dstd, dmean, bmask, inv_var, row_weight)
+    def _entry(lib, name, kind):
+        """(entry point of this kind, its name): the _loss_ pair takes the kind as its first argument"""
+        if kind is None:
+            return getattr(lib, f"nlam_step_tail_{name}"), f"nlam_step_tail_{name}"
+        f = getattr(lib, f"nlam_step_tail_loss_{name}")
+        return (lambda *args: f(kind, *args)), f"nlam_step_tail_loss_{name}"
+
+    @staticmethod
+    def forward(ctx, delta, prev, truth, target, dstd, dmean, bmask, consts, row_weight, scale: float, kind=None):
+        _require_gpu(delta, prev, truth, target, dstd, dmean, bmask, consts, row_weight)
         B, N, F = delta.shape
-        cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
-        delta, prev, truth, target = map(cont, (delta, prev, truth, target))
-        dev = delta.device
-        pred = torch.empty((B, N, F), device=dev, dtype=torch.float32)
-        partials = torch.empty((StepTailFunction.NPARTS,), device=dev, dtype=torch.float32)
-        L.check(lib.nlam_step_tail_fwd(_ptr(delta), _ptr(prev), _ptr(truth), _ptr(target), _ptr(dstd), _ptr(dmean), _ptr(bmask),
-                                       _ptr(inv_var), _ptr(row_weight), scale, _ptr(pred), _ptr(partials), StepTailFunction.NPARTS,
-                                       B * N, N, F, _stream()), "nlam_step_tail_fwd")
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        L.check(lib.nlam_reduce_partials(_ptr(partials), StepTailFunction.NPARTS, 1, 1, _ptr(loss), 0, _stream()), "nlam_reduce_partials")
-        ctx.save_for_backward(pred, target, dstd, bmask, inv_var, row_weight)
-        ctx.scale = scale
+        delta, prev, truth, target = map(_cont, (delta, prev, truth, target))
+        pred = torch.empty((B, N, F), device=delta.device, dtype=torch.float32)
+        fwd, what = StepTailFunction._entry(L.load(), "fwd", kind)
+        loss = _scalar_from_partials(delta.device, lambda partials, nparts: fwd(
+            _ptr(delta), _ptr(prev), _ptr(truth), _ptr(target), _ptr(dstd), _ptr(dmean), _ptr(bmask), _ptr(consts), _ptr(row_weight),
+            scale, _ptr(pred), partials, nparts, B * N, N, F, _stream()), what)
+        ctx.save_for_backward(pred, target, dstd, bmask, consts, row_weight)
+        ctx.scale, ctx.kind = scale, kind
         ctx.set_materialize_grads(False)
         return pred, loss
 
     @staticmethod
     def backward(ctx, g_pred, g_loss):
-        lib = L.load()
-        pred, target, dstd, bmask, inv_var, row_weight = ctx.saved_tensors
+        pred, target, dstd, bmask, consts, row_weight = ctx.saved_tensors
         B, N, F = pred.shape
         if g_pred is None and g_loss is None:
-            return (None,) * 10
+            return (None,) * 11
         dev = pred.device
         gl = g_loss.contiguous().to(torch.float32) if g_loss is not None else torch.zeros((), device=dev, dtype=torch.float32)
         gp = g_pred.contiguous() if g_pred is not None else None
         d_delta = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
         d_prev = torch.empty_like(pred) if ctx.needs_input_grad[1] else None
         if d_delta is None and d_prev is None:
-            return (None,) * 10
-        L.check(lib.nlam_step_tail_bwd(_ptr(gp), _ptr(gl), _ptr(pred), _ptr(target), _ptr(dstd), _ptr(bmask), _ptr(inv_var),
-                                       _ptr(row_weight), ctx.scale, _ptr(d_delta), _ptr(d_prev), B * N, N, F, _stream()),
-                "nlam_step_tail_bwd")
-        return d_delta, d_prev, None, None, None, None, None, None, None, None
+            return (None,) * 11
+        bwd, what = StepTailFunction._entry(L.load(), "bwd", ctx.kind)
+        L.check(bwd(_ptr(gp), _ptr(gl), _ptr(pred), _ptr(target), _ptr(dstd), _ptr(bmask), _ptr(consts), _ptr(row_weight), ctx.scale,
+                    _ptr(d_delta), _ptr(d_prev), B * N, N, F, _stream()), what)
+        return d_delta, d_prev, None, None, None, None, None, None, None, None, None
 
 
 class LossFunction(torch.autograd.Function):
@@ -2327,8 +2343,6 @@ class LossFunction(torch.autograd.Function):
 
     forward(pred (B, T, N, V), target, pred_std (B, T, N, V) | None, var_std (V) | None, row_weight (N) = interior / #interior,
     kind) -> scalar.  Gradients: pred, and pred_std when it requires one."""
-
-    NPARTS = 512
 
     @staticmethod
     def _args(pred, target, pred_std, var_std, row_weight, kind, scale):
@@ -2344,15 +2358,15 @@ class LossFunction(torch.autograd.Function):
         lib = L.load()
         _require_gpu(*(t for t in (pred, target, pred_std, var_std, row_weight) if t is not None))
         B, T = pred.shape[0], pred.shape[1]
-        cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
-        pred, target, pred_std = map(cont, (pred, target, pred_std))
+        pred, target, pred_std = map(_cont, (pred, target, pred_std))
         scale = 1.0 / (B * T)
         p = LossFunction._args(pred, target, pred_std, var_std, row_weight, kind, scale)
-        partials = torch.empty((LossFunction.NPARTS,), device=pred.device, dtype=torch.float32)
-        p.partials, p.nparts = _ptr(partials), LossFunction.NPARTS
-        L.check(lib.nlam_loss_fwd(C.byref(p), _stream()), "nlam_loss_fwd")
-        out = torch.empty((), device=pred.device, dtype=torch.float32)
-        L.check(lib.nlam_reduce_partials(_ptr(partials), LossFunction.NPARTS, 1, 1, _ptr(out), 0, _stream()), "nlam_reduce_partials")
+
+        def launch(partials, nparts):
+            p.partials, p.nparts = partials, nparts
+            return lib.nlam_loss_fwd(C.byref(p), _stream())
+
+        out = _scalar_from_partials(pred.device, launch, "nlam_loss_fwd")
         ctx.save_for_backward(pred, target, pred_std, var_std, row_weight)
         ctx.kind, ctx.scale = kind, scale
         return out
@@ -2368,55 +2382,6 @@ class LossFunction(torch.autograd.Function):
         p.gscalar, p.dpred, p.dstd = _ptr(gc), _ptr(dpred), _ptr(dstd)
         L.check(lib.nlam_loss_bwd(C.byref(p), _stream()), "nlam_loss_bwd")
         return dpred, None, dstd, None, None, None
-
-
-class StepTailLossFunction(torch.autograd.Function):
-    """StepTailFunction with the loss term of any ``--loss`` kind (``_lib.LOSS_*``) for a per-variable std
-    (nlam_step_tail_loss_fwd / _bwd): still one pass each way per AR step.
-    forward(delta, prev, truth, target, dstd, dmean, bmask (N,), var_std (F,), row_weight (N,), scale, kind)
-    -> (pred (B, N, F), loss_t scalar)."""
-
-    NPARTS = 512
-
-    @staticmethod
-    def forward(ctx, delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight, scale: float, kind: int):
-        lib = L.load()
-        _require_gpu(*(t for t in (delta, prev, truth, target, dstd, dmean, bmask, var_std, row_weight) if t is not None))
-        B, N, F = delta.shape
-        cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
-        delta, prev, truth, target = map(cont, (delta, prev, truth, target))
-        dev = delta.device
-        pred = torch.empty((B, N, F), device=dev, dtype=torch.float32)
-        partials = torch.empty((StepTailLossFunction.NPARTS,), device=dev, dtype=torch.float32)
-        L.check(lib.nlam_step_tail_loss_fwd(kind, _ptr(delta), _ptr(prev), _ptr(truth), _ptr(target), _ptr(dstd), _ptr(dmean),
-                                            _ptr(bmask), _ptr(var_std), _ptr(row_weight), scale, _ptr(pred), _ptr(partials),
-                                            StepTailLossFunction.NPARTS, B * N, N, F, _stream()), "nlam_step_tail_loss_fwd")
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        L.check(lib.nlam_reduce_partials(_ptr(partials), StepTailLossFunction.NPARTS, 1, 1, _ptr(loss), 0, _stream()),
-                "nlam_reduce_partials")
-        ctx.save_for_backward(pred, target, dstd, bmask, var_std, row_weight)
-        ctx.scale, ctx.kind = scale, kind
-        ctx.set_materialize_grads(False)
-        return pred, loss
-
-    @staticmethod
-    def backward(ctx, g_pred, g_loss):
-        lib = L.load()
-        pred, target, dstd, bmask, var_std, row_weight = ctx.saved_tensors
-        B, N, F = pred.shape
-        if g_pred is None and g_loss is None:
-            return (None,) * 11
-        dev = pred.device
-        gl = g_loss.contiguous().to(torch.float32) if g_loss is not None else torch.zeros((), device=dev, dtype=torch.float32)
-        gp = g_pred.contiguous() if g_pred is not None else None
-        d_delta = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        d_prev = torch.empty_like(pred) if ctx.needs_input_grad[1] else None
-        if d_delta is None and d_prev is None:
-            return (None,) * 11
-        L.check(lib.nlam_step_tail_loss_bwd(ctx.kind, _ptr(gp), _ptr(gl), _ptr(pred), _ptr(target), _ptr(dstd), _ptr(bmask),
-                                            _ptr(var_std), _ptr(row_weight), ctx.scale, _ptr(d_delta), _ptr(d_prev), B * N, N, F,
-                                            _stream()), "nlam_step_tail_loss_bwd")
-        return d_delta, d_prev, None, None, None, None, None, None, None, None, None
 
 
 def eval_metrics(pred, target, pred_std, var_std, interior_weight, kind, map_steps=(), want_mae=False, want_std=False):

@@ -1,7 +1,8 @@
 """The --loss choices of the reference (train_model.py:271-276, metrics.DEFINED_METRICS) on ForecasterStep(loss=...):
 construction, the C-ABI of nlam_loss_* / nlam_step_tail_loss_* without a GPU, the metric formulas of models.py against
 the reference golden (tests/golden/losses.pt, tests/golden/make_golden_losses.py), and on the GPU the kernels, the
-model training step per kind, the fused step tail against the unfused route, and HIP-graph capture."""
+step-tail kernels on every loss term against the float64 formula, the model training step per kind, the fused step tail
+against the unfused route, and HIP-graph capture."""
 import ctypes as C
 import subprocess
 
@@ -97,6 +98,19 @@ def test_loss_entry_points_reject_bad_arguments_without_a_gpu():
         assert call(L.LOSS_NLL, width=L.LOSS_MAX_VARS + 1, rows=4, nodes=4) == -2
     assert fwd(L.LOSS_MSE, nparts=0) == -1 and bwd(L.LOSS_MAE, d_delta=None) == -1
 
+    # nlam_step_tail_fwd / _bwd share those checks (the codes are those of the library before the merge).  They take no kind,
+    # always read inv_var, and accept any rows / width: those two cases of the _loss_ pair would launch here and are not called.
+    def fwd0(inv_var=fake, rows=8, nodes=4, width=3, nparts=1, pred=fake):
+        return lib.nlam_step_tail_fwd(fake, fake, fake, fake, None, None, fake, inv_var, fake, 1.0, pred, fake, nparts, rows, nodes,
+                                      width, None)
+
+    def bwd0(inv_var=fake, rows=8, nodes=4, width=3, d_delta=fake, gloss=fake):
+        return lib.nlam_step_tail_bwd(None, gloss, fake, fake, None, fake, inv_var, fake, 1.0, d_delta, None, rows, nodes, width, None)
+
+    for call in (fwd0, bwd0):
+        assert call(inv_var=None) == -1 and call(width=0) == -1 and call(rows=0) == -1 and call(nodes=0) == -1
+    assert fwd0(nparts=0) == -1 and fwd0(pred=None) == -1 and bwd0(d_delta=None) == -1 and bwd0(gloss=None) == -1
+
 
 def test_loss_struct_matches_c_layout(tmp_path):
     src = tmp_path / "sz.c"
@@ -190,7 +204,7 @@ def test_loss_kernel_matches_reference_golden(dev, golden, misalign):
 @pytest.mark.gpu
 def test_absolute_error_gradient_is_zero_at_ties(dev, golden):
     """sign(0) = 0 (torch.l1_loss): an interior entry with pred == target gets no gradient, in both kernels."""
-    from neural_lam_amd.ops import StepTailLossFunction
+    from neural_lam_amd.ops import StepTailFunction
 
     for case in _cases(golden["ties"]):
         loss, dpred, _ = _run_loss(case, dev)
@@ -208,12 +222,131 @@ def test_absolute_error_gradient_is_zero_at_ties(dev, golden):
     rw = ((1 - bmask) / (1 - bmask).sum()).contiguous()
     for kind in (L.LOSS_MAE, L.LOSS_WMAE):
         delta.grad = None
-        pred, loss = StepTailLossFunction.apply(delta, prev, torch.zeros_like(prev), target, None, None, bmask,
-                                                torch.rand(F, device=dev) + 0.5, rw, 1.0 / B, kind)
+        pred, loss = StepTailFunction.apply(delta, prev, torch.zeros_like(prev), target, None, None, bmask,
+                                            torch.rand(F, device=dev) + 0.5, rw, 1.0 / B, kind)
         ties = (pred == target) & (bmask == 0)[:, None]
         assert int(ties.sum()) > 0
         loss.backward()
         assert bool((delta.grad[ties] == 0).all())
+
+
+# the step-tail kernel template on each of its seven loss terms, called through the C entry points
+TAIL_TERMS = ["inv_var"] + KINDS
+TAIL_SHAPES = {   # (B, N, F)
+    "quads": (2, 40, 5),       # total 400: the 16-byte loop
+    "scalar": (2, 41, 5),      # total 410, no multiple of 4: the scalar loop
+    "row_wrap": (1, 8, 3),     # 16-byte loop, quads that cross the end of a row (the variable counter wraps inside a quad)
+    "node_wrap": (2, 6, 1),    # 16-byte loop, a quad that crosses the end of a sample (the node counter wraps inside it)
+}
+TAIL_SCALE, TAIL_GLOSS = 0.5, 0.7
+
+
+@pytest.fixture(scope="module")
+def tail_data():
+    """Seeded fp32 inputs per shape, on the CPU: ~30 % of the nodes are boundary (bmask = 1, row_weight = 0)."""
+    out = {}
+    for i, (name, (B, N, F)) in enumerate(TAIL_SHAPES.items()):
+        g = torch.Generator().manual_seed(100 + i)
+        d = {k: torch.randn(B, N, F, generator=g) for k in ("delta", "prev", "truth", "target", "g_pred")}
+        bmask = torch.zeros(N)
+        bmask[torch.randperm(N, generator=g)[: max(1, round(0.3 * N))]] = 1.0
+        d["bmask"], d["row_weight"] = bmask, (1 - bmask) / (1 - bmask).sum()
+        d["dstd"], d["dmean"] = torch.rand(F, generator=g) + 0.5, torch.randn(F, generator=g)
+        d["var_std"] = torch.rand(F, generator=g) + 0.5
+        out[name] = d
+    return out
+
+
+def _tail_reference(d, term, affine, with_gpred):
+    """float64: state update (graph/base.py:331-343), boundary overwrite (autoregressive.py:128-131), the entry of
+    metrics.py with the interior weights; the gradients of delta and prev by autograd."""
+    t = {k: v.double() for k, v in d.items()}
+    delta, prev = t["delta"].requires_grad_(), t["prev"].requires_grad_()
+    new = prev + (delta * t["dstd"] + t["dmean"] if affine else delta)
+    bm = t["bmask"][:, None]
+    pred = bm * t["truth"] + (1 - bm) * new
+    diff, s = pred - t["target"], t["var_std"]
+    if term == "mse":
+        entry = diff**2
+    elif term == "mae":
+        entry = diff.abs()
+    elif term in ("wmse", "inv_var"):
+        entry = diff**2 / s**2
+    elif term == "wmae":
+        entry = diff.abs() / s
+    elif term == "nll":
+        entry = -torch.distributions.Normal(pred, s.expand_as(pred)).log_prob(t["target"])
+    else:
+        z = -diff / s
+        normal = torch.distributions.Normal(torch.zeros((), dtype=torch.float64), torch.ones((), dtype=torch.float64))
+        entry = s * (z * (2 * normal.cdf(z) - 1) + 2 * torch.exp(normal.log_prob(z)) - 1 / torch.pi**0.5)
+    loss = TAIL_SCALE * (t["row_weight"][:, None] * entry).sum()
+    total = TAIL_GLOSS * loss + ((pred * t["g_pred"]).sum() if with_gpred else 0.0)
+    d_delta, d_prev = torch.autograd.grad(total, (delta, prev))
+    return pred.detach(), loss.detach(), d_delta, d_prev
+
+
+def _tail_run(lib, dev, d, term, affine, with_gpred, misalign=False):
+    """pred, loss and the two gradients from the entry points of `term`; d_prev and d_delta come from one backward call each,
+    the other output NULL."""
+    put = (lambda t: _misaligned(t.to(dev))) if misalign else (lambda t: t.to(dev).contiguous())
+    t = {k: put(v) for k, v in d.items()}
+    B, N, F = d["delta"].shape
+    consts = t["var_std"] if term != "inv_var" else put(1.0 / d["var_std"] ** 2)
+    kind = () if term == "inv_var" else (L.LOSS_KINDS[term],)
+    fwd, bwd = (lib.nlam_step_tail_fwd, lib.nlam_step_tail_bwd) if term == "inv_var" else (lib.nlam_step_tail_loss_fwd,
+                                                                                          lib.nlam_step_tail_loss_bwd)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    dstd, dmean = (t["dstd"], t["dmean"]) if affine else (None, None)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    pred = put(torch.zeros(B, N, F))
+    nparts = 512
+    partials, loss = torch.zeros(nparts, device=dev), torch.zeros((), device=dev)
+    gloss = torch.tensor(TAIL_GLOSS, device=dev)
+    L.check(fwd(*kind, ptr(t["delta"]), ptr(t["prev"]), ptr(t["truth"]), ptr(t["target"]), ptr(dstd), ptr(dmean), ptr(t["bmask"]),
+                ptr(consts), ptr(t["row_weight"]), TAIL_SCALE, ptr(pred), ptr(partials), nparts, B * N, N, F, stream), "step tail fwd")
+    L.check(lib.nlam_reduce_partials(ptr(partials), nparts, 1, 1, ptr(loss), 0, stream), "nlam_reduce_partials")
+    grads = []
+    for which in (0, 1):   # d_delta only, d_prev only
+        out = put(torch.zeros(B, N, F))
+        L.check(bwd(*kind, ptr(t["g_pred"]) if with_gpred else None, ptr(gloss), ptr(pred), ptr(t["target"]), ptr(dstd),
+                    ptr(t["bmask"]), ptr(consts), ptr(t["row_weight"]), TAIL_SCALE, ptr(out) if which == 0 else None,
+                    ptr(out) if which == 1 else None, B * N, N, F, stream), "step tail bwd")
+        grads.append(out)
+    torch.cuda.synchronize()
+    return pred, loss, grads[0], grads[1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("term", TAIL_TERMS)
+def test_step_tail_kernels_match_float64_formula(dev, tail_data, term):
+    """step_tail_fwd_kernel / step_tail_bwd_kernel on every loss term (the inv_var form of nlam_step_tail_* and the six kinds
+    of nlam_step_tail_loss_*) against the float64 formula: the 16-byte loop, the scalar loop (a total that is no multiple of
+    4, and 16-byte-misaligned slices of a total that is), quads across the row and the node wrap; with and without dstd /
+    dmean, with and without g_pred, one gradient output at a time; ~30 % boundary nodes.  The two loops must agree bit for
+    bit on the elementwise outputs and to 1e-6 on the loss (the summation order of 400 fp32 terms)."""
+    lib = L.load()
+    for name, d in tail_data.items():
+        boundary = d["bmask"] == 1
+        for affine in (True, False):
+            for with_gpred in (True, False):
+                what = (term, name, affine, with_gpred)
+                ref = _tail_reference(d, term, affine, with_gpred)
+                runs = [_tail_run(lib, dev, d, term, affine, with_gpred)]
+                if name == "quads":
+                    runs.append(_tail_run(lib, dev, d, term, affine, with_gpred, misalign=True))
+                for pred, loss, d_delta, d_prev in runs:
+                    err = abs(float(loss) - float(ref[1])) / abs(float(ref[1]))
+                    errs = [rel_err(a.cpu().double(), b) for a, b in zip((pred, d_delta, d_prev), (ref[0], ref[2], ref[3]))]
+                    print(what, f"loss {float(loss):.8g} rel {err:.2e}; pred / d_delta / d_prev", " ".join(f"{e:.2e}" for e in errs))
+                    assert err <= 1e-5, what
+                    assert max(errs) <= 1e-5, what
+                    assert bool((d_delta[:, boundary.to(dev)] == 0).all()) and bool((d_prev[:, boundary.to(dev)] == 0).all()), what
+                if len(runs) == 2:
+                    (p0, l0, a0, b0), (p1, l1, a1, b1) = runs
+                    assert torch.equal(p0, p1) and torch.equal(a0, a1) and torch.equal(b0, b1), what
+                    print(what, f"loss, 16-byte against scalar loop: rel {abs(float(l0) - float(l1)) / abs(float(l0)):.2e}")
+                    assert abs(float(l0) - float(l1)) <= 1e-6 * abs(float(l0)), what
 
 
 def _golden_step(golden, model, kind, dev, tmp_path):
@@ -244,7 +377,7 @@ def _golden_step(golden, model, kind, dev, tmp_path):
 def test_model_training_step_per_loss_matches_reference_golden(dev, golden, tmp_path, model, kind):
     """ForecasterStep(loss=kind) against the reference's ARForecaster + metrics.<kind>: loss, prediction, every parameter
     gradient (the norms of test_hip_parity.test_model_training_step_matches_reference_golden).  The mean model takes the fused
-    step tail (wmse: its own pair), the output_std model ops.LossFunction with its predicted std."""
+    step tail (wmse: the same kernels on the inv_var term), the output_std model ops.LossFunction with its predicted std."""
     case = golden["models"][model]
     ref = case["kinds"][kind]
     fc, step, batch = _golden_step(golden, model, kind, dev, tmp_path)
@@ -262,9 +395,9 @@ def test_model_training_step_per_loss_matches_reference_golden(dev, golden, tmp_
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", KINDS)
 def test_fused_step_tail_matches_unfused_route(dev, golden, tmp_path, monkeypatch, kind):
-    """T = 3: the fused step tail (ops.StepTailLossFunction, no separate loss launch) against the unfused route
-    (FUSED_STATE_UPDATE off: the state update on its own, then ops.LossFunction over the rollout).  wmse keeps its own pair,
-    ops.StepTailFunction / ops.WmseLossFunction."""
+    """T = 3: the fused step tail (ops.StepTailFunction, no separate loss launch) against the unfused route
+    (FUSED_STATE_UPDATE off: the state update on its own, then ops.LossFunction over the rollout; ops.WmseLossFunction for
+    wmse, which hands in 1 / std^2)."""
     from neural_lam_amd import models as hm
     from neural_lam_amd import ops
 
@@ -275,7 +408,7 @@ def test_fused_step_tail_matches_unfused_route(dev, golden, tmp_path, monkeypatc
         batch = [init, torch.randn(1, 3, N, 5, generator=g).to(dev), torch.randn(1, 3, N, 6, generator=g).to(dev)]
         monkeypatch.setattr(hm, "FUSED_STATE_UPDATE", fused)
         calls = {"loss": 0, "tail": 0}
-        names = ("WmseLossFunction", "StepTailFunction") if kind == "wmse" else ("LossFunction", "StepTailLossFunction")
+        names = ("WmseLossFunction" if kind == "wmse" else "LossFunction", "StepTailFunction")
         for name, key in zip(names, ("loss", "tail")):
             orig = getattr(ops, name).apply
 

@@ -2,14 +2,17 @@
 """Compare two device-assembly listings of csrc/nlam_hip.hip kernel by kernel.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC [-DNLAM_TU=k] --cuda-device-only -S nlam_hip.hip -o X.s
-    tools/device_asm_diff.py before.s after.s
+    tools/device_asm_diff.py [--rename OLD=NEW]... before.s after.s
 
 A host-side refactor must leave the device code alone: the same set of kernel symbols, and under every symbol the same
 text (code, kernel descriptor, resource comments) and the same metadata record.  The order in which the compiler emits the
 functions follows the order in which the host code names them and may change, so the listing is cut at the function
 boundaries and the pieces are compared by symbol.  Two things are normalised: lines that name `__hip_cuid_` (a hash of
 the source text), and the function ordinal in local labels and loop comments (.LBB<n>_<k>, .Lfunc_end<n>; with it the
-padding in front of a comment), which is the emission order again.  Exit status 0 = identical, 1 = not; the kernel count is printed either way."""
+padding in front of a comment), which is the emission order again.  A kernel that was renamed on purpose is paired with
+--rename OLD=NEW (repeatable): the one symbol of before.s that contains OLD is compared with the one symbol of after.s that
+contains NEW, each under a placeholder for its own name, instead of being reported as missing on both sides.
+Exit status 0 = identical, 1 = not; the kernel count is printed either way."""
 import re
 import sys
 
@@ -52,8 +55,24 @@ def pieces(path):
     return out
 
 
+def rename(d, sub, key, path):
+    """Re-key the one kernel of d whose symbol contains sub as `key`, its own name replaced by a placeholder in its text."""
+    syms = [k for k in d if sub in k and not k.startswith(("meta:", "<"))]
+    if len(syms) != 1:
+        sys.exit(f"--rename: {sub!r} matches {len(syms)} symbols of {path}")
+    for k in (syms[0], "meta:" + syms[0]):
+        d[k.replace(syms[0], key)] = [l.replace(syms[0], "<renamed>") for l in d.pop(k)]
+
+
 def main():
+    renames = []
+    while len(sys.argv) > 1 and sys.argv[1] == "--rename":
+        renames.append(sys.argv[2].split("=", 1))
+        del sys.argv[1:3]
     a, b = pieces(sys.argv[1]), pieces(sys.argv[2])
+    for old, new in renames:
+        rename(a, old, f"{old}={new}", sys.argv[1])
+        rename(b, new, f"{old}={new}", sys.argv[2])
     kernels = lambda d: sorted(k[5:] for k in d if k.startswith("meta:"))
     print(f"{sys.argv[1]}: {len(kernels(a))} kernels, {sys.argv[2]}: {len(kernels(b))} kernels")
     bad = 0
