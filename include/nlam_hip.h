@@ -63,6 +63,9 @@
  *   nlam_accum_begin, nlam_adamw_step_accum
  *       Lightning's accumulate_grad_batches: the zero of the gradient and the controlled update gated on the device by the
  *       index of the micro-batch, so that one recorded step serves every micro-step of a window.
+ *   nlam_adamw_step_resident_ema, nlam_adamw_step_controlled_ema, nlam_flat_swap
+ *       Lightning's EMAWeightAveraging (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn): the moving average
+ *       of the weights, kept by the AdamW update launch itself, and the in-place exchange of weights and average.
  */
 #ifndef NLAM_HIP_H
 #define NLAM_HIP_H
@@ -899,6 +902,38 @@ typedef struct {
 } nlam_accum_t;
 int32_t nlam_accum_begin(float* grad, int64_t n, const int32_t* accum, void* hip_stream);
 int32_t nlam_adamw_step_accum(const nlam_optctl_t* p, const nlam_accum_t* a, void* hip_stream);
+
+/* An exponential moving average of the parameters, kept by the launch that writes them (no launch more; `ema` is read
+ * and written once per update, 8 bytes per parameter): AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)) stepped
+ * after every optimizer step, started as EMAWeightAveraging(update_starting_at_step=start_step) starts it.  With u the
+ * 1-based count of APPLIED updates (*step_count_dev once this call's first launches have advanced it), for every element,
+ * p being the new parameter value:
+ *   u < start_step: ema is not touched;   u == start_step: ema = p;   u > start_step: ema = ema + w * (p - ema)
+ * with w = 1.0f - decay computed once on the host, and the last form evaluated as one subtract, one multiply and one add,
+ * each rounded to fp32 (never contracted): every kernel that carries it gives the same bits.  The decision is read on the
+ * device, so no launch argument depends on the step.  ema is not touched where the parameters are not: a step refused for
+ * a non-finite norm, a micro-batch inside an accumulation window, n == 0.  Parameters, moments, step count and bias
+ * corrections get the bits of the entry without `_ema`.
+ * nlam_adamw_step_resident_ema: the two launches of nlam_adamw_step_resident.
+ * nlam_adamw_step_controlled_ema: a == NULL: the three launches of nlam_adamw_step_controlled; otherwise those of
+ *   nlam_adamw_step_accum, with the same gates.
+ * NLAM_EINVAL: null e or e->ema, ema not 4-byte aligned (16-byte accesses are used only where param, grad, both moments
+ * and ema all sit on a 16-byte boundary), decay outside [0, 1) or NaN, start_step < 1, and whatever the entry without
+ * `_ema` rejects. */
+typedef struct {
+    float* ema;                      /* n floats */
+    float decay;                     /* in [0, 1) */
+    int32_t start_step;              /* >= 1: the applied update at which ema becomes a copy of the parameters */
+} nlam_ema_t;
+int32_t nlam_adamw_step_resident_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int32_t* step_count_dev,
+                                     float* bias_corr_dev, float grad_scale, void* hip_stream, const nlam_ema_t* e);
+int32_t nlam_adamw_step_controlled_ema(const nlam_optctl_t* p, const nlam_accum_t* a, const nlam_ema_t* e, void* hip_stream);
+/* a[0 .. n) <-> b[0 .. n), in place, one launch (evaluation under the averaged weights without rebinding a buffer that
+ * captured graphs hold).  Any 4-byte aligned a and b, any n >= 0: 16-byte accesses on the interior that is 16-byte aligned
+ * in BOTH buffers (none when their offsets within 16 bytes differ), single elements around it.  The ranges must not
+ * overlap.  NLAM_EINVAL: null or misaligned buffers, n < 0. */
+int32_t nlam_flat_swap(float* a, float* b, int64_t n, void* hip_stream);
 
 #ifdef __cplusplus
 }

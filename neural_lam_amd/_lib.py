@@ -122,6 +122,9 @@ EXPORTS = [
     "nlam_adamw_step_controlled",
     "nlam_accum_begin",
     "nlam_adamw_step_accum",
+    "nlam_adamw_step_resident_ema",
+    "nlam_adamw_step_controlled_ema",
+    "nlam_flat_swap",
 ]
 
 
@@ -481,6 +484,11 @@ class Accum(C.Structure):
     _fields_ = [("accum", C.c_void_p), ("loss", C.c_void_p), ("steps", C.c_int32)]
 
 
+class Ema(C.Structure):
+    """nlam_ema_t: the moving average of the weights kept by the AdamW update launch (buffer, decay, first averaged update)."""
+    _fields_ = [("ema", C.c_void_p), ("decay", C.c_float), ("start_step", C.c_int32)]
+
+
 class PackRec(C.Structure):
     _fields_ = [("bytes", C.c_ubyte * 64)]
 
@@ -621,6 +629,12 @@ def load():
     lib.nlam_accum_begin.restype = i32
     lib.nlam_adamw_step_accum.argtypes = [C.POINTER(OptCtl), C.POINTER(Accum), vp]
     lib.nlam_adamw_step_accum.restype = i32
+    lib.nlam_adamw_step_resident_ema.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp, f32, vp, C.POINTER(Ema)]
+    lib.nlam_adamw_step_resident_ema.restype = i32
+    lib.nlam_adamw_step_controlled_ema.argtypes = [C.POINTER(OptCtl), C.POINTER(Accum), C.POINTER(Ema), vp]
+    lib.nlam_adamw_step_controlled_ema.restype = i32
+    lib.nlam_flat_swap.argtypes = [vp, vp, i64, vp]
+    lib.nlam_flat_swap.restype = i32
     lib.nlam_mlp_group_blocks.argtypes = [C.POINTER(C.c_int64), i32, C.POINTER(C.c_int32)]
     lib.nlam_mlp_group_blocks.restype = i32
     lib.nlam_mlp_fwd_group.argtypes = [C.POINTER(MlpFwd), i32, vp]

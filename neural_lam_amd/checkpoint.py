@@ -283,6 +283,28 @@ def export_flat_state(shapes, offsets, m, v, t, hyper, group_template=None):
     return {"state": state, "param_groups": [group]}
 
 
+def export_flat_params(names, shapes, offsets, flat) -> dict:
+    """A flat buffer in the ``FlatParams`` layout (the weight average of ``ops.AdamWFlat``) cut into ``{name: CPU tensor}``."""
+    host = flat.detach().to("cpu")   # one device-to-host copy
+    return {n: host[o : o + _numel(s)].view(s).clone() for n, s, o in zip(names, shapes, offsets)}
+
+
+def import_flat_params(state_dict, names, shapes, offsets, flat, own_keys=()):
+    """The inverse: ``{name: tensor}`` (legacy keys remapped as the weights' are) written into ``flat`` at ``offsets``, in
+    place.  Every name must be there with its shape; ``flat=None`` only validates."""
+    sd = remap_legacy_keys(state_dict, own_keys)
+    for n, s in zip(names, shapes):
+        if n not in sd:
+            raise ValueError(f"missing parameter {n!r} in the checkpoint's weight average")
+        if tuple(sd[n].shape) != tuple(s):
+            raise ValueError(f"shape mismatch for {n!r} in the checkpoint's weight average: {tuple(sd[n].shape)}, the parameter "
+                             f"has {tuple(s)}")
+    if flat is not None:
+        with torch.no_grad():
+            for n, s, o in zip(names, shapes, offsets):
+                flat[o : o + _numel(s)].copy_(sd[n].reshape(-1))
+
+
 def module_state_to_cpu(module: nn.Module) -> dict:
     """``module.state_dict()`` as fresh CPU tensors."""
     return {k: v.detach().to("cpu", copy=True) for k, v in module.state_dict().items()}

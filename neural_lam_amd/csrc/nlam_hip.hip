@@ -4006,6 +4006,63 @@ __global__ __launch_bounds__(256) void window_batch_ens_kernel(const nlam_window
 
 #endif
 
+// One element of the AdamW update, shared by every kernel that applies it (adamw_kernel here, adamw_ctl_body in
+// nlam_optctl.inc), with the roundings of the code the compiler made of adamw_kernel's plain expressions: it fused
+// 1 - lr * wd into one fma (hoisted by the callers as `decay`) and nothing else, so every other product and sum is rounded
+// on its own.  Contraction is switched off and the one fma written out, because what the compiler fuses is its choice per
+// kernel and per instantiation (it fused more in the unrolled quads of adamw_ctl_body): coef = 1 and lr_t = lr give the
+// bits of the plain update (x * 1.0f is exact), and an instantiation that does more around it (EMA) gives the same bits.
+__device__ __forceinline__ void adamw_ctl_one(float& pv, float gr, float& mo, float& vo, float decay, float step, float b1, float b2,
+                                              float eps, float bc2_sqrt, float gscale, float coef) {
+#pragma clang fp contract(off)
+    const float g = gr * gscale * coef;
+    pv *= decay;
+    const float mi = b1 * mo + (1.f - b1) * g;
+    const float vi = b2 * vo + (1.f - b2) * g * g;
+    mo = mi;
+    vo = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pv = pv - step * (mi / denom);
+}
+
+// The exponential moving average of the weights (nlam_ema_t), carried by the update kernels as a template flag: the launch
+// that holds the new parameter value in a register also averages it.  Nothing here is a launch argument that depends on
+// the step: the kernel reads the resident count u of applied updates (already advanced for this one) and decides
+//   u < start: the average is not touched;  u == start: average = p;  u > start: average += w * (p - average), w = 1 - decay
+// -- one subtract, one multiply, one add, never contracted, so every kernel that carries it gives the same bits.
+template <bool EMA>
+struct EmaArg {};
+template <>
+struct EmaArg<true> {
+    float* ema;
+    const int32_t* step_count;
+    float w;
+    int32_t start;
+};
+constexpr int kEmaOff = 0, kEmaCopy = 1, kEmaLerp = 2;
+
+__device__ __forceinline__ int ema_mode(const EmaArg<true>& e) {
+    const int u = *e.step_count;
+    return u < e.start ? kEmaOff : (u == e.start ? kEmaCopy : kEmaLerp);
+}
+
+__device__ __forceinline__ float ema_one(float avg, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - avg;
+    const float wd = w * d;
+    return avg + wd;
+}
+
+// a float buffer, a decay in [0, 1) (false for nan), a first averaged update >= 1
+inline bool ema_valid(const nlam_ema_t* e) {
+    return e != nullptr && e->ema != nullptr && (reinterpret_cast<uintptr_t>(e->ema) & 3) == 0 && e->decay >= 0.f && e->decay < 1.f &&
+           e->start_step >= 1;
+}
+
+inline EmaArg<true> ema_arg(const nlam_ema_t* e, const int32_t* step_count) {
+    return EmaArg<true>{e->ema, step_count, 1.0f - e->decay, e->start_step};
+}
+
 #if NLAM_IN_TU(1)   // concat, wmse_bwd, adamw_prep, adamw
 // row-wise concatenation (nlam_concat): a workgroup owns 64 consecutive rows; every source's 64 x w_k block is one
 // contiguous span in memory (read coalesced into the LDS row image), and so is the 64 x wtot output block
@@ -4062,22 +4119,33 @@ __global__ void adamw_prep_kernel(int32_t* step_count, float* bias_corr, float b
     }
 }
 
+template <bool EMA>
 __global__ void adamw_kernel(float* param, const float* grad, float* m, float* v, long n, float lr, float b1, float b2,
-                             float eps, float wd, float bc1, float bc2_sqrt, float gscale, const float* bias_corr) {
+                             float eps, float wd, float bc1, float bc2_sqrt, float gscale, const float* bias_corr,
+                             const EmaArg<EMA> ea) {
     if (bias_corr != nullptr) {
         bc1 = bias_corr[0];
         bc2_sqrt = bias_corr[1];
     }
+    const float decay = fmaf(-lr, wd, 1.f), step = lr / bc1;   // torch.optim.AdamW: decoupled decay first
+    int mode = kEmaOff;
+    if constexpr (EMA) mode = ema_mode(ea);
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
-        const float g = grad[idx] * gscale;
-        float pv = param[idx];
-        pv *= (1.f - lr * wd);                       // torch.optim.AdamW: decoupled decay first
-        const float mi = b1 * m[idx] + (1.f - b1) * g;
-        const float vi = b2 * v[idx] + (1.f - b2) * g * g;
-        m[idx] = mi;
-        v[idx] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        param[idx] = pv - (lr / bc1) * (mi / denom);
+        float pv = param[idx], mo = m[idx], vo = v[idx];
+        float avg = 0.f;
+        if constexpr (EMA) {
+            if (mode == kEmaLerp) avg = ea.ema[idx];
+        }
+        adamw_ctl_one(pv, grad[idx], mo, vo, decay, step, b1, b2, eps, bc2_sqrt, gscale, 1.f);
+        m[idx] = mo;
+        v[idx] = vo;
+        param[idx] = pv;
+        if constexpr (EMA) {
+            if (mode == kEmaLerp)
+                ea.ema[idx] = ema_one(avg, pv, ea.w);
+            else if (mode == kEmaCopy)
+                ea.ema[idx] = pv;
+        }
     }
 }
 #endif
@@ -6400,6 +6468,21 @@ int elementwise_blocks(long total, long cap) {
     return (int)(blocks > cap ? cap : blocks);
 }
 
+// the two launches of the resident path; EMA: the update launch also keeps the moving average
+template <bool EMA>
+int32_t adamw_resident_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int32_t* step_count_dev,
+                                     float* bias_corr_dev, float grad_scale, hipStream_t stream, const EmaArg<EMA> ea) {
+    if (param == nullptr || grad == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || n < 0 || step_count_dev == nullptr ||
+        bias_corr_dev == nullptr)
+        return NLAM_EINVAL;
+    hipLaunchKernelGGL(adamw_prep_kernel, dim3(1), dim3(64), 0, stream, step_count_dev, bias_corr_dev, beta1, beta2);
+    if (n == 0) return (int32_t)hipGetLastError();
+    hipLaunchKernelGGL(adamw_kernel<EMA>, dim3(elementwise_blocks(n, 256 * 8)), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq,
+                       (long)n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale, (const float*)bias_corr_dev, ea);
+    return (int32_t)hipGetLastError();
+}
+
 template <int KIND>
 int32_t loss_launch(const nlam_loss_t& p, bool bwd, hipStream_t stream) {
     const bool per_entry = p.std != nullptr;
@@ -6769,8 +6852,9 @@ int32_t nlam_adamw_step(float* param, const float* grad, float* exp_avg, float* 
     if (n == 0) return 0;
     const float bc1 = 1.f - powf(beta1, (float)step_count);
     const float bc2 = 1.f - powf(beta2, (float)step_count);
-    hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_blocks(n, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, param, grad, exp_avg,
-                       exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale, (const float*)nullptr);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(elementwise_blocks(n, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, param, grad,
+                       exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale,
+                       (const float*)nullptr, EmaArg<false>{});
     return (int32_t)hipGetLastError();
 }
 
@@ -6778,15 +6862,17 @@ int32_t nlam_adamw_step_resident(float* param, const float* grad, float* exp_avg
                                  float beta1, float beta2, float eps, float weight_decay, int32_t* step_count_dev,
                                  float* bias_corr_dev, float grad_scale, void* hip_stream) {
     NLAM_RANGE("nlam_adamw_step_resident");
-    if (param == nullptr || grad == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || n < 0 || step_count_dev == nullptr ||
-        bias_corr_dev == nullptr)
-        return NLAM_EINVAL;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(adamw_prep_kernel, dim3(1), dim3(64), 0, stream, step_count_dev, bias_corr_dev, beta1, beta2);
-    if (n == 0) return (int32_t)hipGetLastError();
-    hipLaunchKernelGGL(adamw_kernel, dim3(elementwise_blocks(n, 256 * 8)), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq,
-                       (long)n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale, (const float*)bias_corr_dev);
-    return (int32_t)hipGetLastError();
+    return adamw_resident_launch<false>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_count_dev,
+                                        bias_corr_dev, grad_scale, (hipStream_t)hip_stream, EmaArg<false>{});
+}
+
+int32_t nlam_adamw_step_resident_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int32_t* step_count_dev,
+                                     float* bias_corr_dev, float grad_scale, void* hip_stream, const nlam_ema_t* e) {
+    NLAM_RANGE("nlam_adamw_step_resident_ema");
+    if (!ema_valid(e)) return NLAM_EINVAL;
+    return adamw_resident_launch<true>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_count_dev,
+                                       bias_corr_dev, grad_scale, (hipStream_t)hip_stream, ema_arg(e, step_count_dev));
 }
 
 

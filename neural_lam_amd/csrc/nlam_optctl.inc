@@ -19,6 +19,9 @@
 //   adamw_control_accum_kernel  adds the micro-batch loss to the window's sum and either holds (advance word 0, raise the
 //                               hold flag) or closes the window and decides as adamw_control_kernel does (one shared body).
 //   adamw_ctl_accum_kernel      adamw_ctl_kernel's body behind the hold flag and the skip flag.
+// The moving average of the weights (nlam_adamw_step_controlled_ema) is a template flag of adamw_ctl_body and its two kernels:
+// behind the same gates, from the parameter value the launch holds (EmaArg / ema_one in nlam_hip.hip).  flat_swap_kernel
+// exchanges weights and average in place (nlam_flat_swap), head / tail as accum_begin_kernel.
 // Included from nlam_hip.hip inside NLAM_IN_TU(5).
 
 namespace {
@@ -195,28 +198,19 @@ __global__ __launch_bounds__(64) void adamw_control_accum_kernel(const OptCtlArg
     optctl_decide(a, sum);
 }
 
-// One element of adamw_kernel with the roundings of the code the compiler makes of it: it fuses 1 - lr * wd into one fma (hoisted
-// here as `decay`) and nothing else, so every other product and sum is rounded on its own.  Contraction is switched off and the
-// one fma written out, because what the compiler fuses is its choice per kernel (it fused more in this one's unrolled quads):
-// coef = 1 and lr_t = lr then give adamw_kernel's bits (x * 1.0f is exact).
-__device__ __forceinline__ void adamw_ctl_one(float& pv, float gr, float& mo, float& vo, float decay, float step, float b1, float b2,
-                                              float eps, float bc2_sqrt, float gscale, float coef) {
-#pragma clang fp contract(off)
-    const float g = gr * gscale * coef;
-    pv *= decay;
-    const float mi = b1 * mo + (1.f - b1) * g;
-    const float vi = b2 * vo + (1.f - b2) * g * g;
-    mo = mi;
-    vo = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pv = pv - step * (mi / denom);
-}
-
+// (adamw_ctl_one, one element of the update, sits in nlam_hip.hip: adamw_kernel shares it)
 // nq quads from 16-byte aligned bases, then the n - 4 nq elements behind them
 // (first / stride: the caller's (long)blockIdx.x * blockDim.x + threadIdx.x and (long)gridDim.x * blockDim.x)
+template <bool EMA>
 __device__ __forceinline__ void adamw_ctl_body(float* param, const float* grad, float* m, float* v, long n, long nq, float b1, float b2,
                                                float eps, float wd, float gscale, const float* bias_corr, const float* ctl_f,
-                                               long first, long stride) {
+                                               long first, long stride, const EmaArg<EMA> ea) {
+    int mode = kEmaOff;
+    f32x4* e4 = nullptr;
+    if constexpr (EMA) {
+        mode = ema_mode(ea);
+        e4 = reinterpret_cast<f32x4*>(ea.ema);
+    }
     const float lr = ctl_f[0], coef = ctl_f[1];
     const float bc1 = bias_corr[0], bc2_sqrt = bias_corr[1];
     const float decay = fmaf(-lr, wd, 1.f), step = lr / bc1;   // torch.optim.AdamW: decoupled decay first
@@ -227,6 +221,10 @@ __device__ __forceinline__ void adamw_ctl_body(float* param, const float* grad, 
     for (long i = first; i < nq; i += stride) {
         f32x4 pv = p4[i], mo = m4[i], vo = v4[i];
         const f32x4 gr = g4[i];
+        f32x4 avg = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (EMA) {
+            if (mode == kEmaLerp) avg = e4[i];
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float pk = pv[k], mk = mo[k], vk = vo[k];
@@ -238,32 +236,77 @@ __device__ __forceinline__ void adamw_ctl_body(float* param, const float* grad, 
         m4[i] = mo;
         v4[i] = vo;
         p4[i] = pv;
+        if constexpr (EMA) {
+            if (mode == kEmaLerp) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) avg[k] = ema_one(avg[k], pv[k], ea.w);
+                e4[i] = avg;
+            } else if (mode == kEmaCopy) {
+                e4[i] = pv;
+            }
+        }
     }
     for (long idx = 4 * nq + first; idx < n; idx += stride) {
         float pk = param[idx], mk = m[idx], vk = v[idx];
+        float avg = 0.f;
+        if constexpr (EMA) {
+            if (mode == kEmaLerp) avg = ea.ema[idx];
+        }
         adamw_ctl_one(pk, grad[idx], mk, vk, decay, step, b1, b2, eps, bc2_sqrt, gscale, coef);
         m[idx] = mk;
         v[idx] = vk;
         param[idx] = pk;
+        if constexpr (EMA) {
+            if (mode == kEmaLerp)
+                ea.ema[idx] = ema_one(avg, pk, ea.w);
+            else if (mode == kEmaCopy)
+                ea.ema[idx] = pk;
+        }
     }
 }
 
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_ctl_kernel(float* param, const float* grad, float* m, float* v, long n, long nq, float b1,
                                                         float b2, float eps, float wd, float gscale, const float* bias_corr,
-                                                        const float* ctl_f, const int32_t* ctl_i) {
-    if (ctl_i[3] != 0) return;   // a non-finite step: parameters and moments stay as they are
-    adamw_ctl_body(param, grad, m, v, n, nq, b1, b2, eps, wd, gscale, bias_corr, ctl_f,
-                   (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+                                                        const float* ctl_f, const int32_t* ctl_i, const EmaArg<EMA> ea) {
+    if (ctl_i[3] != 0) return;   // a non-finite step: parameters and moments (and the average) stay as they are
+    adamw_ctl_body<EMA>(param, grad, m, v, n, nq, b1, b2, eps, wd, gscale, bias_corr, ctl_f,
+                        (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ea);
 }
 
 // ... and while a window is open (hold flag acc[1]) nothing is touched either
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_ctl_accum_kernel(float* param, const float* grad, float* m, float* v, long n, long nq,
                                                               float b1, float b2, float eps, float wd, float gscale,
                                                               const float* bias_corr, const float* ctl_f, const int32_t* ctl_i,
-                                                              const int32_t* acc) {
+                                                              const int32_t* acc, const EmaArg<EMA> ea) {
     if (acc[1] != 0 || ctl_i[3] != 0) return;
-    adamw_ctl_body(param, grad, m, v, n, nq, b1, b2, eps, wd, gscale, bias_corr, ctl_f,
-                   (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+    adamw_ctl_body<EMA>(param, grad, m, v, n, nq, b1, b2, eps, wd, gscale, bias_corr, ctl_f,
+                        (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ea);
+}
+
+constexpr int kSwapThreads = 256;
+constexpr int kSwapMaxBlocks = 256 * 8;   // adamw_ctl_kernel's cap
+
+// a <-> b.  `head` elements in front of the first address that is 16-byte aligned in both buffers (the host passes n when
+// there is none: the two sit at different offsets within 16 bytes), nq quads behind it, the rest one by one.  Every element
+// is read and written by one lane only, so the exchange needs no ordering between lanes.
+__global__ __launch_bounds__(kSwapThreads) void flat_swap_kernel(float* a, float* b, long n, long head, long nq) {
+    const long first = (long)blockIdx.x * kSwapThreads + threadIdx.x, stride = (long)gridDim.x * kSwapThreads;
+    f32x4* a4 = reinterpret_cast<f32x4*>(a + head);
+    f32x4* b4 = reinterpret_cast<f32x4*>(b + head);
+    for (long i = first; i < nq; i += stride) {
+        const f32x4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    const long tail0 = head + 4 * nq;
+    for (long k = first; k < head + (n - tail0); k += stride) {   // the elements around the quads
+        const long idx = k < head ? k : tail0 + (k - head);
+        const float x = a[idx], y = b[idx];
+        a[idx] = y;
+        b[idx] = x;
+    }
 }
 
 constexpr int kZeroThreads = 256;
@@ -305,8 +348,15 @@ int32_t sumsq_launch(const float* grad, int64_t n, double* partials, int64_t wor
     return (int32_t)hipGetLastError();
 }
 
-// the three launches of nlam_adamw_step_controlled; with `acc` each of them behind its gate
-int32_t optctl_launch(const nlam_optctl_t* p, const nlam_accum_t* acc, hipStream_t stream) {
+inline bool accum_valid(const nlam_accum_t* a) {
+    return a != nullptr && a->accum != nullptr && a->steps >= 1 && (reinterpret_cast<uintptr_t>(a->accum) & 3) == 0 &&
+           (reinterpret_cast<uintptr_t>(a->loss) & 3) == 0;
+}
+
+// the three launches of nlam_adamw_step_controlled; with `acc` each of them behind its gate; EMA: the update launch also
+// keeps the moving average `e`
+template <bool EMA>
+int32_t optctl_launch(const nlam_optctl_t* p, const nlam_accum_t* acc, hipStream_t stream, const nlam_ema_t* e = nullptr) {
     if (p == nullptr || p->param == nullptr || p->grad == nullptr || p->exp_avg == nullptr || p->exp_avg_sq == nullptr ||
         p->step_count_dev == nullptr || p->bias_corr_dev == nullptr || p->control == nullptr || p->n < 0)
         return NLAM_EINVAL;
@@ -315,6 +365,11 @@ int32_t optctl_launch(const nlam_optctl_t* p, const nlam_accum_t* acc, hipStream
         return NLAM_EINVAL;
     if (p->schedule == NLAM_SCHED_NONE && p->warmup_steps != 0) return NLAM_EINVAL;
     if ((reinterpret_cast<uintptr_t>(p->control) & 3) != 0) return NLAM_EINVAL;
+    EmaArg<EMA> ea;
+    if constexpr (EMA) {
+        if (!ema_valid(e)) return NLAM_EINVAL;
+        ea = ema_arg(e, p->step_count_dev);
+    }
     int nparts = 0;
     if (acc == nullptr) {
         if (const int32_t rc = sumsq_launch(p->grad, p->n, p->partials, p->partials_doubles, stream, &nparts)) return rc;
@@ -337,22 +392,24 @@ int32_t optctl_launch(const nlam_optctl_t* p, const nlam_accum_t* acc, hipStream
     else
         hipLaunchKernelGGL(adamw_control_accum_kernel, dim3(1), dim3(64), 0, stream, a, acc->accum, acc->loss, (int)acc->steps);
     if (p->n == 0) return (int32_t)hipGetLastError();
-    // quads only where all four buffers sit on a 16-byte boundary (the flat buffers do); element by element otherwise
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(p->param) | reinterpret_cast<uintptr_t>(p->grad) |
-                           reinterpret_cast<uintptr_t>(p->exp_avg) | reinterpret_cast<uintptr_t>(p->exp_avg_sq);
+    // quads only where all four buffers (five with the average) sit on a 16-byte boundary (the flat buffers do); element by
+    // element otherwise
+    uintptr_t bits = reinterpret_cast<uintptr_t>(p->param) | reinterpret_cast<uintptr_t>(p->grad) |
+                     reinterpret_cast<uintptr_t>(p->exp_avg) | reinterpret_cast<uintptr_t>(p->exp_avg_sq);
+    if constexpr (EMA) bits |= reinterpret_cast<uintptr_t>(e->ema);
     const long nq = (bits & 15) == 0 ? (long)(p->n >> 2) : 0L;
     const long work = nq > 0 ? nq : (long)p->n;
     long blocks = (work + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (acc == nullptr)
-        hipLaunchKernelGGL(adamw_ctl_kernel, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg, p->exp_avg_sq,
+        hipLaunchKernelGGL(adamw_ctl_kernel<EMA>, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg, p->exp_avg_sq,
                            (long)p->n, nq, p->beta1, p->beta2, p->eps, p->weight_decay, p->grad_scale, (const float*)p->bias_corr_dev,
-                           (const float*)a.ctl_f, (const int32_t*)a.ctl_i);
+                           (const float*)a.ctl_f, (const int32_t*)a.ctl_i, ea);
     else
-        hipLaunchKernelGGL(adamw_ctl_accum_kernel, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg,
+        hipLaunchKernelGGL(adamw_ctl_accum_kernel<EMA>, dim3((int)blocks), dim3(256), 0, stream, p->param, p->grad, p->exp_avg,
                            p->exp_avg_sq, (long)p->n, nq, p->beta1, p->beta2, p->eps, p->weight_decay, p->grad_scale,
                            (const float*)p->bias_corr_dev, (const float*)a.ctl_f, (const int32_t*)a.ctl_i,
-                           (const int32_t*)acc->accum);
+                           (const int32_t*)acc->accum, ea);
     return (int32_t)hipGetLastError();
 }
 
@@ -378,14 +435,39 @@ int32_t nlam_grad_sumsq(const float* grad, int64_t n, double* partials, int64_t 
 
 int32_t nlam_adamw_step_controlled(const nlam_optctl_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_adamw_step_controlled");
-    return optctl_launch(p, nullptr, (hipStream_t)hip_stream);
+    return optctl_launch<false>(p, nullptr, (hipStream_t)hip_stream);
 }
 
 int32_t nlam_adamw_step_accum(const nlam_optctl_t* p, const nlam_accum_t* a, void* hip_stream) {
     NLAM_RANGE("nlam_adamw_step_accum");
-    if (a == nullptr || a->accum == nullptr || a->steps < 1) return NLAM_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(a->accum) & 3) != 0 || (reinterpret_cast<uintptr_t>(a->loss) & 3) != 0) return NLAM_EINVAL;
-    return optctl_launch(p, a, (hipStream_t)hip_stream);
+    if (!accum_valid(a)) return NLAM_EINVAL;
+    return optctl_launch<false>(p, a, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_adamw_step_controlled_ema(const nlam_optctl_t* p, const nlam_accum_t* a, const nlam_ema_t* e, void* hip_stream) {
+    NLAM_RANGE("nlam_adamw_step_controlled_ema");
+    if (a != nullptr && !accum_valid(a)) return NLAM_EINVAL;
+    if (!ema_valid(e)) return NLAM_EINVAL;   // (in front of optctl_launch's own checks: nothing is launched)
+    return optctl_launch<true>(p, a, (hipStream_t)hip_stream, e);
+}
+
+int32_t nlam_flat_swap(float* a, float* b, int64_t n, void* hip_stream) {
+    NLAM_RANGE("nlam_flat_swap");
+    if (a == nullptr || b == nullptr || n < 0) return NLAM_EINVAL;
+    const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b);
+    if ((ua & 3) != 0 || (ub & 3) != 0) return NLAM_EINVAL;
+    if (n == 0 || a == b) return 0;
+    long head = (long)n, nq = 0;
+    if ((ua & 15) == (ub & 15)) {   // a common 16-byte grid: quads between the first boundary and the last whole quad
+        head = (long)(((16 - (ua & 15)) & 15) >> 2);
+        if (head > (long)n) head = (long)n;
+        nq = ((long)n - head) >> 2;
+    }
+    const long work = nq > (long)n - 4 * nq ? nq : (long)n - 4 * nq;
+    long blocks = (work + kSwapThreads - 1) / kSwapThreads;
+    blocks = blocks < 1 ? 1 : (blocks > kSwapMaxBlocks ? kSwapMaxBlocks : blocks);
+    hipLaunchKernelGGL(flat_swap_kernel, dim3((int)blocks), dim3(kSwapThreads), 0, (hipStream_t)hip_stream, a, b, (long)n, head, nq);
+    return (int32_t)hipGetLastError();
 }
 
 int32_t nlam_accum_begin(float* grad, int64_t n, const int32_t* accum, void* hip_stream) {

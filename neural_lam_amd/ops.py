@@ -2737,10 +2737,18 @@ class AdamWFlat:
       step recorded once serves all of them.  ``micro_step`` is the host mirror of the index within the window, ``t``
       advances on the closing call only, and ``grad_norm`` / ``last_lr`` / ``clip_coef`` keep the last closed window's values
       while a window is open.  A window skipped for a non-finite norm is closed all the same: the next ``begin()`` clears
-      the poisoned gradient."""
+      the poisoned gradient.
+
+    ``ema_decay`` (off by default): an exponential moving average of the parameters in ``ema``, a flat fp32 copy taken at
+    construction -- ``AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay))`` stepped after every optimizer step, started as
+    ``EMAWeightAveraging(update_starting_at_step=ema_start_step)`` starts it.  It is written by the update launch itself (the
+    ``_ema`` entry of whichever path ``step`` takes: no launch more), from the parameter value that launch holds: untouched
+    before applied update ``ema_start_step``, a copy at it, ``ema + (1 - decay) * (p - ema)`` behind it -- and untouched
+    wherever the parameters are (a skipped step, a micro-batch inside a window).  It does not make the optimizer
+    ``controlled``."""
 
     def __init__(self, flat_param, flat_grad, lr=1e-3, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 lr_schedule=None, skip_nonfinite=False, accumulate=1):
+                 lr_schedule=None, skip_nonfinite=False, accumulate=1, ema_decay=None, ema_start_step=1):
         self.p, self.g = flat_param, flat_grad
         self.m = torch.zeros_like(flat_param)
         self.v = torch.zeros_like(flat_param)
@@ -2760,6 +2768,13 @@ class AdamWFlat:
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"accumulate must be a count of micro-batches >= 1, not {accumulate!r}")
         self._accumulate = int(accumulate)
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:   # (false for nan)
+            raise ValueError(f"ema_decay must lie in [0, 1) (or be None), not {ema_decay!r}")
+        if int(ema_start_step) != ema_start_step or ema_start_step < 1:
+            raise ValueError(f"ema_start_step must be an update count >= 1, not {ema_start_step!r}")
+        self._ema_decay = None if ema_decay is None else float(ema_decay)
+        self._ema_start_step = int(ema_start_step)
+        self.ema = None if ema_decay is None else flat_param.detach().clone()
         self._controlled = (self._max_grad_norm is not None or lr_schedule is not None or self._skip_nonfinite
                             or self._accumulate > 1)
         self.micro_step = 0   # host mirror of word 0 of ``acc``: calls mod K
@@ -2783,6 +2798,14 @@ class AdamWFlat:
     skip_nonfinite = property(lambda self: self._skip_nonfinite)
     controlled = property(lambda self: self._controlled)
     accumulate = property(lambda self: self._accumulate)
+    ema_decay = property(lambda self: self._ema_decay)
+    ema_start_step = property(lambda self: self._ema_start_step)
+
+    def _ema_arg(self):
+        """The nlam_ema_t of this optimizer's ``_ema`` launches."""
+        e = L.Ema()
+        e.ema, e.decay, e.start_step = _ptr(self.ema), self._ema_decay, self._ema_start_step
+        return e
 
     def begin(self):
         """The head of a step, in front of forward + backward: the gradient is zeroed -- with ``accumulate`` > 1 by a launch
@@ -2807,11 +2830,12 @@ class AdamWFlat:
         self.t += 1
         if self.controlled:
             return self._step_controlled(grad_scale)
-        rc = L.load().nlam_adamw_step_resident(
-            _ptr(self.p), _ptr(self.g), _ptr(self.m), _ptr(self.v), self.p.numel(), self.lr, self.betas[0],
-            self.betas[1], self.eps, self.wd, _ptr(self.t_dev), _ptr(self.bc_dev), grad_scale, _stream(),
-        )
-        L.check(rc, "nlam_adamw_step_resident")
+        args = (_ptr(self.p), _ptr(self.g), _ptr(self.m), _ptr(self.v), self.p.numel(), self.lr, self.betas[0],
+                self.betas[1], self.eps, self.wd, _ptr(self.t_dev), _ptr(self.bc_dev), grad_scale, _stream())
+        if self.ema is not None:
+            L.check(L.load().nlam_adamw_step_resident_ema(*args, C.byref(self._ema_arg())), "nlam_adamw_step_resident_ema")
+            return
+        L.check(L.load().nlam_adamw_step_resident(*args), "nlam_adamw_step_resident")
 
     def _optctl(self, grad_scale):
         """The nlam_optctl_t of this optimizer's controlled launches."""
@@ -2833,6 +2857,10 @@ class AdamWFlat:
     def _step_controlled(self, grad_scale, loss=None):
         c = self._optctl(grad_scale)
         if self._accumulate == 1:
+            if self.ema is not None:
+                L.check(L.load().nlam_adamw_step_controlled_ema(C.byref(c), None, C.byref(self._ema_arg()), _stream()),
+                        "nlam_adamw_step_controlled_ema")
+                return
             L.check(L.load().nlam_adamw_step_controlled(C.byref(c), _stream()), "nlam_adamw_step_controlled")
             return
         a = L.Accum()
@@ -2840,6 +2868,10 @@ class AdamWFlat:
         if loss is not None and loss.dim() == 0 and loss.dtype == torch.float32 and loss.device == self.acc.device:
             a.loss = _ptr(loss)
             self._window_loss = self._acc_f[L.ACCUM_WINDOW_LOSS]
+        if self.ema is not None:
+            L.check(L.load().nlam_adamw_step_controlled_ema(C.byref(c), C.byref(a), C.byref(self._ema_arg()), _stream()),
+                    "nlam_adamw_step_controlled_ema")
+            return
         L.check(L.load().nlam_adamw_step_accum(C.byref(c), C.byref(a), _stream()), "nlam_adamw_step_accum")
 
     @property

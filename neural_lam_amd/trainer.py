@@ -409,7 +409,7 @@ class Trainer:
                  bucket_bytes: int = 32 << 20, optimizer_factory=None, group=None, use_graph: bool = False,
                  overlap_wgrad: bool = True, early_leaf_backward: bool | None = None, grad_comm_dtype=None,
                  executor: str | None = None, forks_per_segment: int | None = None, max_grad_norm=None, lr_schedule=None,
-                 skip_nonfinite: bool = False, accumulate_grad_batches: int = 1):
+                 skip_nonfinite: bool = False, accumulate_grad_batches: int = 1, ema_decay=None, ema_start_step: int = 1):
         """``max_grad_norm`` / ``lr_schedule`` (an ``ops.LRSchedule``) / ``skip_nonfinite``: the optimizer controls of
         ``ops.AdamWFlat``, decided on the device inside the captured step.  A schedule given here never re-records anything
         and never evicts the optimizer from the graph; setting ``opt.lr`` by hand keeps doing both (see ``_optimizer_changed``).
@@ -421,7 +421,12 @@ class Trainer:
         call opens or closes a window (``AdamWFlat(accumulate=K)``): the recorded step is the same for every micro-step, nothing
         is re-recorded, and eager and replayed micro-steps may mix inside a window.  The host decides only where the gradient
         exchange goes out (world > 1: on the closing micro-step) -- and everything for an ``optimizer_factory`` optimizer,
-        which has no device gate and therefore needs ``use_graph=False``."""
+        which has no device gate and therefore needs ``use_graph=False``.
+
+        ``ema_decay`` / ``ema_start_step``: an exponential moving average of the weights (Lightning's ``EMAWeightAveraging``
+        over ``AveragedModel``), kept by the AdamW update launch of ``ops.AdamWFlat`` inside the captured step: no launch
+        more, nothing re-recorded, untouched by a skipped step and by the micro-batches inside a window.  ``ema_state_dict()``
+        gives the averaged weights, ``with tr.ema_weights():`` evaluates under them, checkpoints carry them."""
         import os
 
         if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
@@ -464,9 +469,12 @@ class Trainer:
 
             self.opt = AdamWFlat(self.fp.flat, self.fp.grad, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                  max_grad_norm=max_grad_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite,
-                                 accumulate=self.accumulate_grad_batches)
+                                 accumulate=self.accumulate_grad_batches, ema_decay=ema_decay, ema_start_step=ema_start_step)
             self._device_gate = self.accumulate_grad_batches > 1
         else:
+            if ema_decay is not None:
+                raise ValueError("ema_decay / ema_start_step are options of the built-in AdamWFlat: an optimizer_factory builds "
+                                 "its own optimizer")
             if max_grad_norm is not None or lr_schedule is not None or skip_nonfinite:
                 raise ValueError("max_grad_norm / lr_schedule / skip_nonfinite are options of the built-in AdamWFlat: an "
                                  "optimizer_factory builds its own optimizer")
@@ -914,6 +922,7 @@ class Trainer:
             self._opt_step(self._static_loss)
 
     def step(self, *batch):
+        self._refuse_inside_ema_weights("step")
         if self.use_graph:
             return self._graph_step(*batch)
         if self.accumulate_grad_batches > 1:
@@ -959,6 +968,7 @@ class Trainer:
 
         ``standardize=True`` folds on_after_batch_transfer into that launch: the module must then NOT standardise again
         (``ForecasterStep(standardize=False)``).  Returns the loss; ``self.batch_times`` holds the target times."""
+        self._refuse_inside_ema_weights("step_from")
         if getattr(self.module, "standardize_inputs", False) and standardize:
             raise ValueError("the module standardises its inputs itself: pass standardize=False or build it with standardize=False")
         if self.use_graph and self._graph is not None:
@@ -1008,6 +1018,67 @@ class Trainer:
             return self.opt.step_count()
         return self.opt.t
 
+    # ---- weight averaging (ops.AdamWFlat(ema_decay=...)) ----
+    _ema_swapped = False   # inside ``ema_weights()``: the flat parameter buffer holds the average, ``opt.ema`` the raw weights
+
+    def _ema_buffer(self):
+        ema = getattr(self.opt, "ema", None)
+        if ema is None:
+            raise RuntimeError("this trainer keeps no moving average of the weights: build it with ema_decay=...")
+        return ema
+
+    def _refuse_inside_ema_weights(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): the parameter buffer holds the averaged weights; leave the block first")
+
+    def ema_state_dict(self) -> dict:
+        """The module's ``state_dict()`` on the CPU with every trainable parameter replaced by its moving average (buffers and
+        frozen parameters as they are): what ``load_state_dict`` of a reference module takes."""
+        from .checkpoint import export_flat_params, module_state_to_cpu
+
+        self._refuse_inside_ema_weights("ema_state_dict")
+        names, shapes, offsets = self._layout()
+        out = module_state_to_cpu(self.module)
+        out.update(export_flat_params(names, shapes, offsets, self._ema_buffer()))
+        return out
+
+    def _weights_changed_in_place(self):
+        """A raw kernel rewrote the flat parameter buffer: torch's version counters are advanced by hand (what the caches
+        keyed on them compare) and an embedding cache of static features computed from the old weights is dropped."""
+        bump = torch.autograd.graph.increment_version
+        for t in (self.fp.flat, self._ema_buffer(), *self.fp.params):
+            bump(t)
+        for m in self.module.modules():
+            if getattr(m, "_static", None) is not None:
+                m._static = None
+
+    def _swap_ema(self):
+        from . import _lib as L
+
+        flat, ema = self.fp.flat, self._ema_buffer()
+        L.check(L.load().nlam_flat_swap(flat.data_ptr(), ema.data_ptr(), flat.numel(), torch.cuda.current_stream().cuda_stream),
+                "nlam_flat_swap")
+        self._weights_changed_in_place()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate (or export) under the averaged weights: the flat parameter buffer and the average are exchanged IN PLACE
+        by one launch (``nlam_flat_swap``) and exchanged back on exit, exceptions included.  No buffer is rebound, so captured
+        training and evaluation graphs stay valid and read the averaged weights inside the block; packed weight images are
+        rewritten from the weights by the step that uses them.  Training inside the block is refused."""
+        self._ema_buffer()
+        self._refuse_inside_ema_weights("ema_weights()")
+        if self.micro_step != 0:
+            raise RuntimeError(f"ema_weights() inside an accumulation window (micro-batch {self.micro_step} of "
+                               f"{self.accumulate_grad_batches}): the weights are exchanged at a window boundary")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False
+
     # ---- checkpoints (checkpoint.save_checkpoint / load_checkpoint) ----
     def _flat_adamw(self):
         ops = self._ops()
@@ -1023,9 +1094,10 @@ class Trainer:
     def state_dict(self) -> dict:
         """``{"state_dict", "optimizer_states": [sd]}`` with CPU tensors; ``sd`` is what ``torch.optim.AdamW`` over the
         reference module's parameters would hold (one entry per parameter, in ``named_parameters()`` order)."""
-        from .checkpoint import NAMESPACE, export_flat_state, module_state_to_cpu
+        from .checkpoint import NAMESPACE, export_flat_params, export_flat_state, module_state_to_cpu
 
         opt = self._flat_adamw()
+        self._refuse_inside_ema_weights("state_dict()")
         if self.micro_step != 0:
             raise RuntimeError(f"state_dict() inside an accumulation window (micro-batch {self.micro_step} of "
                                f"{self.accumulate_grad_batches}): a checkpoint is taken at a window boundary, the reference "
@@ -1044,6 +1116,10 @@ class Trainer:
                 "max_grad_norm": opt.max_grad_norm, "skip_nonfinite": opt.skip_nonfinite, "skipped_steps": opt.skipped_steps}}
             if self.accumulate_grad_batches > 1:
                 out[NAMESPACE]["optimizer_controls"]["accumulate_grad_batches"] = self.accumulate_grad_batches
+        if opt.ema is not None:
+            # the averaged weights, per parameter under the reference's names: beside the reference-layout parts, not in them
+            out.setdefault(NAMESPACE, {})["ema"] = {"decay": opt.ema_decay, "start_step": opt.ema_start_step,
+                                                    "state_dict": export_flat_params(names, shapes, offsets, opt.ema)}
         return out
 
     def load_state_dict(self, ckpt: dict, restore_opt: bool = True, strict: bool = True):
@@ -1056,11 +1132,20 @@ class Trainer:
         with optimizer controls also restores the base learning rate and the skipped-steps count; one written without them
         loads as before.
         ``restore_opt=False``: weights only; step 0, zero moments and the hyper-parameters the trainer was built with.
+        A trainer with ``ema_decay``: the checkpoint's average is restored in place, bit for bit (its decay and start step are
+        checked against this trainer's, which go on holding); a checkpoint without one, and ``restore_opt=False``, start the
+        average at the loaded weights.  A trainer without ``ema_decay`` ignores a checkpoint's average.
         At world > 1 every rank loads, and one all-reduce of a checksum checks that the ranks hold the same state."""
-        from .checkpoint import NAMESPACE, import_flat_state, load_module_weights, reorder_optimizer_state
+        from .checkpoint import NAMESPACE, import_flat_params, import_flat_state, load_module_weights, reorder_optimizer_state
 
         opt = self._flat_adamw()
+        self._refuse_inside_ema_weights("load_state_dict()")
         names, shapes, offsets = self._layout()
+        saved_ema = None
+        if getattr(opt, "ema", None) is not None and restore_opt:
+            saved_ema = (ckpt.get(NAMESPACE) or {}).get("ema")
+            if saved_ema is not None:   # validated before anything is written
+                import_flat_params(saved_ema["state_dict"], names, shapes, offsets, None, self.module.state_dict().keys())
         sd = None
         if restore_opt:
             states = ckpt.get("optimizer_states")
@@ -1077,6 +1162,19 @@ class Trainer:
                 opt.v.zero_()
             t, hyper = 0, self._built_hyper
         load_module_weights(self.module, ckpt["state_dict"], strict=strict)
+        if getattr(opt, "ema", None) is not None:
+            import warnings
+
+            with torch.no_grad():
+                opt.ema.copy_(self.fp.flat)
+            if saved_ema is not None:
+                import_flat_params(saved_ema["state_dict"], names, shapes, offsets, opt.ema, self.module.state_dict().keys())
+                theirs, mine = (float(saved_ema["decay"]), int(saved_ema["start_step"])), (opt.ema_decay, opt.ema_start_step)
+                if theirs != mine:
+                    warnings.warn(f"the checkpoint's weight average was kept with (decay, start step) = {theirs}, this trainer "
+                                  f"runs {mine}: the run continues under this trainer's")
+            elif restore_opt:
+                warnings.warn("the checkpoint holds no weight average: this trainer's starts at the loaded weights")
         opt.t = t
         opt.t_dev.fill_(t)
         opt.lr, opt.betas, opt.eps, opt.wd = hyper["lr"], tuple(hyper["betas"]), hyper["eps"], hyper["weight_decay"]
@@ -1113,13 +1211,17 @@ class Trainer:
             self._check_ranks_agree()
 
     def _check_ranks_agree(self):
-        """One all-reduce (MAX of the checksums and of their negatives): every rank must hold the same weights and moments."""
+        """One all-reduce (MAX of the checksums and of their negatives): every rank must hold the same weights, moments and
+        (with ``ema_decay``) weight average."""
         opt = self.opt
-        c = torch.stack([self.fp.flat.double().sum(), (self.fp.flat.double() ** 2).sum(), opt.m.double().sum(),
-                         opt.v.double().sum(), opt.t_dev.double().sum()])
+        sums = [self.fp.flat.double().sum(), (self.fp.flat.double() ** 2).sum(), opt.m.double().sum(), opt.v.double().sum(),
+                opt.t_dev.double().sum()]
+        if getattr(opt, "ema", None) is not None:   # every rank averages the same parameters: the averages agree too
+            sums += [opt.ema.double().sum(), (opt.ema.double() ** 2).sum()]
+        c = torch.stack(sums)
         both = torch.cat([c, -c])
         dist.all_reduce(both, op=dist.ReduceOp.MAX, group=self.buckets.group)
-        if not torch.equal(both[:5], -both[5:]):
+        if not torch.equal(both[: len(sums)], -both[len(sums) :]):
             raise ValueError("after loading the checkpoint the ranks hold different weights / optimizer state")
 
 
