@@ -45,6 +45,9 @@
  *       (and wmse), per-variable or per-entry (predicted) std, the same reduction; the step-tail pair fuses
  *       them into the AR step's state update: the kernels of nlam_step_tail_fwd / _bwd, instantiated on the kind's
  *       loss term and its std where those two take inv_var = 1 / std^2.
+ *   nlam_step_tail_ext_fwd, nlam_step_tail_ext_bwd
+ *       that step tail with the output clamps of get_clamped_new_state (step_predictors/base.py) and / or the softplus
+ *       of a predicted std (output_std) inside the pass; the loss term takes the predicted std per entry.
  *   nlam_eval_metrics, nlam_eval_workspace_floats
  *       the evaluation tensors of validation_step / test_step (models/module.py:546-576, :607-681): per-step loss,
  *       per-variable masked MSE / MAE / mean std, per-node loss maps; one pass over the rollout + a fixed-order reduction.
@@ -644,6 +647,63 @@ int32_t nlam_step_tail_loss_fwd(int32_t kind, const float* delta, const float* p
 int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* gloss, const float* pred, const float* target,
                                 const float* dstd, const float* bmask, const float* var_std, const float* row_weight, float scale,
                                 float* d_delta, float* d_prev, int64_t rows, int32_t nodes, int32_t width, void* hip_stream);
+
+/* The step tail with the two options of a step predictor that the pair above leaves out, still one pass each way:
+ * output clamping (StepPredictor.get_clamped_new_state, step_predictors/base.py) and a predicted std (output_std).
+ * Per element (row, f), n = row % nodes, F = nvars, ld = delta_ld (F, or 2 F with a std head):
+ *   r    = delta[row * ld + f] * dstd[f] + dmean[f]
+ *   new  = prev + r                                                                   NLAM_CLAMP_NONE
+ *        = lo + (hi - lo) * sigmoid(log(u / (1 - u)) + r), u = clamp((prev - lo) / (hi - lo), 1e-6, 1 - 1e-6)   NLAM_CLAMP_BOTH
+ *        = lo + softplus(inv_softplus(prev - lo) + r)                                 NLAM_CLAMP_LOWER
+ *        = hi - softplus(inv_softplus(hi - prev) - r)                                 NLAM_CLAMP_UPPER
+ *   pred = bmask[n] * truth + (1 - bmask[n]) * new
+ *   std  = softplus(delta[row * ld + F + f])        -> pred_std (rows, F), with a std head
+ *   loss += scale * row_weight[n] * entry(pred - target; consts[f], or this element's std)
+ * softplus (beta 1, threshold 20) and inv_softplus (utils/tensor.py, lower clamp log(float32(1 + 1e-6))) are torch's, and the
+ * backward gives the derivatives autograd gives that formulation (0 through a clamp outside its bounds).  lo / hi are the
+ * standardised limits, lo < hi is the caller's contract; entries of variables without that limit are not read.
+ * Forward: target == NULL and partials == NULL means no loss term (inference); otherwise one partial per block as above.
+ * Backward: writes d_prev (may be NULL) and the whole d_delta (rows, ld): the mean half G * d new / d r * dstd[f] with
+ * G = (1 - bmask[n]) * (g_pred + scale * gloss * row_weight[n] * d entry / d pred), and the std half
+ * (g_std + scale * gloss * row_weight[n] * d entry / d std) * softplus'(raw), written also where it is zero.  g_pred and
+ * g_std may be NULL; with target == NULL the loss took no part and gloss is not read.
+ * clamp_mode_host is HOST memory, read during the call (a captured launch keeps its values): the library checks it and hands the
+ * modes to the kernel with its arguments.  Every other pointer is device memory.  NLAM_EINVAL / NLAM_EUNSUP before any launch. */
+#define NLAM_CLAMP_NONE  0
+#define NLAM_CLAMP_BOTH  1
+#define NLAM_CLAMP_LOWER 2
+#define NLAM_CLAMP_UPPER 3
+typedef struct {
+    const float* delta;          /* (rows, delta_ld) the network output */
+    const float* prev;           /* (rows, nvars) */
+    const float* truth;          /* forward: (rows, nvars) the boundary forcing */
+    const float* target;         /* (rows, nvars), or NULL: no loss term */
+    const float* dstd;           /* (nvars) or NULL (1) */
+    const float* dmean;          /* (nvars) or NULL (0) */
+    const float* bmask;          /* (nodes) */
+    const float* row_weight;     /* (nodes), read with a loss term */
+    const float* consts;         /* (nvars) the per-variable std; NULL with a std head or for mse / mae */
+    const int32_t* clamp_mode_host;   /* HOST (nvars) NLAM_CLAMP_*, or NULL: none */
+    const float* clamp_lo;       /* (nvars) */
+    const float* clamp_hi;       /* (nvars) */
+    float* pred;                 /* (rows, nvars): written by the forward, read by the backward (with a loss term) */
+    float* pred_std;             /* (rows, nvars) likewise; non-NULL exactly when delta_ld == 2 * nvars */
+    float* partials;             /* forward: (nparts), NULL exactly when target is */
+    const float* g_pred;         /* backward: (rows, nvars) or NULL */
+    const float* g_std;          /* backward: (rows, nvars) or NULL (std head only) */
+    const float* gloss;          /* backward: the scalar gradient of the loss (device), read with a loss term */
+    float* d_delta;              /* backward: (rows, delta_ld) */
+    float* d_prev;               /* backward: (rows, nvars) or NULL */
+    int64_t rows;
+    int32_t nodes;
+    int32_t nvars;               /* <= NLAM_LOSS_MAX_VARS */
+    int32_t delta_ld;            /* nvars or 2 * nvars */
+    int32_t kind;                /* NLAM_LOSS_* (a valid one also without a loss term) */
+    int32_t nparts;
+    float scale;
+} nlam_step_tail_t;
+int32_t nlam_step_tail_ext_fwd(const nlam_step_tail_t* p, void* hip_stream);
+int32_t nlam_step_tail_ext_bwd(const nlam_step_tail_t* p, void* hip_stream);
 
 /* The evaluation metrics of validation_step / test_step (models/module.py:491-504, :546-576, :607-681) over a rollout,
  * pred / target / std (batch * steps * nodes, nvars) fp32, with "masked grid mean" = sum_n row_weight[n] * x (row_weight =

@@ -42,6 +42,8 @@ TILE_SPLIT = 1 << 30
 LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
 LOSS_MSE, LOSS_MAE, LOSS_WMSE, LOSS_WMAE, LOSS_NLL, LOSS_CRPS_GAUSS = 1, 2, 3, 4, 5, 6
 LOSS_MAX_VARS = 4096
+# NLAM_CLAMP_*: the output clamp of one state variable (nlam_step_tail_t.clamp_mode_host)
+CLAMP_NONE, CLAMP_BOTH, CLAMP_LOWER, CLAMP_UPPER = 0, 1, 2, 3
 EVAL_MAX_MAPS = 32    # NLAM_EVAL_MAX_MAPS: lead times of one nlam_eval_metrics call's loss maps
 EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
 MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
@@ -109,6 +111,8 @@ EXPORTS = [
     "nlam_loss_bwd",
     "nlam_step_tail_loss_fwd",
     "nlam_step_tail_loss_bwd",
+    "nlam_step_tail_ext_fwd",
+    "nlam_step_tail_ext_bwd",
     "nlam_eval_metrics",
     "nlam_eval_workspace_floats",
     "nlam_concat",
@@ -396,6 +400,40 @@ class Loss(C.Structure):
     ]
 
 
+class StepTail(C.Structure):
+    """nlam_step_tail_t; ``clamp_mode_host`` points at HOST memory (an ``(C.c_int32 * nvars)`` array the caller keeps alive)."""
+
+    _fields_ = [
+        ("delta", C.c_void_p),
+        ("prev", C.c_void_p),
+        ("truth", C.c_void_p),
+        ("target", C.c_void_p),
+        ("dstd", C.c_void_p),
+        ("dmean", C.c_void_p),
+        ("bmask", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("consts", C.c_void_p),
+        ("clamp_mode_host", C.c_void_p),
+        ("clamp_lo", C.c_void_p),
+        ("clamp_hi", C.c_void_p),
+        ("pred", C.c_void_p),
+        ("pred_std", C.c_void_p),
+        ("partials", C.c_void_p),
+        ("g_pred", C.c_void_p),
+        ("g_std", C.c_void_p),
+        ("gloss", C.c_void_p),
+        ("d_delta", C.c_void_p),
+        ("d_prev", C.c_void_p),
+        ("rows", C.c_int64),
+        ("nodes", C.c_int32),
+        ("nvars", C.c_int32),
+        ("delta_ld", C.c_int32),
+        ("kind", C.c_int32),
+        ("nparts", C.c_int32),
+        ("scale", C.c_float),
+    ]
+
+
 class Eval(C.Structure):
     _fields_ = [
         ("pred", C.c_void_p),
@@ -599,6 +637,10 @@ def load():
     lib.nlam_loss_fwd.restype = i32
     lib.nlam_loss_bwd.argtypes = [C.POINTER(Loss), vp]
     lib.nlam_loss_bwd.restype = i32
+    lib.nlam_step_tail_ext_fwd.argtypes = [C.POINTER(StepTail), vp]
+    lib.nlam_step_tail_ext_fwd.restype = i32
+    lib.nlam_step_tail_ext_bwd.argtypes = [C.POINTER(StepTail), vp]
+    lib.nlam_step_tail_ext_bwd.restype = i32
     lib.nlam_step_tail_loss_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i64, i32, i32, vp]
     lib.nlam_step_tail_loss_fwd.restype = i32
     lib.nlam_step_tail_loss_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]

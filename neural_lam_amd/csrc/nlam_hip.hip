@@ -3653,6 +3653,255 @@ __global__ __launch_bounds__(256) void step_tail_bwd_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------
+// The extended step tail (nlam_step_tail_ext_fwd / _bwd): the tail above plus the output clamps of
+// StepPredictor.get_clamped_new_state (HAS_CLAMP) and the predicted std of an output_std model (HAS_STD: delta is
+// (rows, 2 * width), its second half the raw std; the loss term then takes this element's std instead of the variable's).
+// The formulas are torch's, operation for operation (softplus: beta 1, threshold 20; utils/tensor.py inverse_softplus /
+// inverse_sigmoid), and so are the derivatives: zero through a clamp outside its bounds, one on the branch above the threshold.
+// ---------------------------------------------------------------------------
+constexpr float kIspLow = 0x1.fffffp-21f;       // log(float32(1 + 1e-6)) as torch evaluates it in fp32: inverse_softplus' lower clamp
+constexpr float kSigLow = 1e-6f;                // inverse_sigmoid's clamp, (float)1e-6 and (float)(1 - 1e-6)
+constexpr float kSigHigh = 0x1.ffffdep-1f;
+constexpr float kSoftplusThreshold = 20.f;
+
+// the kernel argument: the caller's struct and its (host) clamp modes, two bits per variable
+struct StepTailExtArgs {
+    nlam_step_tail_t p;
+    uint32_t mode_bits[NLAM_LOSS_MAX_VARS / 16];
+};
+
+__device__ __forceinline__ float softplus_fwd(float z) { return z > kSoftplusThreshold ? z : log1pf(expf(z)); }
+__device__ __forceinline__ float softplus_grad(float z) { return z > kSoftplusThreshold ? 1.f : 1.f / (1.f + expf(-z)); }
+
+// inverse_softplus(y) and its derivative dy
+__device__ __forceinline__ float inv_softplus(float y, float& dy) {
+    const float yc = fminf(fmaxf(y, kIspLow), kSoftplusThreshold);
+    const float em = expm1f(yc);
+    dy = y > kSoftplusThreshold ? 1.f : (y >= kIspLow ? (em + 1.f) / em : 0.f);
+    return y > kSoftplusThreshold ? y : logf(em);
+}
+
+// the new state of one element from prev and the rescaled delta r, with dr = d new / d r and dp = d new / d prev
+__device__ __forceinline__ float clamped_new(int mode, float pv, float r, float lo, float hi, float& dr, float& dp) {
+    if (mode == NLAM_CLAMP_NONE) {
+        dr = dp = 1.f;
+        return pv + r;
+    }
+    if (mode == NLAM_CLAMP_BOTH) {
+        const float span = hi - lo;
+        const float x = (pv - lo) / span;
+        const float u = fminf(fmaxf(x, kSigLow), kSigHigh);
+        const float s = 1.f / (1.f + expf(-(logf(u / (1.f - u)) + r)));
+        const float k = s * (1.f - s);
+        dr = span * k;
+        dp = (x >= kSigLow && x <= kSigHigh) ? k / (u * (1.f - u)) : 0.f;
+        return lo + span * s;
+    }
+    const bool lower = mode == NLAM_CLAMP_LOWER;
+    float dy;
+    const float inv = inv_softplus(lower ? pv - lo : hi - pv, dy);
+    const float q = lower ? inv + r : inv - r;
+    dr = softplus_grad(q);
+    dp = dr * dy;
+    const float sp = softplus_fwd(q);
+    return lower ? lo + sp : hi - sp;
+}
+
+// the per-variable tables of one workgroup in dynamic LDS, staged once: (dstd, dmean), the loss constants of a per-variable
+// std, (lo, hi) and the clamp mode
+template <int KIND, bool HAS_CLAMP, bool HAS_STD>
+struct StepTailTables {
+    const float2* aff;
+    const float2* lc;
+    const float2* lim;
+    const int* mode;
+    __device__ __forceinline__ StepTailTables(const StepTailExtArgs& a) {
+        extern __shared__ __attribute__((aligned(16))) float smem[];
+        const nlam_step_tail_t& p = a.p;
+        const int F = p.nvars;
+        float2* const aff_w = reinterpret_cast<float2*>(smem);
+        float2* const lc_w = aff_w + F;
+        float2* const lim_w = lc_w + F;
+        int* const mode_w = reinterpret_cast<int*>(lim_w + F);
+        for (int v = threadIdx.x; v < F; v += blockDim.x) {
+            aff_w[v] = make_float2(p.dstd != nullptr ? p.dstd[v] : 1.f, p.dmean != nullptr ? p.dmean[v] : 0.f);
+            float c0 = 0.f, c1 = 0.f;
+            if (!HAS_STD && p.consts != nullptr) loss_consts<KIND>(p.consts[v], c0, c1);
+            lc_w[v] = make_float2(c0, c1);
+            if constexpr (HAS_CLAMP) {
+                lim_w[v] = make_float2(p.clamp_lo[v], p.clamp_hi[v]);
+                mode_w[v] = (int)((a.mode_bits[v >> 4] >> (2 * (v & 15))) & 3u);
+            }
+        }
+        __syncthreads();
+        aff = aff_w;
+        lc = lc_w;
+        lim = lim_w;
+        mode = mode_w;
+    }
+    static size_t lds_bytes(int width) { return (size_t)width * (3 * sizeof(float2) + sizeof(int)); }
+};
+
+template <int KIND, bool HAS_CLAMP, bool HAS_STD>
+__global__ __launch_bounds__(256) void step_tail_ext_fwd_kernel(const StepTailExtArgs a) {
+    const StepTailTables<KIND, HAS_CLAMP, HAS_STD> tab(a);
+    const nlam_step_tail_t& p = a.p;
+    const int nodes = p.nodes, width = p.nvars, ld = p.delta_ld;
+    const long total = p.rows * width;
+    const bool small = total < (1L << 31);
+    const bool has_loss = p.target != nullptr;
+    const float* __restrict__ delta = p.delta;
+    const float* __restrict__ bmask = p.bmask;
+    const float* __restrict__ row_weight = p.row_weight;
+    // one element: the prediction (and its std) out, this element's weighted loss entry back
+    auto elem = [&](float dl, float raw, float pr, float tr, float tg, int f, int n, float& pv, float& sd) {
+        const float2 af = tab.aff[f];
+        const float r = dl * af.x + af.y;
+        float nw = pr + r;
+        if constexpr (HAS_CLAMP) {
+            const int m = tab.mode[f];
+            if (m != NLAM_CLAMP_NONE) {
+                float dr, dp;
+                const float2 l = tab.lim[f];
+                nw = clamped_new(m, pr, r, l.x, l.y, dr, dp);
+            }
+        }
+        const float bm = bmask[n];
+        pv = bm * tr + (1.f - bm) * nw;
+        sd = 0.f;
+        if constexpr (HAS_STD) sd = softplus_fwd(raw);
+        if (!has_loss) return 0.f;
+        const float w = row_weight[n];
+        if (w == 0.f) return 0.f;
+        float c0, c1;
+        if constexpr (HAS_STD) {
+            loss_consts<KIND>(sd, c0, c1);
+        } else {
+            const float2 c = tab.lc[f];
+            c0 = c.x;
+            c1 = c.y;
+        }
+        return w * loss_entry<KIND>(pv - tg, c0, c1);
+    };
+    float s = 0.f;
+    // 16-byte accesses of the (rows, width) operands, four elements per thread; with a std head the delta rows are twice as
+    // long, so its eight values of a quad are loaded one by one (before any of the transcendental work)
+    const bool vec = (total & 3) == 0 && small &&
+                     ((reinterpret_cast<uintptr_t>(p.prev) | reinterpret_cast<uintptr_t>(p.truth) | reinterpret_cast<uintptr_t>(p.pred) |
+                       reinterpret_cast<uintptr_t>(p.target) | reinterpret_cast<uintptr_t>(p.pred_std) |
+                       (HAS_STD ? 0 : reinterpret_cast<uintptr_t>(delta))) & 15) == 0;
+    if (vec) {
+        const unsigned nq = (unsigned)(total >> 2), nthr = gridDim.x * blockDim.x;
+        for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += nthr) {
+            const unsigned e = 4 * q;
+            const unsigned r = e / (unsigned)width;
+            int f = (int)(e - r * (unsigned)width);
+            int n = (int)(r % (unsigned)nodes);
+            const f32x4 pr = *reinterpret_cast<const f32x4*>(p.prev + e), tr = *reinterpret_cast<const f32x4*>(p.truth + e);
+            f32x4 tg = {0.f, 0.f, 0.f, 0.f}, dl, raw = {0.f, 0.f, 0.f, 0.f};
+            if (has_loss) tg = *reinterpret_cast<const f32x4*>(p.target + e);
+            if constexpr (HAS_STD) {
+                long di = (long)r * ld + f;
+                int fd = f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    dl[c] = delta[di];
+                    raw[c] = delta[di + width];
+                    ++di;
+                    if (++fd == width) {
+                        fd = 0;
+                        di += ld - width;
+                    }
+                }
+            } else {
+                dl = *reinterpret_cast<const f32x4*>(delta + e);
+            }
+            f32x4 pv4, sd4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float pv, sd;
+                s += elem(dl[c], raw[c], pr[c], tr[c], tg[c], f, n, pv, sd);
+                pv4[c] = pv;
+                sd4[c] = sd;
+                if (++f == width) {
+                    f = 0;
+                    if (++n == nodes) n = 0;
+                }
+            }
+            *reinterpret_cast<f32x4*>(p.pred + e) = pv4;
+            if constexpr (HAS_STD) *reinterpret_cast<f32x4*>(p.pred_std + e) = sd4;
+        }
+    }
+    for (long e0 = vec ? total : (long)blockIdx.x * blockDim.x; e0 < total; e0 += (long)gridDim.x * blockDim.x) {
+        const long e = e0 + threadIdx.x;
+        if (e < total) {
+            long r;
+            int n;
+            row_and_node(e, width, nodes, small, r, n);
+            const int f = (int)(e - r * width);
+            const long di = r * ld + f;
+            const float dl = delta[di], raw = HAS_STD ? delta[di + width] : 0.f;
+            const float pr = p.prev[e], tr = p.truth[e], tg = has_loss ? p.target[e] : 0.f;
+            float pv, sd;
+            s += elem(dl, raw, pr, tr, tg, f, n, pv, sd);
+            p.pred[e] = pv;
+            if constexpr (HAS_STD) p.pred_std[e] = sd;
+        }
+    }
+    if (has_loss) block_sum_to_partial(s, p.scale, p.partials);
+}
+
+// d_prev and the whole d_delta of one step from the gradients of its outputs (g_pred, g_std; either may be NULL) and of the loss
+template <int KIND, bool HAS_CLAMP, bool HAS_STD>
+__global__ __launch_bounds__(256) void step_tail_ext_bwd_kernel(const StepTailExtArgs a) {
+    const StepTailTables<KIND, HAS_CLAMP, HAS_STD> tab(a);
+    const nlam_step_tail_t& p = a.p;
+    const int nodes = p.nodes, width = p.nvars, ld = p.delta_ld;
+    const long total = p.rows * width;
+    const bool small = total < (1L << 31);
+    const bool has_loss = p.target != nullptr;
+    const float g = has_loss ? p.scale * p.gloss[0] : 0.f;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        long r;
+        int n;
+        row_and_node(e, width, nodes, small, r, n);
+        const int f = (int)(e - r * width);
+        const long di = r * ld + f;
+        const float dl = p.delta[di], raw = HAS_STD ? p.delta[di + width] : 0.f;
+        const float pr = p.prev[e];
+        float G = p.g_pred != nullptr ? p.g_pred[e] : 0.f;
+        float gs = HAS_STD && p.g_std != nullptr ? p.g_std[e] : 0.f;
+        const float w = has_loss ? p.row_weight[n] : 0.f;
+        const float d = has_loss ? p.pred[e] - p.target[e] : 0.f;
+        const float sd = HAS_STD && has_loss ? p.pred_std[e] : 1.f;
+        const float bm = p.bmask[n];
+        if (w != 0.f) {
+            if constexpr (HAS_STD) {
+                float c0, c1;
+                loss_consts<KIND>(sd, c0, c1);
+                G += g * w * loss_dpred<KIND>(d, c0);
+                gs += g * w * loss_dstd<KIND>(d, sd);
+            } else {
+                G += g * w * loss_dpred<KIND>(d, tab.lc[f].x);
+            }
+        }
+        G *= 1.f - bm;
+        const float2 af = tab.aff[f];
+        float dr = 1.f, dp = 1.f;
+        if constexpr (HAS_CLAMP) {
+            const int m = tab.mode[f];
+            if (m != NLAM_CLAMP_NONE) {
+                const float2 l = tab.lim[f];
+                clamped_new(m, pr, dl * af.x + af.y, l.x, l.y, dr, dp);
+            }
+        }
+        if (p.d_prev != nullptr) p.d_prev[e] = G * dp;
+        p.d_delta[di] = G * dr * af.x;
+        if constexpr (HAS_STD) p.d_delta[di + width] = gs * softplus_grad(raw);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // evaluation metrics (nlam_eval_metrics): the per-step loss, per-variable masked MSE / MAE / mean std and the per-node loss
 // maps of validation_step / test_step in one pass over the rollout.  A workgroup owns (batch, step, node chunk); its lanes
 // take 16-byte quads of the chunk with a stride of 4 * lanes elements, lanes a multiple of nvars, so every lane sees the
@@ -6572,6 +6821,68 @@ int32_t step_tail_bwd(int32_t kind, const float* g_pred, const float* gloss, con
     });
 }
 
+// nlam_step_tail_ext_fwd / _bwd: every check before any launch.  clamp_mode_host is host memory: its values are checked here and
+// travel to the kernel inside its argument.
+int32_t step_tail_ext_check(const nlam_step_tail_t* p, bool bwd) {
+    if (p == nullptr || !loss_kind_valid(p->kind)) return NLAM_EINVAL;
+    if (p->delta == nullptr || p->prev == nullptr || p->bmask == nullptr) return NLAM_EINVAL;
+    if (p->rows < 1 || p->nodes < 1 || p->nvars < 1 || p->rows % p->nodes != 0) return NLAM_EINVAL;
+    if (p->nvars > NLAM_LOSS_MAX_VARS) return NLAM_EUNSUP;
+    const bool has_std = p->delta_ld == 2 * p->nvars;
+    if ((p->delta_ld != p->nvars && !has_std) || has_std != (p->pred_std != nullptr)) return NLAM_EINVAL;
+    const bool has_loss = p->target != nullptr;
+    if (has_loss) {
+        if (p->row_weight == nullptr || p->pred == nullptr) return NLAM_EINVAL;
+        if (loss_reads_std(p->kind) && !has_std && p->consts == nullptr) return NLAM_EINVAL;
+    }
+    if (!bwd) {
+        if (p->truth == nullptr || p->pred == nullptr || has_loss != (p->partials != nullptr) || (has_loss && p->nparts < 1))
+            return NLAM_EINVAL;
+    } else {
+        if (p->d_delta == nullptr || (has_loss && p->gloss == nullptr) || (p->g_std != nullptr && !has_std)) return NLAM_EINVAL;
+    }
+    if (p->clamp_mode_host != nullptr) {
+        if (p->clamp_lo == nullptr || p->clamp_hi == nullptr) return NLAM_EINVAL;
+        for (int v = 0; v < p->nvars; ++v)
+            if (p->clamp_mode_host[v] < NLAM_CLAMP_NONE || p->clamp_mode_host[v] > NLAM_CLAMP_UPPER) return NLAM_EINVAL;
+    }
+    return 0;
+}
+
+int32_t step_tail_ext(const nlam_step_tail_t* p, bool bwd, void* hip_stream) {
+    if (const int32_t rc = step_tail_ext_check(p, bwd)) return rc;
+    StepTailExtArgs a;
+    a.p = *p;
+    memset(a.mode_bits, 0, sizeof(a.mode_bits));
+    bool clamp = false;
+    if (p->clamp_mode_host != nullptr)
+        for (int v = 0; v < p->nvars; ++v) {
+            a.mode_bits[v >> 4] |= (uint32_t)p->clamp_mode_host[v] << (2 * (v & 15));
+            clamp |= p->clamp_mode_host[v] != NLAM_CLAMP_NONE;
+        }
+    const bool has_std = p->pred_std != nullptr;
+    // neither option: the tail of nlam_step_tail_loss_fwd / _bwd, on its kernels (the same bits)
+    if (!clamp && !has_std && p->target != nullptr) {
+        if (!bwd)
+            return step_tail_fwd(p->kind, p->delta, p->prev, p->truth, p->target, p->dstd, p->dmean, p->bmask, p->consts, p->row_weight,
+                                 p->scale, p->pred, p->partials, p->nparts, p->rows, p->nodes, p->nvars, hip_stream);
+        return step_tail_bwd(p->kind, p->g_pred, p->gloss, p->pred, p->target, p->dstd, p->bmask, p->consts, p->row_weight, p->scale,
+                             p->d_delta, p->d_prev, p->rows, p->nodes, p->nvars, hip_stream);
+    }
+    const long total = (long)p->rows * p->nvars;
+    const int blocks = !bwd && p->target != nullptr ? p->nparts : elementwise_blocks(total, 2048);
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    return pick_loss(p->kind, [&](auto kind) {
+        return pick_bool(clamp, [&](auto hc) {
+            return pick_bool(has_std, [&](auto hs) {
+                const size_t lds = StepTailTables<kind, hc, hs>::lds_bytes(p->nvars);
+                if (!bwd) return launch<step_tail_ext_fwd_kernel<kind, hc, hs>>(dim3(blocks), dim3(256), lds, stream, a);
+                return launch<step_tail_ext_bwd_kernel<kind, hc, hs>>(dim3(blocks), dim3(256), lds, stream, a);
+            });
+        });
+    });
+}
+
 // nlam_eval_metrics: the chunks of a (batch, step) and the argument checks (before any launch)
 long eval_nchunks(int32_t nodes, int32_t nvars) { return (nodes + eval_chunk_nodes(nvars) - 1) / eval_chunk_nodes(nvars); }
 
@@ -6907,6 +7218,16 @@ int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* 
     if (!loss_kind_valid(kind)) return NLAM_EINVAL;
     return step_tail_bwd(kind, g_pred, gloss, pred, target, dstd, bmask, var_std, row_weight, scale, d_delta, d_prev, rows, nodes, width,
                          hip_stream);
+}
+
+int32_t nlam_step_tail_ext_fwd(const nlam_step_tail_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_step_tail_ext_fwd");
+    return step_tail_ext(p, false, hip_stream);
+}
+
+int32_t nlam_step_tail_ext_bwd(const nlam_step_tail_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_step_tail_ext_bwd");
+    return step_tail_ext(p, true, hip_stream);
 }
 
 int32_t nlam_eval_metrics(const nlam_eval_t* p, void* hip_stream) {

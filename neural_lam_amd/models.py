@@ -55,6 +55,10 @@ FUSED_STATE_UPDATE = True
 import os as _os
 
 FOLD_INPUT_CAT = _os.environ.get("NLAM_FOLD_CAT", "1") == "1"
+# output clamping and the predicted std inside the step-tail pass (ops.StepTailExtFunction); NLAM_FUSED_CLAMPED_TAIL=0 restores the
+# torch-op tail of such models (get_clamped_new_state, softplus, the loss pass over the rollout) for A/B runs.  On: at cfg2 size
+# 1.75 against 1.80 ms per step with a predicted std, 1.72 against 2.71 ms with three clamps (profiles/clamped_tail/README.md)
+FUSED_CLAMPED_TAIL = _os.environ.get("NLAM_FUSED_CLAMPED_TAIL", "1") == "1"
 # static-feature embedders (keys of static_embedding_specs: "mesh", "g2m", "m2g", "m2m", ..; "all") whose backward runs as soon as
 # the gradient of their output is complete instead of in the grouped launch at the very end of backward (NLAM_EARLY_EMB; default none)
 EARLY_EMBEDDER_BACKWARD = frozenset(k for k in _os.environ.get("NLAM_EARLY_EMB", "").split(",") if k)
@@ -82,6 +86,11 @@ class BufferList(nn.Module):
 
     def __iter__(self):
         return (self[i] for i in range(self.n_buffers))
+
+
+def _rebuild_clamp_tables(module, incompatible_keys):
+    """load_state_dict post hook of a StepPredictor (a module-level function: the module stays picklable)."""
+    module.clamp_tables()
 
 
 class StepPredictor(nn.Module):
@@ -140,6 +149,52 @@ class StepPredictor(nn.Module):
         self.register_buffer("clamp_lower_upper_idx", torch.tensor(lu_idx))
         self.register_buffer("clamp_lower_idx", torch.tensor(lo_idx))
         self.register_buffer("clamp_upper_idx", torch.tensor(hi_idx))
+        # the kernel's tables follow the buffers: built here, after every .to() / .float() (_apply) and after load_state_dict, so that
+        # no call inside a stream capture has to build them (the first build copies the index buffers to the host)
+        self.clamp_tables()
+        self.register_load_state_dict_post_hook(_rebuild_clamp_tables)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if hasattr(self, "clamp_upper_idx"):
+            self.clamp_tables()
+        return out
+
+    def __setstate__(self, state):
+        # copy.deepcopy / unpickling: the copied tables are keyed on the original's buffers, so build this module's own here
+        super().__setstate__(state)
+        self.__dict__.pop("_clamp_tables", None)
+        if hasattr(self, "clamp_upper_idx"):
+            self.clamp_tables()
+
+    def clamp_tables(self):
+        """The clamps as one per-variable table (ops.ClampTables: mode NLAM_CLAMP_* on the host, lo / hi standardised limits
+        where the model lives, 0 where a variable has no such limit), None for a model without clamps.  Built from the buffers
+        prepare_clamping_params registers, there and whenever they are replaced or written (``_apply``, ``load_state_dict``); the
+        key below only catches a buffer written by hand, and rebuilding then synchronises with the device."""
+        from ._lib import CLAMP_BOTH, CLAMP_LOWER, CLAMP_UPPER
+        from .ops import ClampTables
+
+        bufs = (self.clamp_lower_upper_idx, self.clamp_lower_idx, self.clamp_upper_idx, self.sigmoid_lower_lims,
+                self.sigmoid_upper_lims, self.softplus_lower_lims, self.softplus_upper_lims)
+        if sum(b.numel() for b in bufs[:3]) == 0:
+            return None
+        key = tuple((id(b), b._version) for b in bufs)
+        cached = getattr(self, "_clamp_tables", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        lu, lo_i, hi_i = (b.long() for b in bufs[:3])
+        n = self.state_mean.shape[0]
+        modes = torch.zeros(n, dtype=torch.int32)
+        lo = torch.zeros(n, dtype=torch.float32, device=self.state_mean.device)
+        hi = torch.zeros_like(lo)
+        modes[lu.cpu()], modes[lo_i.cpu()], modes[hi_i.cpu()] = CLAMP_BOTH, CLAMP_LOWER, CLAMP_UPPER
+        lo[lu], hi[lu] = bufs[3].float(), bufs[4].float()
+        lo[lo_i] = bufs[5].float()
+        hi[hi_i] = bufs[6].float()
+        tables = ClampTables(modes.tolist(), lo, hi)
+        self._clamp_tables = (key, tables)
+        return tables
 
     def get_clamped_new_state(self, state_delta, prev_state):
         sp = torch.nn.functional.softplus
@@ -304,6 +359,12 @@ class BaseGraphModel(StepPredictor):
         the forecaster may then fuse it with the boundary overwrite and the loss (ops.StepTailFunction)."""
         no_clamp = self.clamp_lower_upper_idx.numel() + self.clamp_lower_idx.numel() + self.clamp_upper_idx.numel() == 0
         return no_clamp and not self.output_std and self.diff_std.dim() == 1
+
+    def can_fuse_ext_tail(self) -> bool:
+        """True when the step's tail has output clamps and / or a predicted std and may run as one pass with the boundary
+        overwrite and the loss term (ops.StepTailExtFunction on the raw network output); FUSED_CLAMPED_TAIL = False says no."""
+        no_clamp = self.clamp_lower_upper_idx.numel() + self.clamp_lower_idx.numel() + self.clamp_upper_idx.numel() == 0
+        return FUSED_CLAMPED_TAIL and (self.output_std or not no_clamp) and self.diff_std.dim() == 1
 
     def forward(self, prev_state, prev_prev_state, forcing, raw_delta: bool = False):
         B = prev_state.shape[0]
@@ -579,21 +640,57 @@ class ARForecaster(nn.Module):
     def predicts_std(self):
         return self.predictor.predicts_std
 
+    def takes_ext_tail(self, init_states, boundary_states) -> bool:
+        """Whether ``forward`` runs the tail of these inputs on ops.StepTailExtFunction: a predictor with output clamps or a
+        predicted std (``can_fuse_ext_tail``, never true together with ``can_return_raw_delta``), fp32 tensors on the GPU."""
+        return (FUSED_STATE_UPDATE and init_states.is_cuda and init_states.dtype == torch.float32
+                and boundary_states.dtype == torch.float32 and getattr(self.predictor, "can_fuse_ext_tail", lambda: False)())
+
     def forward(self, init_states, forcing_features, boundary_states, loss_spec=None):
         """``loss_spec = (target_states, inv_var (F,), row_weight (N,), scale)``: also return the training loss
         ``scale * sum_t sum_n,f row_weight * inv_var * (pred - target)^2`` as a third value, with each step's state
         update + boundary overwrite + loss term fused into one pass (ops.StepTailFunction) when the predictor's tail is
         the plain rescale (no clamping / predicted std).  ``loss_spec = (target_states, var_std (F,), row_weight (N,), scale,
         kind)`` with a ``_lib.LOSS_*`` kind: the same for that loss with the per-variable std ``var_std`` (the same
-        Function, ``kind`` given); the third value is None where the tail cannot be fused."""
+        Function, ``kind`` given); the third value is None where the tail cannot be fused.  A predictor with output
+        clamps or a predicted std (``can_fuse_ext_tail``) takes ops.StepTailExtFunction instead, with or without a ``loss_spec``: the
+        five-entry spec gives its loss term (``var_std`` None with a predicted std); the four-entry one is wmse, so it runs as
+        ``NLAM_LOSS_WMSE`` on the predicted std, or on ``var_std = inv_var ** -0.5`` (one small launch per call: hand in the std)."""
         prev_prev_state, prev_state = init_states[:, 0], init_states[:, 1]
         preds, stds = [], []
         cache = self.predictor.static_cache() if hasattr(self.predictor, "static_cache") else contextlib.nullcontext()
         fused_tail = (loss_spec is not None and FUSED_STATE_UPDATE and init_states.is_cuda and init_states.dtype == torch.float32
                       and boundary_states.dtype == torch.float32 and getattr(self.predictor, "can_return_raw_delta", lambda: False)())
+        ext_tail = self.takes_ext_tail(init_states, boundary_states)
         losses = []
+        if ext_tail and loss_spec is not None:
+            ext_spec = loss_spec
+            if len(loss_spec) == 4:   # the wmse form: the kind's entry takes a std
+                from ._lib import LOSS_WMSE
+
+                target, inv_var, row_weight, scale = loss_spec
+                ext_spec = (target, None if self.predictor.output_std else torch.rsqrt(inv_var), row_weight, scale, LOSS_WMSE)
         with cache:
             for i in range(forcing_features.shape[1]):
+                if ext_tail:
+                    from .ops import StepTailExtFunction
+
+                    delta, _ = self.predictor(prev_state, prev_prev_state, forcing_features[:, i], raw_delta=True)
+                    target_i = consts = row_weight = kind = None
+                    scale = 1.0
+                    if loss_spec is not None:
+                        target, consts, row_weight, scale, kind = ext_spec
+                        target_i = target[:, i]
+                    new_state, pred_std, loss_t = StepTailExtFunction.apply(
+                        delta.float(), prev_state, boundary_states[:, i], target_i, self.predictor.diff_std, self.predictor.diff_mean,
+                        self.boundary_mask.reshape(-1), consts, row_weight, scale, kind, self.predictor.clamp_tables())
+                    preds.append(new_state)
+                    if pred_std is not None:
+                        stds.append(pred_std)
+                    if loss_t is not None:
+                        losses.append(loss_t)
+                    prev_prev_state, prev_state = prev_state, new_state
+                    continue
                 if fused_tail:
                     from .ops import StepTailFunction
 
@@ -625,7 +722,7 @@ class ARForecaster(nn.Module):
 
         if loss_spec is not None:
             loss = None
-            if fused_tail:
+            if losses:
                 loss = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
             return _stack(preds), (_stack(stds) if stds else None), loss
         return _stack(preds), (_stack(stds) if stds else None)
@@ -802,7 +899,7 @@ class ForecasterStep(nn.Module):
             standardize = self.standardize_inputs
         if standardize:
             init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
-        if not self.default_loss:
+        if not self.default_loss or self._ext_tail(init_states, target_states):
             return self._forward_loss(init_states, target_states, forcing)
         if (self.inv_var is not None and init_states.is_cuda and FUSED_STATE_UPDATE and isinstance(self.forecaster, ARForecaster)):
             # rollout with every step's state update + boundary overwrite + loss term in one pass (one more in backward)
@@ -823,13 +920,19 @@ class ForecasterStep(nn.Module):
         time_step_loss = torch.mean(wmse(prediction, target_states, pred_std, mask=self.interior_index), dim=0)
         return prediction, torch.mean(time_step_loss)
 
+    def _ext_tail(self, init_states, boundary_states) -> bool:
+        """Whether the rollout of these inputs runs its tail on ops.StepTailExtFunction (ARForecaster.takes_ext_tail)."""
+        return isinstance(self.forecaster, ARForecaster) and self.forecaster.takes_ext_tail(init_states, boundary_states)
+
     def _forward_loss(self, init_states, target_states, forcing):
         """Every ``loss`` but wmse: the fused step tail (ops.StepTailFunction with the kind) where the predictor can return its raw delta,
-        the one-pass ops.LossFunction on the rollout otherwise (clamped or predicted-std models)."""
+        ops.StepTailExtFunction for a clamped or predicted-std model (wmse included: the kind's entry on the per-variable or the
+        predicted std), the one-pass ops.LossFunction on the rollout where neither applies (FUSED_CLAMPED_TAIL off)."""
         from ._lib import LOSS_MAE, LOSS_MSE
         from .ops import LossFunction
 
-        if self.per_var_std is not None and init_states.is_cuda and FUSED_STATE_UPDATE and isinstance(self.forecaster, ARForecaster):
+        fusable = self.per_var_std is not None or self._ext_tail(init_states, target_states)
+        if fusable and init_states.is_cuda and FUSED_STATE_UPDATE and isinstance(self.forecaster, ARForecaster):
             B, T = target_states.shape[0], target_states.shape[1]
             prediction, pred_std, loss = self.forecaster(
                 init_states, forcing, target_states,

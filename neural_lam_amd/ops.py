@@ -2336,6 +2336,95 @@ class StepTailFunction(torch.autograd.Function):
         return d_delta, d_prev, None, None, None, None, None, None, None, None, None
 
 
+class ClampTables:
+    """The per-variable output clamps of a step predictor as nlam_step_tail_t takes them: ``mode`` (F,) NLAM_CLAMP_* per
+    variable in host memory, ``lo`` / ``hi`` (F,) fp32 standardised limits on the device (0 where a variable has no such limit)."""
+
+    __slots__ = ("mode", "lo", "hi", "modes")
+
+    def __init__(self, modes, lo, hi):
+        self.modes = tuple(int(m) for m in modes)
+        self.mode = (C.c_int32 * len(self.modes))(*self.modes)
+        self.lo, self.hi = lo, hi
+
+    def __reduce__(self):   # the ctypes array is rebuilt from the modes: a module that holds its tables copies and pickles
+        return ClampTables, (self.modes, self.lo, self.hi)
+
+
+class StepTailExtFunction(torch.autograd.Function):
+    """StepTailFunction for a predictor with output clamping and / or a predicted std, still one pass each way
+    (nlam_step_tail_ext_fwd / _bwd; the formulas are in include/nlam_hip.h):
+
+    forward(delta (B, N, F | 2 F), prev, truth, target | None, dstd, dmean, bmask (N,), consts (F,) | None, row_weight (N,) | None,
+    scale, kind | None, clamp: ClampTables | None) -> (pred (B, N, F), pred_std (B, N, F) | None, loss_t scalar | None).
+    ``delta`` of width 2 F carries the raw std in its second half.  ``target=None``: no loss term (inference, evaluation, a loss
+    computed outside: the gradients then arrive through pred and pred_std).  ``consts`` is the per-variable std of ``kind``, None
+    with a predicted std and for mse / mae."""
+
+    @staticmethod
+    def _args(delta, prev, target, dstd, dmean, bmask, consts, row_weight, scale, kind, clamp, pred, pred_std):
+        B, N, F = prev.shape
+        p = L.StepTail()
+        p.delta, p.prev, p.target, p.dstd, p.dmean = _ptr(delta), _ptr(prev), _ptr(target), _ptr(dstd), _ptr(dmean)
+        p.bmask, p.row_weight, p.consts = _ptr(bmask), _ptr(row_weight), _ptr(consts)
+        if clamp is not None:
+            p.clamp_mode_host, p.clamp_lo, p.clamp_hi = C.addressof(clamp.mode), _ptr(clamp.lo), _ptr(clamp.hi)
+        p.pred, p.pred_std = _ptr(pred), _ptr(pred_std)
+        p.rows, p.nodes, p.nvars, p.delta_ld = B * N, N, F, delta.shape[-1]
+        p.kind, p.scale = (kind if kind is not None else L.LOSS_MSE), scale
+        return p
+
+    @staticmethod
+    def forward(ctx, delta, prev, truth, target, dstd, dmean, bmask, consts, row_weight, scale: float, kind=None, clamp=None):
+        lib = L.load()
+        tables = () if clamp is None else (clamp.lo, clamp.hi)
+        _require_gpu(*(t for t in (delta, prev, truth, target, dstd, dmean, bmask, consts, row_weight, *tables) if t is not None))
+        B, N, F = prev.shape
+        if delta.shape[-1] not in (F, 2 * F):
+            raise ValueError(f"StepTailExtFunction: delta of width {delta.shape[-1]} for {F} state variables")
+        if clamp is not None and len(clamp.modes) != F:
+            raise ValueError(f"StepTailExtFunction: {len(clamp.modes)} clamp modes for {F} state variables")
+        delta, prev, truth, target = map(_cont, (delta, prev, truth, target))
+        dev = prev.device
+        pred = torch.empty((B, N, F), device=dev, dtype=torch.float32)
+        pred_std = torch.empty((B, N, F), device=dev, dtype=torch.float32) if delta.shape[-1] == 2 * F else None
+        p = StepTailExtFunction._args(delta, prev, target, dstd, dmean, bmask, consts, row_weight, scale, kind, clamp, pred, pred_std)
+        p.truth = _ptr(truth)
+        loss = None
+        if target is None:
+            L.check(lib.nlam_step_tail_ext_fwd(C.byref(p), _stream()), "nlam_step_tail_ext_fwd")
+        else:
+            def launch(partials, nparts):
+                p.partials, p.nparts = partials, nparts
+                return lib.nlam_step_tail_ext_fwd(C.byref(p), _stream())
+
+            loss = _scalar_from_partials(dev, launch, "nlam_step_tail_ext_fwd")
+        ctx.save_for_backward(delta, prev, pred, pred_std, target, dstd, dmean, bmask, consts, row_weight, *tables)
+        ctx.scale, ctx.kind, ctx.clamp = scale, kind, clamp
+        ctx.set_materialize_grads(False)
+        return pred, pred_std, loss
+
+    @staticmethod
+    def backward(ctx, g_pred, g_std, g_loss):
+        delta, prev, pred, pred_std, target, dstd, dmean, bmask, consts, row_weight = ctx.saved_tensors[:10]
+        none = (None,) * 12
+        if (g_pred is None and g_std is None and g_loss is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return none
+        dev = prev.device
+        gl = None
+        if target is not None:
+            gl = g_loss.contiguous().to(torch.float32) if g_loss is not None else torch.zeros((), device=dev, dtype=torch.float32)
+        gp = g_pred.contiguous() if g_pred is not None else None
+        gs = g_std.contiguous() if g_std is not None else None
+        d_delta = torch.empty_like(delta)
+        d_prev = torch.empty_like(prev) if ctx.needs_input_grad[1] else None
+        p = StepTailExtFunction._args(delta, prev, target, dstd, dmean, bmask, consts, row_weight, ctx.scale, ctx.kind, ctx.clamp,
+                                      pred, pred_std)
+        p.g_pred, p.g_std, p.gloss, p.d_delta, p.d_prev = _ptr(gp), _ptr(gs), _ptr(gl), _ptr(d_delta), _ptr(d_prev)
+        L.check(L.load().nlam_step_tail_ext_bwd(C.byref(p), _stream()), "nlam_step_tail_ext_bwd")
+        return (d_delta if ctx.needs_input_grad[0] else None, d_prev) + none[2:]
+
+
 class LossFunction(torch.autograd.Function):
     """``mean_t mean_b metrics.<kind>(pred, target, std, interior mask)`` as one pass each way (nlam_loss_fwd / _bwd) for every
     ``--loss`` kind (``_lib.LOSS_*``).  The std is per entry (``pred_std``, an output_std model's prediction) or, with
