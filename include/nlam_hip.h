@@ -334,6 +334,10 @@ int32_t nlam_max_width(void);
  *   16 .. 1024: values above 256 oversubscribe the CUs; set before the first launch of a step is recorded -- nlam_mlp_bwd_blocks
  *   follows it.  Measured (profiles/round6/ab_chain_cus.log): 192 .. 240 lose 1.5-5 %, 384 .. 1024 lose 0.5-5 %). */
 #define NLAM_TUNE_CHAIN_CUS 13
+/*   NLAM_TUNE_WGRAD_DMA_R: 32-row chunks wgrad_dma_kernel (m and every source width <= 64) requests behind one barrier: 1, 2 or
+ *   4, clamped to what the LDS holds for the launch's source count (4 with one source, 2 with two or three); 0 (default) = the
+ *   built-in choice per source count.  The partial sums are bit-identical for every value: a speed knob for A/B runs. */
+#define NLAM_TUNE_WGRAD_DMA_R 14
 int32_t nlam_set_tuning(int32_t key, int32_t value);
 /* Scratch the wide kernels need for the packed (MFMA A-operand order) weights of this
  * call; 0 when the call runs on the narrow (weights-in-LDS) kernels. */

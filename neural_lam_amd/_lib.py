@@ -35,6 +35,7 @@ TUNE_WGRAD_LDMA_VAR = 10
 TUNE_WBF_EDGE = 11
 TUNE_WGRAD_MAX_WGS = 12
 TUNE_CHAIN_CUS = 13
+TUNE_WGRAD_DMA_R = 14
 # nlam_wgrad_plan codes (include/nlam_hip.h): the kernel family nlam_wgrad launches
 WGP_SMALLN, WGP_DMA, WGP_NARROW, WGP_WIDE, WGP_WBF, WGP_WBF_BIG, WGP_WBF_B, WGP_WBF_B_BIG, WGP_LDMA_B, WGP_LDMA_1, WGP_LDMA_3 = range(1, 12)
 TILE_SPLIT = 1 << 30
@@ -717,6 +718,8 @@ def load():
         check(lib.nlam_set_tuning(TUNE_WBF_EDGE, int(os.environ["NLAM_WBF_EDGE"])), "nlam_set_tuning(NLAM_WBF_EDGE)")
     if os.environ.get("NLAM_WGRAD_LDMA_VAR"):
         check(lib.nlam_set_tuning(TUNE_WGRAD_LDMA_VAR, int(os.environ["NLAM_WGRAD_LDMA_VAR"])), "nlam_set_tuning(NLAM_WGRAD_LDMA_VAR)")
+    if os.environ.get("NLAM_WGRAD_DMA_R"):
+        check(lib.nlam_set_tuning(TUNE_WGRAD_DMA_R, int(os.environ["NLAM_WGRAD_DMA_R"])), "nlam_set_tuning(NLAM_WGRAD_DMA_R)")
     if os.environ.get("NLAM_CHAIN_CUS"):
         check(lib.nlam_set_tuning(TUNE_CHAIN_CUS, int(os.environ["NLAM_CHAIN_CUS"])), "nlam_set_tuning(NLAM_CHAIN_CUS)")
     if os.environ.get("NLAM_WGRAD_MAX_WGS"):

@@ -110,6 +110,7 @@ extern int chain_cus;                                              // persistent
 extern int wgrad_max_wgs;                                          // workgroups of a big split-bf16 weight gradient (NLAM_TUNE_WGRAD_MAX_WGS)
 extern int wbf_edge;                                               // mlp_fwd_edge_kernel for the factorised one-term edge layers (NLAM_TUNE_WBF_EDGE)
 extern int wgrad_ldma_var;                                         // its (rows per stage, ring depth) variant (NLAM_TUNE_WGRAD_LDMA_VAR)
+extern int wgrad_dma_r;                                            // chunks per barrier interval of wgrad_dma_kernel, 0 = per source count (NLAM_TUNE_WGRAD_DMA_R)
 extern int wgrad_min_parts;                                        // nlam_set_tuning (defined in slice 1)
 extern int wgrad_min_parts_wide;                                   // the same for weight matrices of more than 128 rows
 extern int wgrad_big_min_rows;                                     // nlam_set_tuning (defined in slice 1)
@@ -2650,17 +2651,27 @@ constexpr int kWgTile = kWgradRows * 64;  // floats in one [32 rows][64 cols] LD
 
 
 // Fast path: m <= 64, every source width <= 64, all multiples of 4.
-// LDS holds, per buffer, one [32][64] tile for A and one per source, filled by
+// An LDS stage holds R slots, each one [32][64] tile for A and one per source, filled by
 // LDS-DMA (global_load_lds_dwordx4: no staging registers, 1 KiB = 4 rows per
 // wave-instruction, per-lane gathered source address, lane-linear destination).
-// Two buffers: chunk k+1 streams in while chunk k feeds the MFMAs; one barrier
-// per chunk.  MFMA operands are k-major b32 reads of the row-major tiles
-// (consecutive lanes = consecutive columns: conflict-free, the two half-waves read
-// adjacent rows).
-template <int NBW, bool SILU>
+// Two stages: the next R chunks stream in while the current R feed the MFMAs; one barrier
+// (a full drain: vmcnt(0)) per R chunks, so R x (1 + sources) x 2 DMAs per wave are in
+// flight behind each drain instead of (1 + sources) x 2.  MFMA operands are k-major b32
+// reads of the row-major tiles (consecutive lanes = consecutive columns: conflict-free,
+// the two half-waves read adjacent rows).
+// A workgroup's chunk sequence is c0, c0 + g, c0 + 2 g, .. (g workgroups); interval t of the loop
+// carries chunks t R .. t R + R - 1 OF THAT SEQUENCE, multiplied chunk after chunk on the same
+// accumulators: the summation order does not depend on R, the partials are bit-identical for every R.
+// NS is the source count as a constant (descriptors, column offsets and validity then live in
+// registers, computed once); NS = 0 takes it from the argument (R = 1 only): every (NBW, NS) pair that
+// has no instantiation of its own.
+template <int NBW, bool SILU, int NS, int R>
 __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgrad_t p) {
+    static_assert(NS >= 0 && NS <= NLAM_MAX_SRC && R >= 1 && (NS > 0 || R == 1), "run-time source count: one chunk per interval");
+    constexpr int MS = NS > 0 ? NS : NLAM_MAX_SRC;   // sources the unrolled loops cover
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int ntile = 1 + p.nsrc;
+    const int nsrc = NS > 0 ? NS : p.nsrc;
+    const int ntile = 1 + nsrc;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, hi = lane >> 5;
@@ -2670,7 +2681,9 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgr
     int blk_mb[NBW], blk_tile[NBW], blk_nb[NBW], blk_col0[NBW], blk_w[NBW];
     {
         int nb_total = 0;
-        for (int s = 0; s < p.nsrc; ++s) nb_total += (p.src[s].width + 31) >> 5;
+#pragma unroll
+        for (int s = 0; s < MS; ++s)
+            if (s < nsrc) nb_total += (p.src[s].width + 31) >> 5;
 #pragma unroll
         for (int q = 0; q < NBW; ++q) {
             const int blk = wave + 4 * q;
@@ -2682,17 +2695,21 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgr
             if (blk < MB * nb_total) {
                 blk_mb[q] = blk / nb_total;
                 int nbg = blk % nb_total, off = 0;
-                for (int s = 0; s < p.nsrc; ++s) {
+                bool found = false;
+#pragma unroll
+                for (int s = 0; s < MS; ++s) {
+                    if (s >= nsrc || found) continue;
                     const int nbs = (p.src[s].width + 31) >> 5;
                     if (nbg < nbs) {
                         blk_tile[q] = 1 + s;
                         blk_nb[q] = nbg;
                         blk_col0[q] = off + nbg * 32;
                         blk_w[q] = off + p.src[s].width;
-                        break;
+                        found = true;
+                    } else {
+                        nbg -= nbs;
+                        off += p.src[s].width;
                     }
-                    nbg -= nbs;
-                    off += p.src[s].width;
                 }
             }
         }
@@ -2704,93 +2721,157 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgr
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 
-    const int chunks_per_batch = (p.rows + kWgradRows - 1) / kWgradRows;
-    const long total_chunks = (long)chunks_per_batch * p.batch;
+    const int cpb = (p.rows + kWgradRows - 1) / kWgradRows;   // chunks per batch item
+    const long total_chunks = (long)cpb * p.batch;
     const int lrow = lane >> 4, lcol = (lane & 15) << 2;  // lane -> (row within the 4-row group, first column)
 
-    // gather indices of a chunk (one per fetched row and source); loaded one chunk ahead of the DMA that uses
-    // them, so the index -> row dependent-load chain never sits in front of the MFMAs
-    auto load_idx = [&](long ch, int(&ix)[2][NLAM_MAX_SRC]) {
-        const int r0 = (int)(ch % chunks_per_batch) * kWgradRows;
-        const int nr = min(kWgradRows, p.rows - r0);
+    // everything of the argument the loop needs, once: per-source base pointer at this lane's columns, batch stride, width, index
+    // table, whether the lane's columns exist -- the loop then holds no load of the argument and no address arithmetic but
+    // index x width + base
+    // (byte addresses and 32-bit byte pitches: a row's address is ONE 32 x 32 -> 64-bit multiply-add on its non-negative index)
+    typedef unsigned long long u64;
+    const char* const abase = reinterpret_cast<const char*>(p.A + lcol);
+    const bool acol = lcol < p.m;
+    const int arows = p.rows;
+    const unsigned apitch = (unsigned)p.m * 4u;
+    const long abatch = (long)p.rows * p.m * 4;
+    const char* sbase[MS];
+    const int* sidx[MS];
+    long sbatch[MS];
+    unsigned spitch[MS];
+    bool scol[MS];
 #pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const int r = wave * 8 + g * 4 + lrow;
-            const int prow = r0 + (r < nr ? r : 0);
-#pragma unroll
-            for (int s = 0; s < NLAM_MAX_SRC; ++s) {
-                ix[g][s] = prow;
-                if (s < p.nsrc && r < nr && p.src[s].idx != nullptr) ix[g][s] = p.src[s].idx[prow];
-            }
+    for (int s = 0; s < MS; ++s) {
+        const bool on = s < nsrc;
+        sbase[s] = on ? reinterpret_cast<const char*>(p.src[s].ptr + lcol) : nullptr;
+        sidx[s] = on ? p.src[s].idx : nullptr;
+        sbatch[s] = on ? (long)p.src[s].bstride * 4 : 0;
+        spitch[s] = on ? (unsigned)p.src[s].width * 4u : 0u;
+        scol[s] = on && lcol < p.src[s].width;
+    }
+    const char* zero16 = reinterpret_cast<const char*>(g_zero16);   // the address comes from the GOT: fetched here, not per chunk
+    asm volatile("" : "+s"(zero16));
+    const int trow = wave * 8 + lrow;                         // tile row this lane fetches in group g: trow + 4 g
+    float* const lds_row = smem + (size_t)(wave * 8) * 64;   // this wave's eight rows of tile 0, slot 0, stage 0
+
+    // The sequence as (batch item, chunk inside it) cursors that advance by g chunks: no division in the loop.
+    const int g = (int)gridDim.x, c0 = xcd_slot((int)blockIdx.x, g);   // chunk c -> slot c % g: the rows an XCD gathers stay in an eighth of the tables
+    const int nseq = c0 < total_chunks ? (int)((total_chunks - c0 + g - 1) / g) : 0;   // chunks of this workgroup
+    const int gq = g / cpb, gr = g % cpb;
+    struct Cursor {
+        int b, c;
+    };
+    auto advance = [&](Cursor& k) {
+        k.b += gq;
+        k.c += gr;
+        if (k.c >= cpb) {
+            k.c -= cpb;
+            ++k.b;
         }
     };
-    auto issue = [&](long ch, int buf, const int(&ix)[2][NLAM_MAX_SRC]) {
-        const int b = (int)(ch / chunks_per_batch);
-        const int r0 = (int)(ch % chunks_per_batch) * kWgradRows;
-        const int nr = min(kWgradRows, p.rows - r0);
+    Cursor kl = {c0 / cpb, c0 % cpb};   // next chunk whose gather indices are loaded
+    Cursor ki = kl;                     // next chunk whose rows are requested
+
+    // Gather indices of a chunk (one per fetched row and source; -1 = the chunk has no such row), and the row itself for A.
+    // Loaded one interval ahead of the DMAs that use them, so the index -> row dependent-load chain never sits in front of the
+    // MFMAs.
+    auto load_idx = [&](int(&ix)[2][MS], int(&pr)[2]) {
+        const int r0 = kl.c * kWgradRows;
+        const int nr = min(kWgradRows, arows - r0);
 #pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const int r = wave * 8 + g * 4 + lrow;   // tile row this lane fetches
+        for (int gi = 0; gi < 2; ++gi) {
+            const int r = trow + 4 * gi;
             const bool rv = r < nr;
-            const long prow = r0 + (rv ? r : 0);
+            const int prow = r0 + (rv ? r : 0);
+            pr[gi] = rv ? prow : -1;
+#pragma unroll
+            for (int s = 0; s < MS; ++s) {
+                int v = prow;
+                if (rv && sidx[s] != nullptr) v = sidx[s][prow];
+                ix[gi][s] = rv ? v : -1;
+            }
+        }
+        advance(kl);
+    };
+    auto issue = [&](float* slot, const int(&ix)[2][MS], const int(&pr)[2]) {
+        const long aoff = ki.b * abatch;
+#pragma unroll
+        for (int gi = 0; gi < 2; ++gi) {
             // tile 0: A
             {
-                const float* src = (rv && lcol < p.m) ? p.A + ((size_t)b * p.rows + prow) * p.m + lcol : g_zero16;
-                float* dst = smem + ((size_t)(buf * ntile) * kWgTile) + (wave * 8 + g * 4) * 64;
+                const char* src = (acol && pr[gi] >= 0) ? abase + ((u64)(unsigned)pr[gi] * apitch + aoff) : zero16;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void*)(slot + gi * 4 * 64), 16, 0, 0);
             }
 #pragma unroll
-            for (int s = 0; s < NLAM_MAX_SRC; ++s) {
-                if (s >= p.nsrc) continue;
-                const nlam_src_t S = p.src[s];
-                const float* src = g_zero16;
-                if (rv && lcol < S.width) src = S.ptr + (long)b * S.bstride + (long)ix[g][s] * S.width + lcol;
-                float* dst = smem + ((size_t)(buf * ntile + 1 + s) * kWgTile) + (wave * 8 + g * 4) * 64;
+            for (int s = 0; s < MS; ++s) {
+                if (s >= nsrc) continue;
+                const char* src = (scol[s] && ix[gi][s] >= 0) ? sbase[s] + ((u64)(unsigned)ix[gi][s] * spitch[s] + ki.b * sbatch[s]) : zero16;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void*)(slot + (1 + s) * kWgTile + gi * 4 * 64), 16, 0, 0);
             }
         }
+        advance(ki);
     };
 
-    long ch = xcd_slot((int)blockIdx.x, (int)gridDim.x);   // chunk c -> slot c % g: the rows an XCD gathers stay in an eighth of the tables
+    const int stage_floats = R * ntile * kWgTile;
+    int ix[R][2][MS], pr[R][2];
+    // prologue: the first R chunks behind ONE wait for their gather indices, and the registers re-defined by the (empty) asm:
+    // with the index loads still pending in the compiler's books, every address computation in issue() got an s_waitcnt
+    // vmcnt(0) of its own -- behind an LDS-DMA it cannot count past, so each of the DMAs waited for the one before (seen in the
+    // ISA, round 6: eight dependent round trips at the head of a launch of ~14 chunks per workgroup).  The loop's chunks never
+    // had the problem.
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+        if (j < nseq) load_idx(ix[j], pr[j]);
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+#pragma unroll
+        for (int gi = 0; gi < 2; ++gi) {
+            asm volatile("" : "+v"(pr[j][gi]));
+#pragma unroll
+            for (int s = 0; s < MS; ++s) asm volatile("" : "+v"(ix[j][gi][s]));
+        }
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+        if (j < nseq) issue(lds_row + j * ntile * kWgTile, ix[j], pr[j]);
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+        if (R + j < nseq) load_idx(ix[j], pr[j]);
+
     int buf = 0;
-    int ix[2][NLAM_MAX_SRC];
-    if (ch < total_chunks) {
-        load_idx(ch, ix);
-        // ONE wait for the first chunk's gather indices, and the registers re-defined by the (empty) asm: with the index loads still
-        // pending in the compiler's books, every address computation in issue() got an s_waitcnt vmcnt(0) of its own -- behind an
-        // LDS-DMA it cannot count past, so each of the chunk's eight DMAs waited for the one before (seen in the ISA, round 6:
-        // eight dependent round trips at the head of a launch of ~14 chunks per workgroup).  The loop's chunks never had the problem.
-        static_assert(NLAM_MAX_SRC == 3, "the asm below lists ix[2][3]");
-        asm volatile("" : "+v"(ix[0][0]), "+v"(ix[0][1]), "+v"(ix[0][2]), "+v"(ix[1][0]), "+v"(ix[1][1]), "+v"(ix[1][2]));
-        issue(ch, 0, ix);
-    }
-    if (ch + gridDim.x < total_chunks) load_idx(ch + gridDim.x, ix);
-    for (; ch < total_chunks; ch += gridDim.x) {
-        __syncthreads();  // drains this wave's LDS-DMA (vmcnt(0)); everyone is done reading buf ^ 1
-        if (ch + gridDim.x < total_chunks) issue(ch + gridDim.x, buf ^ 1, ix);
-        if (ch + 2 * (long)gridDim.x < total_chunks) load_idx(ch + 2 * (long)gridDim.x, ix);
-        const float* At = smem + (size_t)(buf * ntile) * kWgTile;
+    for (int k0 = 0; k0 < nseq; k0 += R) {
+        __syncthreads();  // drains this wave's LDS-DMA (vmcnt(0)); everyone is done reading stage buf ^ 1
 #pragma unroll
-        for (int q = 0; q < NBW; ++q) {
-            if (blk_mb[q] >= 0) {
-                const float* Bt = smem + (size_t)(buf * ntile + blk_tile[q]) * kWgTile;
-                const int ac = blk_mb[q] * 32 + i, bc = blk_nb[q] * 32 + i;
-                // all operands of the chunk first (one lgkmcnt wait), then 16 back-to-back MFMAs;
-                // SiLU is a compile-time variant: as a run-time flag it was evaluated (and discarded) for every MFMA
-                float a[kWgradRows / 2], bv[kWgradRows / 2];
+        for (int j = 0; j < R; ++j)   // a sequence that is no multiple of R ends with a short interval: nothing requested ..
+            if (k0 + R + j < nseq) issue(lds_row + (buf ^ 1) * stage_floats + j * ntile * kWgTile, ix[j], pr[j]);
 #pragma unroll
-                for (int ks = 0; ks < kWgradRows / 2; ++ks) {
-                    a[ks] = At[(2 * ks + hi) * 64 + ac];
-                    bv[ks] = Bt[(2 * ks + hi) * 64 + bc];
+        for (int j = 0; j < R; ++j)
+            if (k0 + 2 * R + j < nseq) load_idx(ix[j], pr[j]);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            if (k0 + j >= nseq) continue;   // .. and nothing multiplied for the missing slots
+            const float* At = smem + (size_t)buf * stage_floats + (size_t)(j * ntile) * kWgTile;
+#pragma unroll
+            for (int q = 0; q < NBW; ++q) {
+                if (blk_mb[q] >= 0) {
+                    const float* Bt = At + (size_t)blk_tile[q] * kWgTile;
+                    const int ac = blk_mb[q] * 32 + i, bc = blk_nb[q] * 32 + i;
+                    // all operands of the chunk first (one lgkmcnt wait), then 16 back-to-back MFMAs;
+                    // SiLU is a compile-time variant: as a run-time flag it was evaluated (and discarded) for every MFMA
+                    float a[kWgradRows / 2], bv[kWgradRows / 2];
+#pragma unroll
+                    for (int ks = 0; ks < kWgradRows / 2; ++ks) {
+                        a[ks] = At[(2 * ks + hi) * 64 + ac];
+                        bv[ks] = Bt[(2 * ks + hi) * 64 + bc];
+                    }
+                    if constexpr (SILU) {
+#pragma unroll
+                        for (int ks = 0; ks < kWgradRows / 2; ++ks) bv[ks] = silu_f(bv[ks]);
+                    }
+#pragma unroll
+                    for (int ks = 0; ks < kWgradRows / 2; ++ks) acc[q] = MFMA32(a[ks], bv[ks], acc[q]);
                 }
-                if constexpr (SILU) {
-#pragma unroll
-                    for (int ks = 0; ks < kWgradRows / 2; ++ks) bv[ks] = silu_f(bv[ks]);
-                }
-#pragma unroll
-                for (int ks = 0; ks < kWgradRows / 2; ++ks) acc[q] = MFMA32(a[ks], bv[ks], acc[q]);
             }
         }
         buf ^= 1;
@@ -5485,6 +5566,7 @@ int nlam_detail::wbf_edge = 1;
 int nlam_detail::chain_cus = kNumCUs;
 int nlam_detail::wgrad_max_wgs = 128;   // round 6: 256 (one per CU) until then -- see nlam_wgrad_nparts
 int nlam_detail::wgrad_ldma_var = 0;
+int nlam_detail::wgrad_dma_r = 0;          // 0: the per-source-count default of wgrad_narrow; 1, 2, 4 for A/B runs (NLAM_TUNE_WGRAD_DMA_R)
 int nlam_detail::wgrad_ldma = 3;           // bit 0: bf16-operand launches, bit 1: fp32-operand one-term launches with 256 x 256 windows (NLAM_TUNE_WGRAD_LDMA)
 int nlam_detail::wgrad_chunks_per_wg = 8;   // A/B at cfg2 (tools/ab_bench.sh): 2.13 -> 2.06 ms per step against one chunk per workgroup
 #endif
@@ -5558,6 +5640,11 @@ int32_t nlam_set_tuning(int32_t key, int32_t value) {
     if (key == NLAM_TUNE_WGRAD_LDMA_VAR) {
         if (value < 0 || value > 3) return NLAM_EINVAL;
         nlam_detail::wgrad_ldma_var = value;
+        return 0;
+    }
+    if (key == NLAM_TUNE_WGRAD_DMA_R) {
+        if (value != 0 && value != 1 && value != 2 && value != 4) return NLAM_EINVAL;
+        nlam_detail::wgrad_dma_r = value;
         return 0;
     }
     if (key == NLAM_TUNE_WGRAD_LDMA) {
@@ -6486,6 +6573,18 @@ int32_t nlam_detail::wgrad_wide(const nlam_wgrad_t* p, hipStream_t stream) {
 #endif
 
 #if NLAM_IN_TU(2)
+namespace {
+// chunks per barrier interval of wgrad_dma_kernel by source count (1, 2, 3) when NLAM_TUNE_WGRAD_DMA_R is 0
+constexpr int kWgradDmaR[NLAM_MAX_SRC] = {1, 1, 1};
+
+template <int NBW, bool SILU, int NS, int R>
+int32_t launch_wgrad_dma(hipStream_t stream, const nlam_wgrad_t& p) {
+    constexpr size_t lds = (size_t)2 * R * (1 + NS) * kWgTile * sizeof(float);   // two stages of R slots of (1 + NS) tiles
+    static_assert(NS >= 1 && lds <= kMaxLds, "wgrad_dma_kernel: R chunks per interval do not fit the LDS with this many sources");
+    return launch<wgrad_dma_kernel<NBW, SILU, NS, R>>(dim3(p.nparts), dim3(kWgradThreads), lds, stream, p);
+}
+}  // namespace
+
 int32_t nlam_detail::wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t stream) {
     if (plan == NLAM_WGP_SMALLN) {
         hipLaunchKernelGGL(wgrad_smalln_kernel, dim3(p->nparts), dim3(256), 0, stream, *p);
@@ -6496,10 +6595,26 @@ int32_t nlam_detail::wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t s
     if (plan == NLAM_WGP_DMA) {
         const int nblocks = ((p->m + 31) / 32) * nb_total;
         const int nbw = (nblocks + 3) / 4;
+        const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
+        // the (blocks per wave, sources) pairs of the models -- one block per source and wave: dW2 (1, 1), the two- and
+        // three-source dW1 at full width (2, 2) / (3, 3) -- have the source count as a constant and R chunks per barrier
+        // interval (NLAM_TUNE_WGRAD_DMA_R, clamped to what the LDS holds); the SiLU occurs with one source only
+        if (nbw == p->nsrc && (!silu || p->nsrc == 1)) {
+            int r = nlam_detail::wgrad_dma_r > 0 ? nlam_detail::wgrad_dma_r : kWgradDmaR[p->nsrc - 1];
+            if (p->nsrc > 1 && r > 2) r = 2;
+            if (p->nsrc == 1)
+                return pick<1, 2, 4>(r, [&](auto rr) {
+                    return pick_bool(silu, [&](auto sl) { return launch_wgrad_dma<1, sl, 1, rr>(stream, *p); });
+                });
+            return pick<1, 2>(r, [&](auto rr) {
+                if (p->nsrc == 2) return launch_wgrad_dma<2, false, 2, rr>(stream, *p);
+                return launch_wgrad_dma<3, false, 3, rr>(stream, *p);
+            });
+        }
         const size_t lds = (size_t)2 * (1 + p->nsrc) * kWgTile * sizeof(float);
         return pick<1, 2, 3>(nbw < 1 ? 1 : nbw, [&](auto nb) {
-            return pick_bool((p->flags & NLAM_F_SILU_B) != 0, [&](auto silu) {
-                return launch<wgrad_dma_kernel<nb, silu>>(dim3(p->nparts), dim3(kWgradThreads), lds, stream, *p);
+            return pick_bool(silu, [&](auto sl) {
+                return launch<wgrad_dma_kernel<nb, sl, 0, 1>>(dim3(p->nparts), dim3(kWgradThreads), lds, stream, *p);
             });
         });
     }
