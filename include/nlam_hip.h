@@ -372,6 +372,42 @@ int32_t nlam_wgrad_nparts(const nlam_wgrad_t* p);
 #define NLAM_WGP_LDMA_3    11   /* wgrad_ldma_kernel, fp32 operands, three terms (bit 2)                           */
 int32_t nlam_wgrad_plan(const nlam_wgrad_t* p);
 
+/* Kernel instantiation nlam_mlp_fwd / nlam_mlp_bwd launch for a NARROW call (hid, dout and every source width <= 64:
+ * nlam_mlp_*_family == 0), host logic, no launch -- or the NLAM_EINVAL / NLAM_EUNSUP the launch would return.  The narrow
+ * launchers switch on this code, so the two cannot disagree.  A wide call gives NLAM_MLPP_NOT_NARROW (0), a call with
+ * rows == 0 (which launches nothing and returns 0) NLAM_MLPP_EMPTY.  Otherwise the code is a bit field:
+ *   NLAM_MLPP_KERNEL(c)  forward: NLAM_MLPP_FWD_GENERIC  mlp_fwd_kernel, fully generic shapes (fp32 MFMA)
+ *                                 NLAM_MLPP_FWD_FAST     mlp_fwd_kernel, FAST shapes (fp32 MFMA)
+ *                                 NLAM_MLPP_FWD_BF       mlp_fwd_bf_kernel (split-bf16)
+ *                        backward: NLAM_MLPP_BWD_GENERIC mlp_bwd_kernel (fp32 MFMA)
+ *                                  NLAM_MLPP_BWD_FAST    mlp_bwd_fast_kernel (fp32 MFMA or split-bf16)
+ *   NLAM_MLPP_HB(c), NLAM_MLPP_OB(c)   32-column blocks of the hidden / output width the kernel is instantiated for
+ *   NLAM_MLPP_NS(c)      bf16 terms per operand the kernel EXECUTES (0 = fp32 MFMA): a split-bf16 mode the flags ask for runs as
+ *                        0 on shapes the split kernels do not cover
+ *   NLAM_MLPP_RAG        forward: ragged-input instantiation (a single source of a width that is no multiple of 32, a ragged
+ *                        output width, or concatenated pieces); backward: the ragged-output instantiation (dz2 32-padded)
+ *   NLAM_MLPP_RES        forward: the residual instantiation (NLAM_F_ADD_SRC0 with `out`, or NLAM_F_ADD_SRC1)
+ *   NLAM_MLPP_PRE        forward: the factorised (NLAM_F_PRE_ADD) instantiation
+ *   NLAM_MLPP_CAT        forward: the concatenated-pieces (ncat > 0) instantiation */
+#define NLAM_MLPP_NOT_NARROW   0
+#define NLAM_MLPP_FWD_GENERIC  1
+#define NLAM_MLPP_FWD_FAST     2
+#define NLAM_MLPP_FWD_BF       3
+#define NLAM_MLPP_BWD_GENERIC  1
+#define NLAM_MLPP_BWD_FAST     2
+#define NLAM_MLPP_KERNEL(c)    ((c) & 3)
+#define NLAM_MLPP_HB(c)        (((c) >> 2) & 3)
+#define NLAM_MLPP_OB(c)        (((c) >> 4) & 3)
+#define NLAM_MLPP_NS(c)        (((c) >> 6) & 3)
+#define NLAM_MLPP_RAG          (1 << 8)
+#define NLAM_MLPP_RES          (1 << 9)
+#define NLAM_MLPP_PRE          (1 << 10)
+#define NLAM_MLPP_CAT          (1 << 11)
+#define NLAM_MLPP_EMPTY        (1 << 12)
+#define NLAM_MLPP_CODE(kernel, hb, ob, ns) ((kernel) | ((hb) << 2) | ((ob) << 4) | ((ns) << 6))
+int32_t nlam_mlp_fwd_plan(const nlam_mlp_fwd_t* p);
+int32_t nlam_mlp_bwd_plan(const nlam_mlp_bwd_t* p);
+
 int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream);
 int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream);
 

@@ -38,6 +38,23 @@ TUNE_CHAIN_CUS = 13
 TUNE_WGRAD_DMA_R = 14
 # nlam_wgrad_plan codes (include/nlam_hip.h): the kernel family nlam_wgrad launches
 WGP_SMALLN, WGP_DMA, WGP_NARROW, WGP_WIDE, WGP_WBF, WGP_WBF_BIG, WGP_WBF_B, WGP_WBF_B_BIG, WGP_LDMA_B, WGP_LDMA_1, WGP_LDMA_3 = range(1, 12)
+# nlam_mlp_fwd_plan / nlam_mlp_bwd_plan codes (include/nlam_hip.h, NLAM_MLPP_*): the instantiation a narrow launch runs
+MLPP_NOT_NARROW = 0
+MLPP_FWD_GENERIC, MLPP_FWD_FAST, MLPP_FWD_BF = 1, 2, 3
+MLPP_BWD_GENERIC, MLPP_BWD_FAST = 1, 2
+MLPP_RAG, MLPP_RES, MLPP_PRE, MLPP_CAT, MLPP_EMPTY = 1 << 8, 1 << 9, 1 << 10, 1 << 11, 1 << 12
+
+
+def mlpp_code(kernel, hb, ob, ns, bits=0):
+    """NLAM_MLPP_CODE: kernel | HB | OB | executed term count, plus NLAM_MLPP_RAG / RES / PRE / CAT bits."""
+    return kernel | (hb << 2) | (ob << 4) | (ns << 6) | bits
+
+
+def mlpp_fields(code):
+    """(kernel, HB, OB, NS, bits) of a plan code."""
+    return code & 3, (code >> 2) & 3, (code >> 4) & 3, (code >> 6) & 3, code & ~0xFF
+
+
 TILE_SPLIT = 1 << 30
 # training-loss kinds (NLAM_LOSS_*), keyed by the reference's metric names (metrics.DEFINED_METRICS)
 LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
@@ -70,6 +87,8 @@ EXPORTS = [
     "nlam_mlp_bwd_dz2_ld",
     "nlam_wgrad_nparts",
     "nlam_wgrad_plan",
+    "nlam_mlp_fwd_plan",
+    "nlam_mlp_bwd_plan",
     "nlam_mlp_fwd",
     "nlam_mlp_bwd",
     "nlam_mlp_fwd_gemm_workspace_floats",
@@ -579,6 +598,10 @@ def load():
     lib.nlam_wgrad_nparts.restype = i32
     lib.nlam_wgrad_plan.argtypes = [C.POINTER(Wgrad)]
     lib.nlam_wgrad_plan.restype = i32
+    lib.nlam_mlp_fwd_plan.argtypes = [C.POINTER(MlpFwd)]
+    lib.nlam_mlp_fwd_plan.restype = i32
+    lib.nlam_mlp_bwd_plan.argtypes = [C.POINTER(MlpBwd)]
+    lib.nlam_mlp_bwd_plan.restype = i32
     lib.nlam_mlp_pack_floats.argtypes = [C.POINTER(PackJob), i32]
     lib.nlam_mlp_pack_floats.restype = i64
     lib.nlam_mlp_pack.argtypes = [vp, i32, vp]

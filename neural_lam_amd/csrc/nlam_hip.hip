@@ -5198,6 +5198,71 @@ bool bwd_ragged_out(const nlam_mlp_bwd_t* p) {
     return true;
 }
 
+// nlam_mlp_fwd_plan for a checked narrow call: every eligibility test of fwd_narrow lives here, the launcher switches on the code
+int fwd_narrow_plan(const nlam_mlp_fwd_t* p) {
+    const int HB = (p->hid + 31) / 32, OB = (p->dout + 31) / 32;
+    // an output width that is not a whole 32-column block runs on the split-bf16 kernels when nothing downstream of GEMM2
+    // needs whole blocks: no LayerNorm, no aggregation, no residual (output_map, graph/base.py:322); W2 / b2 are zero-padded
+    // when staged and the ragged-input instantiation stores the block as dwords
+    const bool ragged_out = (p->dout % 32 != 0) && p->ln_w == nullptr && p->aggr == nullptr && p->nsrc == 1 && p->out != nullptr &&
+                            (p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1 | NLAM_F_PRE_ADD)) == 0 && p->xhat == nullptr;
+    const bool fast_out = (p->hid % 32 == 0) && (p->dout % 32 == 0 || ragged_out);
+    bool fast = fast_out && !ragged_out, w64 = true, ragged = ragged_out;
+    for (int s = 0; s < p->nsrc; ++s) {
+        fast = fast && (p->src[s].width % 8 == 0);
+        w64 = w64 && p->src[s].width <= 64;
+        ragged = ragged || (p->src[s].width % 32 != 0);
+    }
+    if (ragged && p->nsrc != 1) w64 = false;   // ragged inputs are covered for single-source MLPs (embedders, grid MLPs)
+    if (p->ncat > 0) ragged = true;            // concatenated pieces are read by the ragged-input instantiation
+    const bool resid = ((p->flags & NLAM_F_ADD_SRC0) != 0 && p->out != nullptr) || (p->flags & NLAM_F_ADD_SRC1) != 0;
+    if (ragged && resid) w64 = false;
+    if ((p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1)) != 0) {   // residual rows are read as whole 16-B chunks
+        const int rs = (p->flags & NLAM_F_ADD_SRC1) ? 1 : 0;
+        w64 = w64 && (p->src[rs].width % 32 == 0) && ((p->flags & NLAM_F_ADD_SRC0) == 0 || p->src[0].width % 32 == 0);
+    }
+    // matrix path: NLAM_F_MM_* asks for the split-bf16 cores; shapes they do not cover run the fp32 MFMA
+    int ns = 0;
+    if (fast_out && w64) ns = (int)((p->flags & NLAM_F_MM_MASK) >> NLAM_F_MM_SHIFT);
+    if (ns > 3) return NLAM_EINVAL;
+    if (p->ncat > 0) {   // concatenated pieces: the CAT instantiation of the ragged-input split-bf16 kernel, square MLPs
+        if (ns == 0 || HB != OB || HB > 2) return NLAM_EUNSUP;
+        return NLAM_MLPP_CODE(NLAM_MLPP_FWD_BF, HB, HB, ns) | NLAM_MLPP_RAG | NLAM_MLPP_CAT;
+    }
+    if (p->flags & NLAM_F_PRE_ADD) {   // factorised edge MLP: split-bf16 modes, whole 32-column units, addends of width hid
+        bool ok = ns > 0 && !ragged && p->nsrc >= 2 && (p->flags & NLAM_F_ADD_SRC1) == 0 && HB == OB;
+        for (int s = 1; s < p->nsrc; ++s) ok = ok && p->src[s].width == p->hid;
+        if (!ok || HB > 2) return NLAM_EUNSUP;
+        return NLAM_MLPP_CODE(NLAM_MLPP_FWD_BF, HB, HB, ns) | NLAM_MLPP_PRE | (resid ? NLAM_MLPP_RES : 0);
+    }
+    if (HB > 2 || OB > 2) return NLAM_EUNSUP;
+    if (ns == 0) return NLAM_MLPP_CODE(fast ? NLAM_MLPP_FWD_FAST : NLAM_MLPP_FWD_GENERIC, HB, OB, 0);   // fp32 MFMA
+    return NLAM_MLPP_CODE(NLAM_MLPP_FWD_BF, HB, OB, ns) | (ragged ? NLAM_MLPP_RAG : (resid ? NLAM_MLPP_RES : 0));
+}
+
+// nlam_mlp_bwd_plan for a checked narrow call: every eligibility test of bwd_narrow lives here, the launcher switches on the code
+int bwd_narrow_plan(const nlam_mlp_bwd_t* p) {
+    const int HB = (p->hid + 31) / 32, OB = (p->dout + 31) / 32;
+    const bool ro = bwd_ragged_out(p);   // output_map: dout not a whole block, no LayerNorm -> split-bf16 fast kernel, dz2 padded to OB * 32 columns
+    if ((ro ? OB * 32 : 0) != p->dz2_ld) return NLAM_EINVAL;   // the caller sized dz2 with nlam_mlp_bwd_dz2_ld
+    bool fast = (p->hid % 32 == 0) && (p->dout % 32 == 0 || ro);
+    for (int s = 0; s < p->nsrc; ++s)
+        if (p->dmode[s] != 0) fast = fast && (p->src[s].width == 32 || p->src[s].width == 64);
+    if ((p->flags & NLAM_F_ADD_SRC0) && p->dmode[0] != 0 && p->src[0].width != p->dout) fast = false;
+    if (p->flags & NLAM_F_NO_ACT) fast = false;   // the generic kernel carries the activation switch
+    if (p->flags & NLAM_F_PRE_ADD) {   // factorised edge MLP: FAST shapes and split-bf16 modes only
+        bool ok = fast && ((p->flags & NLAM_F_MM_MASK) != 0) && (p->flags & NLAM_F_ADD_SRC1) == 0 && p->nsrc >= 2;
+        ok = ok && (p->src[0].width == 32 || p->src[0].width == 64);
+        for (int s = 1; s < p->nsrc; ++s) ok = ok && p->src[s].width == p->hid && (p->dmode[s] == 0 || p->dmode[s] == 2 || p->dmode[s] == 3);
+        if (!ok) return NLAM_EUNSUP;
+    }
+    if (HB > 2 || OB > 2) return NLAM_EUNSUP;
+    if (!fast) return NLAM_MLPP_CODE(NLAM_MLPP_BWD_GENERIC, HB, OB, 0);
+    const int ns = (int)((p->flags & NLAM_F_MM_MASK) >> NLAM_F_MM_SHIFT);
+    // ragged output: OB == 1 by construction (dout < 32 ... the only shape the reference has: output_map)
+    return NLAM_MLPP_CODE(NLAM_MLPP_BWD_FAST, HB, OB, ns) | (ro ? NLAM_MLPP_RAG : 0);
+}
+
 int bwd_wide_maxw(const nlam_mlp_bwd_t* p) {
     int w = p->hid > p->dout ? p->hid : p->dout;
     for (int s = 0; s < p->nsrc; ++s)
@@ -5819,6 +5884,24 @@ int32_t nlam_mlp_bwd_family(const nlam_mlp_bwd_t* p) {
     return bwd_wbf_ns(p) > 0 ? 2 : 1;
 }
 
+// the instantiation a narrow launch runs: the checks of nlam_mlp_fwd / nlam_mlp_bwd in their order, then the launcher's own code
+int32_t nlam_mlp_fwd_plan(const nlam_mlp_fwd_t* p) {
+    const int32_t bad = nlam_detail::fwd_check(p);
+    if (bad != 0) return bad;
+    if (p->rows == 0) return NLAM_MLPP_EMPTY;
+    if (mlp_is_wide(p)) return NLAM_MLPP_NOT_NARROW;
+    return fwd_narrow_plan(p);
+}
+
+int32_t nlam_mlp_bwd_plan(const nlam_mlp_bwd_t* p) {
+    const int32_t bad = nlam_detail::bwd_check(p);
+    if (bad != 0) return bad;
+    if (p->rows == 0) return NLAM_MLPP_EMPTY;
+    if (mlp_is_wide(p)) return NLAM_MLPP_NOT_NARROW;
+    if (p->flags & NLAM_F_ACC_DSRC0) return NLAM_EUNSUP;
+    return bwd_narrow_plan(p);
+}
+
 // workgroups (= rows of `vec_partials` written) per member of a grouped backward launch
 int32_t nlam_mlp_bwd_group_blocks(const nlam_mlp_bwd_t* ps, int32_t n, int32_t* blocks) {
     if (ps == nullptr || blocks == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
@@ -6003,33 +6086,12 @@ int32_t nlam_detail::fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream) {
     // are fewer tiles than CUs); tiles are dealt to workgroups first, then to waves
     const long ttiles = (long)p->ntiles * p->batch;
     const dim3 grid((int)(ttiles < 1 ? 1 : (ttiles < kMaxGridBlocks ? ttiles : kMaxGridBlocks))), block(kFwdWaves * 64);
-    const int HB = (p->hid + 31) / 32, OB = (p->dout + 31) / 32;
-    // an output width that is not a whole 32-column block runs on the split-bf16 kernels when nothing downstream of GEMM2
-    // needs whole blocks: no LayerNorm, no aggregation, no residual (output_map, graph/base.py:322); W2 / b2 are zero-padded
-    // when staged and the ragged-input instantiation stores the block as dwords
-    const bool ragged_out = (p->dout % 32 != 0) && p->ln_w == nullptr && p->aggr == nullptr && p->nsrc == 1 && p->out != nullptr &&
-                            (p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1 | NLAM_F_PRE_ADD)) == 0 && p->xhat == nullptr;
-    const bool fast_out = (p->hid % 32 == 0) && (p->dout % 32 == 0 || ragged_out);
-    bool fast = fast_out && !ragged_out, w64 = true, ragged = ragged_out;
-    for (int s = 0; s < p->nsrc; ++s) {
-        fast = fast && (p->src[s].width % 8 == 0);
-        w64 = w64 && p->src[s].width <= 64;
-        ragged = ragged || (p->src[s].width % 32 != 0);
-    }
-    if (ragged && p->nsrc != 1) w64 = false;   // ragged inputs are covered for single-source MLPs (embedders, grid MLPs)
-    if (p->ncat > 0) ragged = true;            // concatenated pieces are read by the ragged-input instantiation
-    const bool resid = ((p->flags & NLAM_F_ADD_SRC0) != 0 && p->out != nullptr) || (p->flags & NLAM_F_ADD_SRC1) != 0;
-    if (ragged && resid) w64 = false;
-    if ((p->flags & (NLAM_F_ADD_SRC0 | NLAM_F_ADD_SRC1)) != 0) {   // residual rows are read as whole 16-B chunks
-        const int rs = (p->flags & NLAM_F_ADD_SRC1) ? 1 : 0;
-        w64 = w64 && (p->src[rs].width % 32 == 0) && ((p->flags & NLAM_F_ADD_SRC0) == 0 || p->src[0].width % 32 == 0);
-    }
-    // matrix path: NLAM_F_MM_* asks for the split-bf16 cores; shapes they do not cover run the fp32 MFMA
-    int ns = 0;
-    if (fast_out && w64) ns = (int)((p->flags & NLAM_F_MM_MASK) >> NLAM_F_MM_SHIFT);
-    if (ns > 3) return NLAM_EINVAL;
-    if (p->ncat > 0) {   // concatenated pieces: the CAT instantiation of the ragged-input split-bf16 kernel, square MLPs
-        if (ns == 0 || HB != OB || HB > 2) return NLAM_EUNSUP;
+    // which instantiation: fwd_narrow_plan (the code nlam_mlp_fwd_plan answers with); only the launch shapes are decided here
+    const int plan = fwd_narrow_plan(p);
+    if (plan < 0) return plan;
+    const int HB = NLAM_MLPP_HB(plan), OB = NLAM_MLPP_OB(plan), ns = NLAM_MLPP_NS(plan);
+    const bool fast = NLAM_MLPP_KERNEL(plan) == NLAM_MLPP_FWD_FAST, ragged = (plan & NLAM_MLPP_RAG) != 0, resid = (plan & NLAM_MLPP_RES) != 0;
+    if (plan & NLAM_MLPP_CAT) {   // concatenated pieces: the CAT instantiation of the ragged-input split-bf16 kernel, square MLPs
         nlam_mlp_fwd_t pc = *p;   // unused piece slots: width 0 (they start at the total width and are never selected)
         for (int k = p->ncat; k < NLAM_MAX_CAT; ++k) {
             pc.cat_ptr[k] = p->cat_ptr[0];
@@ -6042,10 +6104,7 @@ int32_t nlam_detail::fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream) {
             });
         });
     }
-    if (p->flags & NLAM_F_PRE_ADD) {   // factorised edge MLP: split-bf16 modes, whole 32-column units, addends of width hid
-        bool ok = ns > 0 && !ragged && p->nsrc >= 2 && (p->flags & NLAM_F_ADD_SRC1) == 0 && HB == OB;
-        for (int s = 1; s < p->nsrc; ++s) ok = ok && p->src[s].width == p->hid;
-        if (!ok) return NLAM_EUNSUP;
+    if (plan & NLAM_MLPP_PRE) {   // factorised edge MLP: split-bf16 modes, whole 32-column units, addends of width hid
         return pick<1, 2>(HB, [&](auto hb) {
             return pick_else<1, 3, 2>(ns, [&](auto nsc) {
                 return pick_bool(resid, [&](auto res) {
@@ -6390,31 +6449,20 @@ extern "C" int32_t nlam_mlp_bwd_group(const nlam_mlp_bwd_t* ps, int32_t n, void*
 #if NLAM_IN_TU(2)
 int32_t nlam_detail::bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream) {
     const dim3 grid(grid_blocks((long)p->ntiles * p->batch)), block(kBlockThreads);
-    const int HB = (p->hid + 31) / 32, OB = (p->dout + 31) / 32;
-    const bool ro = bwd_ragged_out(p);   // output_map: dout not a whole block, no LayerNorm -> split-bf16 fast kernel, dz2 padded to OB * 32 columns
-    if ((ro ? OB * 32 : 0) != p->dz2_ld) return NLAM_EINVAL;   // the caller sized dz2 with nlam_mlp_bwd_dz2_ld
-    bool fast = (p->hid % 32 == 0) && (p->dout % 32 == 0 || ro);
-    for (int s = 0; s < p->nsrc; ++s)
-        if (p->dmode[s] != 0) fast = fast && (p->src[s].width == 32 || p->src[s].width == 64);
-    if ((p->flags & NLAM_F_ADD_SRC0) && p->dmode[0] != 0 && p->src[0].width != p->dout) fast = false;
-    if (p->flags & NLAM_F_NO_ACT) fast = false;   // the generic kernel carries the activation switch
-    if (p->flags & NLAM_F_PRE_ADD) {   // factorised edge MLP: FAST shapes and split-bf16 modes only
-        bool ok = fast && ((p->flags & NLAM_F_MM_MASK) != 0) && (p->flags & NLAM_F_ADD_SRC1) == 0 && p->nsrc >= 2;
-        ok = ok && (p->src[0].width == 32 || p->src[0].width == 64);
-        for (int s = 1; s < p->nsrc; ++s) ok = ok && p->src[s].width == p->hid && (p->dmode[s] == 0 || p->dmode[s] == 2 || p->dmode[s] == 3);
-        if (!ok) return NLAM_EUNSUP;
-    }
+    // which instantiation: bwd_narrow_plan (the code nlam_mlp_bwd_plan answers with)
+    const int plan = bwd_narrow_plan(p);
+    if (plan < 0) return plan;
+    const int HB = NLAM_MLPP_HB(plan), OB = NLAM_MLPP_OB(plan), ns = NLAM_MLPP_NS(plan);
+    const bool fast = NLAM_MLPP_KERNEL(plan) == NLAM_MLPP_BWD_FAST, ro = (plan & NLAM_MLPP_RAG) != 0;
     if (fast) {
-        const int ns = (int)((p->flags & NLAM_F_MM_MASK) >> NLAM_F_MM_SHIFT);
         if (ro)   // OB == 1 by construction (dout < 32 ... the only shape the reference has: output_map)
             return pick_else<2, 1>(HB, [&](auto hb) {
                 return pick_else<1, 3, 2>(ns, [&](auto nsc) {
                     return launch<mlp_bwd_fast_kernel<hb, 1, nsc, true>>(grid, block, bwd_fast_lds_bytes(p, hb, 1, nsc), stream, *p);
                 });
             });
-        const bool listed = (HB == 1 || HB == 2) && (OB == 1 || OB == 2);   // every other pair runs as (2, 2)
-        return pick<1, 2>(listed ? HB : 2, [&](auto hb) {
-            return pick<1, 2>(listed ? OB : 2, [&](auto ob) {
+        return pick<1, 2>(HB, [&](auto hb) {
+            return pick<1, 2>(OB, [&](auto ob) {
                 return pick_else<0, 3, 2, 1>(ns, [&](auto nsc) {
                     return launch<mlp_bwd_fast_kernel<hb, ob, nsc>>(grid, block, bwd_fast_lds_bytes(p, hb, ob, nsc), stream, *p);
                 });
