@@ -138,7 +138,10 @@ extern "C" {
 /* matrix path of the GEMMs (bits 8-9): 0 = v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chains);
  * n = 1..3: operands split into n bf16 terms on the bf16 matrix cores, fp32 accumulate
  * (1 = plain bf16 operands, 2 = ~2^-16 product error, 3 = fp32-class ~2^-24).  Shapes the
- * split kernels do not cover (widths not multiples of 32) run the fp32 path. */
+ * split kernels do not cover (widths not multiples of 32) run the fp32 path.  Wide launches (a width above 64): hid and the
+ * source widths must be multiples of 4 and the launch at or above the super-tile threshold; a forward that aggregates
+ * (aggr != NULL) with a dout that is no multiple of 4 runs the fp32 path too -- the super-tile aggregation writes whole float4s
+ * of a receiver's row -- and is NLAM_EUNSUP together with NLAM_F_PRE_ADD.  nlam_mlp_*_wide_plan says what a launch runs. */
 #define NLAM_F_MM_SHIFT   8
 #define NLAM_F_MM_MASK    (3u << NLAM_F_MM_SHIFT)
 #define NLAM_F_MM_BF16X1  (1u << NLAM_F_MM_SHIFT)
@@ -251,8 +254,10 @@ typedef struct {
     const float* b1;       /* NLAM_F_LEAF_WGRAD only (required there): first-layer bias; that kernel recomputes the pre-activation
                               z1 = W1 x + b1 from the (<= 4-column) input row and never reads `z1` (which may be NULL) */
     int32_t dz2_ld;        /* floats between rows of dz2: MUST equal nlam_mlp_bwd_dz2_ld(p) -- 0 = dout, except for an output width
-                              that is not a multiple of 32 on the split-bf16 kernel (output_map, dout = 17): then 32-padded, the
-                              columns past dout are written as zeros, and nlam_wgrad takes dz2 with m = that stride */
+                              that is not a multiple of 32 on the split-bf16 kernel (output_map, dout = 17): then 32-padded, and
+                              nlam_wgrad takes dz2 with m = that stride.  The narrow kernel writes the columns past dout as zeros;
+                              the wide kernels (a width above 64, dout no multiple of 4) write the dout real columns only and
+                              leave the padding as it is: the caller zero-fills it once (it must read as zeros in nlam_wgrad) */
     int32_t _pad2;
 } nlam_mlp_bwd_t;
 
@@ -407,6 +412,43 @@ int32_t nlam_wgrad_plan(const nlam_wgrad_t* p);
 #define NLAM_MLPP_CODE(kernel, hb, ob, ns) ((kernel) | ((hb) << 2) | ((ob) << 4) | ((ns) << 6))
 int32_t nlam_mlp_fwd_plan(const nlam_mlp_fwd_t* p);
 int32_t nlam_mlp_bwd_plan(const nlam_mlp_bwd_t* p);
+
+/* The same for a WIDE call (hid, dout or a source width above 64: nlam_mlp_*_family != 0): the instantiation nlam_mlp_fwd /
+ * nlam_mlp_bwd launch under the current tuning (nlam_set_tuning), host logic, no launch -- or the NLAM_EINVAL / NLAM_EUNSUP the
+ * launch would return.  The wide launchers switch on this code, so the two cannot disagree.  A narrow call gives
+ * NLAM_MLPW_NOT_WIDE (0), a call with rows == 0 NLAM_MLPW_EMPTY.  Otherwise the code is a bit field:
+ *   NLAM_MLPW_KERNEL(c)  NLAM_MLPW_WIDE  mlp_fwd_wide_kernel / mlp_bwd_wide_kernel<NWV, FB> (fp32 MFMA, one tile per workgroup)
+ *                        NLAM_MLPW_WBF   mlp_fwd_wbf_kernel / mlp_bwd_wbf_kernel (split-bf16 super-tile template)
+ *                        NLAM_MLPW_EDGE  mlp_fwd_edge_kernel / mlp_bwd_edge_kernel<NS, D, SBF> (D = 512 with one term, 256 with three)
+ *   NLAM_MLPW_NS(c)      bf16 terms per operand the kernel EXECUTES: 0 (fp32 MFMA), 1 or 3.  Two requested terms run as three; in
+ *                        the forward one requested term runs as three when the hidden width has an odd number of 32-column blocks;
+ *                        launches below the super-tile threshold (NLAM_TUNE_WBF_MIN_SUPERTILES), widths that are no multiples
+ *                        of 4 and, in the forward, an aggregating launch (aggr != NULL) whose dout is no multiple of 4 run as 0
+ *                        (with NLAM_F_PRE_ADD, which the fp32 kernels do not have, such a launch is NLAM_EUNSUP)
+ *   NLAM_MLPW_PLAN(c)    NLAM_MLPW_WBF only: the launch geometry.  Forward (WbfPlan) 1: d <= 128, 2: d <= 256, 3: d <= 512 on 8-wave
+ *                        workgroups; 4: d <= 256 on 64-row super tiles (mid-size launches); 5, 6, 7: the 4-wave half plans
+ *                        (NLAM_TUNE_WBF_HALF bits 0 and 2).  Backward (WbfBwdPlan) 1, 2, 3 as in the forward; 5: the 4-wave plan of
+ *                        128 < d <= 256 (NLAM_TUNE_WBF_HALF bit 1)
+ *   NLAM_MLPW_NWV(c), NLAM_MLPW_FB(c)   NLAM_MLPW_WIDE only: waves per workgroup and 32-feature blocks per wave, <4, 1>, <8, 1> or <8, 2>
+ *   NLAM_MLPW_V4         NLAM_MLPW_WBF only: the instantiation with branch-free 16-byte chunk accesses (every width a multiple of 4,
+ *                        backward: no padded dz2 either; NLAM_TUNE_WBF_V4)
+ *   NLAM_MLPW_SBF        the bf16-storage instantiation (NLAM_F_STORE_BF16).  Stored values are rounded to nearest, ties to even
+ *                        (v_cvt_pk_bf16_f32). */
+#define NLAM_MLPW_NOT_WIDE     0
+#define NLAM_MLPW_WIDE         1
+#define NLAM_MLPW_WBF          2
+#define NLAM_MLPW_EDGE         3
+#define NLAM_MLPW_KERNEL(c)    ((c) & 3)
+#define NLAM_MLPW_NS(c)        (((c) >> 2) & 3)
+#define NLAM_MLPW_PLAN(c)      (((c) >> 4) & 7)
+#define NLAM_MLPW_NWV(c)       (((c) >> 7) & 15)
+#define NLAM_MLPW_FB(c)        (((c) >> 11) & 3)
+#define NLAM_MLPW_V4           (1 << 13)
+#define NLAM_MLPW_SBF          (1 << 14)
+#define NLAM_MLPW_EMPTY        (1 << 15)
+#define NLAM_MLPW_CODE(kernel, ns, plan, nwv, fb) ((kernel) | ((ns) << 2) | ((plan) << 4) | ((nwv) << 7) | ((fb) << 11))
+int32_t nlam_mlp_fwd_wide_plan(const nlam_mlp_fwd_t* p);
+int32_t nlam_mlp_bwd_wide_plan(const nlam_mlp_bwd_t* p);
 
 int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream);
 int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream);

@@ -55,6 +55,22 @@ def mlpp_fields(code):
     return code & 3, (code >> 2) & 3, (code >> 4) & 3, (code >> 6) & 3, code & ~0xFF
 
 
+# nlam_mlp_fwd_wide_plan / nlam_mlp_bwd_wide_plan codes (include/nlam_hip.h, NLAM_MLPW_*): the instantiation a wide launch runs
+MLPW_NOT_WIDE = 0
+MLPW_WIDE, MLPW_WBF, MLPW_EDGE = 1, 2, 3
+MLPW_V4, MLPW_SBF, MLPW_EMPTY = 1 << 13, 1 << 14, 1 << 15
+
+
+def mlpw_code(kernel, ns=0, plan=0, nwv=0, fb=0, bits=0):
+    """NLAM_MLPW_CODE: kernel | executed term count | plan | <NWV, FB>, plus the NLAM_MLPW_V4 / NLAM_MLPW_SBF bits."""
+    return kernel | (ns << 2) | (plan << 4) | (nwv << 7) | (fb << 11) | bits
+
+
+def mlpw_fields(code):
+    """(kernel, NS, plan, NWV, FB, bits) of a wide plan code."""
+    return code & 3, (code >> 2) & 3, (code >> 4) & 7, (code >> 7) & 15, (code >> 11) & 3, code & (MLPW_V4 | MLPW_SBF | MLPW_EMPTY)
+
+
 TILE_SPLIT = 1 << 30
 # training-loss kinds (NLAM_LOSS_*), keyed by the reference's metric names (metrics.DEFINED_METRICS)
 LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
@@ -89,6 +105,8 @@ EXPORTS = [
     "nlam_wgrad_plan",
     "nlam_mlp_fwd_plan",
     "nlam_mlp_bwd_plan",
+    "nlam_mlp_fwd_wide_plan",
+    "nlam_mlp_bwd_wide_plan",
     "nlam_mlp_fwd",
     "nlam_mlp_bwd",
     "nlam_mlp_fwd_gemm_workspace_floats",
@@ -602,6 +620,10 @@ def load():
     lib.nlam_mlp_fwd_plan.restype = i32
     lib.nlam_mlp_bwd_plan.argtypes = [C.POINTER(MlpBwd)]
     lib.nlam_mlp_bwd_plan.restype = i32
+    lib.nlam_mlp_fwd_wide_plan.argtypes = [C.POINTER(MlpFwd)]
+    lib.nlam_mlp_fwd_wide_plan.restype = i32
+    lib.nlam_mlp_bwd_wide_plan.argtypes = [C.POINTER(MlpBwd)]
+    lib.nlam_mlp_bwd_wide_plan.restype = i32
     lib.nlam_mlp_pack_floats.argtypes = [C.POINTER(PackJob), i32]
     lib.nlam_mlp_pack_floats.restype = i64
     lib.nlam_mlp_pack.argtypes = [vp, i32, vp]

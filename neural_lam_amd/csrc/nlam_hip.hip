@@ -90,15 +90,15 @@ namespace nlam_detail {   // launchers: external linkage, each defined in exactl
 int32_t fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream);   // slice 1
 int32_t bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream);   // slice 2
 int32_t wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t stream);   // slice 2 (plan: nlam_wgrad_plan's code)
-int32_t fwd_wide(const nlam_mlp_fwd_t* p, hipStream_t stream);     // slice 3
-int32_t bwd_wide(const nlam_mlp_bwd_t* p, hipStream_t stream);     // slice 3
+int32_t fwd_wide(const nlam_mlp_fwd_t* p, int plan, hipStream_t stream);     // slice 3 (plan: nlam_mlp_fwd_wide_plan's code)
+int32_t bwd_wide(const nlam_mlp_bwd_t* p, int plan, hipStream_t stream);     // slice 3 (plan: nlam_mlp_bwd_wide_plan's code)
 int32_t fwd_wide_group(const nlam_mlp_fwd_t* ps, int n, hipStream_t stream);   // slice 3
 int32_t bwd_wide_group(const nlam_mlp_bwd_t* ps, int n, hipStream_t stream);   // slice 3
 int32_t fwd_check(const nlam_mlp_fwd_t* p);                        // argument checks of nlam_mlp_fwd (slice 1)
 int32_t bwd_check(const nlam_mlp_bwd_t* p);                        // argument checks of nlam_mlp_bwd (slice 1)
 int32_t wgrad_wide(const nlam_wgrad_t* p, hipStream_t stream);     // slice 3
-int32_t fwd_wbf(const nlam_mlp_fwd_t* p, hipStream_t stream);      // slice 4
-int32_t bwd_wbf(const nlam_mlp_bwd_t* p, hipStream_t stream);      // slice 4
+int32_t fwd_wbf(const nlam_mlp_fwd_t* p, int plan, hipStream_t stream);      // slice 4 (plan: nlam_mlp_fwd_wide_plan's code)
+int32_t bwd_wbf(const nlam_mlp_bwd_t* p, int plan, hipStream_t stream);      // slice 4 (plan: nlam_mlp_bwd_wide_plan's code)
 int32_t wgrad_wbf(const nlam_wgrad_t* p, int plan, hipStream_t stream);      // slice 4 (plan: nlam_wgrad_plan's code)
 int32_t wgrad_wbf_group(const nlam_wgrad_t* ps, int n, hipStream_t stream);   // slice 4
 extern int wbf_min_supertiles;                                     // nlam_set_tuning (defined in slice 1)
@@ -5612,6 +5612,59 @@ bool bwd_edge_ok(const nlam_mlp_bwd_t* p) {
     return (long)p->ntiles * p->batch >= 2 * 64;
 }
 
+// mlp_fwd_edge_kernel takes the launch: the factorised InteractionNet edge layer of one width -- d = 512 in the one-term mode
+// (cfg5), d = 256 in the fp32-class mode (cfg3): its own software-pipelined kernel (round 6)
+// (d = 256 in the one-term mode -- cfg3 under autocast, not a BASELINE configuration -- measured no faster than the
+// template's 4-wave shape, 103.3 vs 102.5 us on the m2m edges: not instantiated)
+bool fwd_edge_ok(const nlam_mlp_fwd_t* p, int wns, bool v4) {
+    return nlam_detail::wbf_edge != 0 && v4 && (p->flags & NLAM_F_PRE_ADD) && !(p->flags & (NLAM_F_ADD_SRC1 | NLAM_F_NO_ACT)) &&
+           p->nsrc == NLAM_MAX_SRC && p->hid == p->dout && ((wns == 1 && p->hid == 512) || (wns == 3 && p->hid == 256 && !(p->flags & NLAM_F_STORE_BF16))) &&
+           p->src[0].width == p->hid && p->src[1].width == p->hid && p->src[2].width == p->hid && p->ln_w != nullptr && p->ln_b != nullptr &&
+           p->b1 != nullptr && p->b2 != nullptr && p->aggr != nullptr && p->rowptr != nullptr && p->ncat == 0 &&
+           (long)p->ntiles * p->batch >= 2 * 64;
+}
+
+// nlam_mlp_fwd_wide_plan for a checked wide call with rows > 0: every decision of fwd_wide and fwd_wbf lives here (fwd_wbf_ns,
+// fwd_wbf_choose, wide_cfg, the V4 predicate, the edge-kernel condition, the bf16-storage table); the launchers switch on the code
+int fwd_wide_plan(const nlam_mlp_fwd_t* p) {
+    const int wns = fwd_wbf_ns(p);
+    if (wns == 0) {   // fp32 MFMA kernels of nlam_wide.inc
+        if (p->flags & NLAM_F_PRE_ADD) return NLAM_EUNSUP;   // no factorised variant
+        const WideCfg cfg = wide_cfg(p->hid > p->dout ? p->hid : p->dout);
+        if (cfg.nwv == 0) return NLAM_EUNSUP;
+        return NLAM_MLPW_CODE(NLAM_MLPW_WIDE, 0, 0, cfg.nwv, cfg.fb);
+    }
+    const WbfPlan pl = fwd_wbf_choose(p, wns);
+    bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0;   // every chunk a whole 16-byte piece: the branch-free chunk accessors
+    for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
+    const bool sbf = (p->flags & NLAM_F_STORE_BF16) != 0;   // z1 / xhat as bf16 rows: one term, whole blocks, the shapes of store_bf16_ok()
+    if (sbf && !store_bf16_ok(p)) return NLAM_EUNSUP;
+    if (fwd_edge_ok(p, wns, v4)) return NLAM_MLPW_CODE(NLAM_MLPW_EDGE, wns, 0, 0, 0) | (sbf ? NLAM_MLPW_SBF : 0);
+    if (sbf && !(pl.cfg == 2 || pl.cfg == 3 || pl.cfg == 5 || pl.cfg == 6 || pl.cfg == 7)) return NLAM_EUNSUP;
+    if (pl.cfg < 1 || pl.cfg > 7 || (wns == 3 && pl.cfg > 5)) return NLAM_EUNSUP;
+    return NLAM_MLPW_CODE(NLAM_MLPW_WBF, wns, pl.cfg, 0, 0) | (v4 ? NLAM_MLPW_V4 : 0) | (sbf ? NLAM_MLPW_SBF : 0);
+}
+
+// nlam_mlp_bwd_wide_plan for a checked wide call with rows > 0: bwd_wbf_ns, wbf_bwd_choose, wide_cfg, the V4 predicate,
+// bwd_edge_ok and the bf16-storage table of bwd_wide and bwd_wbf
+int bwd_wide_plan(const nlam_mlp_bwd_t* p) {
+    const int wns = bwd_wbf_ns(p);
+    if (wns == 0) {
+        if (p->flags & (NLAM_F_PRE_ADD | NLAM_F_ACC_DSRC0)) return NLAM_EUNSUP;
+        const WideCfg cfg = wide_cfg(bwd_wide_maxw(p));
+        if (cfg.nwv == 0) return NLAM_EUNSUP;
+        return NLAM_MLPW_CODE(NLAM_MLPW_WIDE, 0, 0, cfg.nwv, cfg.fb);
+    }
+    const WbfBwdPlan pl = wbf_bwd_choose(bwd_wide_maxw(p));
+    const bool sbf = (p->flags & NLAM_F_STORE_BF16) != 0;
+    if (bwd_edge_ok(p)) return NLAM_MLPW_CODE(NLAM_MLPW_EDGE, wns, 0, 0, 0) | (sbf ? NLAM_MLPW_SBF : 0);
+    bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0 && p->dz2_ld == 0;
+    for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
+    if (sbf && (wns != 1 || p->hid % 32 != 0 || p->dout % 32 != 0 || p->dz2_ld != 0 || pl.cfg == 1)) return NLAM_EUNSUP;
+    if (pl.cfg != 1 && pl.cfg != 2 && pl.cfg != 3 && pl.cfg != 5) return NLAM_EUNSUP;
+    return NLAM_MLPW_CODE(NLAM_MLPW_WBF, wns, pl.cfg, 0, 0) | (v4 ? NLAM_MLPW_V4 : 0) | (sbf ? NLAM_MLPW_SBF : 0);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -5902,6 +5955,23 @@ int32_t nlam_mlp_bwd_plan(const nlam_mlp_bwd_t* p) {
     return bwd_narrow_plan(p);
 }
 
+// the instantiation a wide launch runs: the checks of nlam_mlp_fwd / nlam_mlp_bwd in their order, then the launcher's own code
+int32_t nlam_mlp_fwd_wide_plan(const nlam_mlp_fwd_t* p) {
+    const int32_t bad = nlam_detail::fwd_check(p);
+    if (bad != 0) return bad;
+    if (p->rows == 0) return NLAM_MLPW_EMPTY;
+    if (!mlp_is_wide(p)) return NLAM_MLPW_NOT_WIDE;
+    return fwd_wide_plan(p);
+}
+
+int32_t nlam_mlp_bwd_wide_plan(const nlam_mlp_bwd_t* p) {
+    const int32_t bad = nlam_detail::bwd_check(p);
+    if (bad != 0) return bad;
+    if (p->rows == 0) return NLAM_MLPW_EMPTY;
+    if (!mlp_is_wide(p)) return NLAM_MLPW_NOT_WIDE;
+    return bwd_wide_plan(p);
+}
+
 // workgroups (= rows of `vec_partials` written) per member of a grouped backward launch
 int32_t nlam_mlp_bwd_group_blocks(const nlam_mlp_bwd_t* ps, int32_t n, int32_t* blocks) {
     if (ps == nullptr || blocks == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
@@ -5971,8 +6041,10 @@ int32_t nlam_mlp_fwd(const nlam_mlp_fwd_t* p, void* hip_stream) {
     if (p->rows == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (mlp_is_wide(p)) {
-        if (fwd_wbf_ns(p) > 0) return nlam_detail::fwd_wbf(p, stream);   // split-bf16 matrix path (nlam_wbf.inc)
-        return nlam_detail::fwd_wide(p, stream);
+        const int plan = fwd_wide_plan(p);
+        if (plan < 0) return plan;
+        if (NLAM_MLPW_KERNEL(plan) != NLAM_MLPW_WIDE) return nlam_detail::fwd_wbf(p, plan, stream);   // split-bf16 matrix path (nlam_wbf.inc)
+        return nlam_detail::fwd_wide(p, plan, stream);
     }
     return nlam_detail::fwd_narrow(p, stream);
 }
@@ -5991,13 +6063,23 @@ int32_t launch_fwd_wbf(bool v4, int blocks, size_t lds, hipStream_t stream, cons
 }
 }  // namespace
 
-int32_t nlam_detail::fwd_wbf(const nlam_mlp_fwd_t* p, hipStream_t stream) {
-    const int wns = fwd_wbf_ns(p);
-    const WbfPlan pl = fwd_wbf_choose(p, wns);
+int32_t nlam_detail::fwd_wbf(const nlam_mlp_fwd_t* p, int plan, hipStream_t stream) {
+    // which instantiation: `plan`, fwd_wide_plan's code (what nlam_mlp_fwd_wide_plan answers with); only the launch shapes are decided here
+    const int wns = NLAM_MLPW_NS(plan);
+    const bool v4 = (plan & NLAM_MLPW_V4) != 0, sbf = (plan & NLAM_MLPW_SBF) != 0;
+    const WbfPlan pl = fwd_wbf_choose(p, wns);   // the geometry of the plan (rows per super tile, waves, LDS), not a second decision:
+    if (NLAM_MLPW_KERNEL(plan) == NLAM_MLPW_WBF && pl.cfg != NLAM_MLPW_PLAN(plan)) return NLAM_EINVAL;   // it must be the code's plan
     if ((p->flags & NLAM_F_WPACK_READY) == 0) {   // else: `wpack` was filled for this step already (nlam_pack_records)
         packbf_jobs_t jobs;
         const long most = build_fwd_wbf_jobs(p, wns, jobs);
         launch_pack_bf(jobs, most, wns, stream);
+    }
+    if (NLAM_MLPW_KERNEL(plan) == NLAM_MLPW_EDGE) {
+        const long ns2 = (long)((p->ntiles + 1) / 2) * p->batch;
+        const dim3 egrid((int)(ns2 < nlam_detail::chain_cus ? ns2 : nlam_detail::chain_cus)), eblock(512);
+        if (wns == 3) return launch<mlp_fwd_edge_kernel<3, 256, false>>(egrid, eblock, fwd_edge_lds<3, 256>(), stream, *p);
+        if (sbf) return launch<mlp_fwd_edge_kernel<1, 512, true>>(egrid, eblock, fwd_edge_lds<1, 512>(), stream, *p);
+        return launch<mlp_fwd_edge_kernel<1, 512, false>>(egrid, eblock, fwd_edge_lds<1, 512>(), stream, *p);
     }
     const size_t lds = fwd_wbf_lds(p, wns, pl);
     const long nsuper = (long)((p->ntiles + pl.nrt - 1) / pl.nrt) * p->batch;
@@ -6005,53 +6087,26 @@ int32_t nlam_detail::fwd_wbf(const nlam_mlp_fwd_t* p, hipStream_t stream) {
     // weight-gradient kernels of the side streams, measured 20 % slower in the captured cfg3 step: 59.8 vs 49.4 ms)
     const long wcap = pl.nw == 4 ? 2 * nlam_detail::chain_cus : nlam_detail::chain_cus;
     const int wblocks = (int)(nsuper < wcap ? (nsuper < 1 ? 1 : nsuper) : wcap);
-    bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0;   // every chunk a whole 16-byte piece: the branch-free chunk accessors
-    for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
-    // the factorised InteractionNet edge layer of one width -- d = 512 in the one-term mode (cfg5), d = 256 in the fp32-class
-    // mode (cfg3): its own software-pipelined kernel (round 6)
-    if (nlam_detail::wbf_edge != 0 && v4 && (p->flags & NLAM_F_PRE_ADD) && !(p->flags & (NLAM_F_ADD_SRC1 | NLAM_F_NO_ACT)) &&
-        p->nsrc == NLAM_MAX_SRC && p->hid == p->dout && ((wns == 1 && p->hid == 512) || (wns == 3 && p->hid == 256 && !(p->flags & NLAM_F_STORE_BF16))) &&
-        p->src[0].width == p->hid && p->src[1].width == p->hid && p->src[2].width == p->hid && p->ln_w != nullptr && p->ln_b != nullptr &&
-        p->b1 != nullptr && p->b2 != nullptr && p->aggr != nullptr && p->rowptr != nullptr && p->ncat == 0 &&
-        (long)p->ntiles * p->batch >= 2 * 64) {
-        if ((p->flags & NLAM_F_STORE_BF16) && !store_bf16_ok(p)) return NLAM_EUNSUP;
-        const long ns2 = (long)((p->ntiles + 1) / 2) * p->batch;
-        const dim3 egrid((int)(ns2 < nlam_detail::chain_cus ? ns2 : nlam_detail::chain_cus)), eblock(512);
-        // (d = 256 in the one-term mode -- cfg3 under autocast, not a BASELINE configuration -- measured no faster than the
-        // template's 4-wave shape, 103.3 vs 102.5 us on the m2m edges: not instantiated)
-        if (wns == 3) return launch<mlp_fwd_edge_kernel<3, 256, false>>(egrid, eblock, fwd_edge_lds<3, 256>(), stream, *p);
-        if (p->flags & NLAM_F_STORE_BF16) return launch<mlp_fwd_edge_kernel<1, 512, true>>(egrid, eblock, fwd_edge_lds<1, 512>(), stream, *p);
-        return launch<mlp_fwd_edge_kernel<1, 512, false>>(egrid, eblock, fwd_edge_lds<1, 512>(), stream, *p);
-    }
-    // pl.cfg -> <NS, NW, FG, FB, RT, RTP, SBF>: the instantiations that exist, one per line
-    if (p->flags & NLAM_F_STORE_BF16) {   // z1 / xhat as bf16 rows: one term, whole blocks, the shapes of store_bf16_ok()
-        if (!store_bf16_ok(p)) return NLAM_EUNSUP;
-        switch (pl.cfg) {
-        case 2: return launch_fwd_wbf<1, 8, 8, 1, 4, 2, true>(v4, wblocks, lds, stream, *p);
-        case 5: return launch_fwd_wbf<1, 4, 4, 2, 2, 1, true>(v4, wblocks, lds, stream, *p);
-        case 6: return launch_fwd_wbf<1, 4, 4, 4, 1, 1, true>(v4, wblocks, lds, stream, *p);
-        case 7: return launch_fwd_wbf<1, 4, 4, 4, 2, 2, true>(v4, wblocks, lds, stream, *p);
-        case 3: return launch_fwd_wbf<1, 8, 8, 2, 2, 1, true>(v4, wblocks, lds, stream, *p);
-        default: return NLAM_EUNSUP;
-        }
-    }
-    if (wns == 1) {
-        switch (pl.cfg) {
-        case 1: return launch_fwd_wbf<1, 8, 4, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
-        case 2: return launch_fwd_wbf<1, 8, 8, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
-        case 4: return launch_fwd_wbf<1, 8, 8, 1, 2, 2, false>(v4, wblocks, lds, stream, *p);
-        case 5: return launch_fwd_wbf<1, 4, 4, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
-        case 6: return launch_fwd_wbf<1, 4, 4, 4, 1, 1, false>(v4, wblocks, lds, stream, *p);
-        case 7: return launch_fwd_wbf<1, 4, 4, 4, 2, 2, false>(v4, wblocks, lds, stream, *p);
-        default: return launch_fwd_wbf<1, 8, 8, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
-        }
-    }
-    switch (pl.cfg) {
-    case 1: return launch_fwd_wbf<3, 8, 4, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
-    case 2: return launch_fwd_wbf<3, 8, 8, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
-    case 4: return launch_fwd_wbf<3, 8, 8, 1, 2, 2, false>(v4, wblocks, lds, stream, *p);
-    case 5: return launch_fwd_wbf<3, 4, 4, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
-    default: return launch_fwd_wbf<3, 8, 8, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    // (terms executed, plan, bf16 storage) -> <NS, NW, FG, FB, RT, RTP, SBF>: the instantiations that exist, one per line
+    switch (NLAM_MLPW_CODE(0, wns, NLAM_MLPW_PLAN(plan), 0, 0) | (sbf ? NLAM_MLPW_SBF : 0)) {
+    case NLAM_MLPW_CODE(0, 1, 2, 0, 0) | NLAM_MLPW_SBF: return launch_fwd_wbf<1, 8, 8, 1, 4, 2, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 3, 0, 0) | NLAM_MLPW_SBF: return launch_fwd_wbf<1, 8, 8, 2, 2, 1, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 5, 0, 0) | NLAM_MLPW_SBF: return launch_fwd_wbf<1, 4, 4, 2, 2, 1, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 6, 0, 0) | NLAM_MLPW_SBF: return launch_fwd_wbf<1, 4, 4, 4, 1, 1, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 7, 0, 0) | NLAM_MLPW_SBF: return launch_fwd_wbf<1, 4, 4, 4, 2, 2, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 1, 0, 0): return launch_fwd_wbf<1, 8, 4, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 2, 0, 0): return launch_fwd_wbf<1, 8, 8, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 3, 0, 0): return launch_fwd_wbf<1, 8, 8, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 4, 0, 0): return launch_fwd_wbf<1, 8, 8, 1, 2, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 5, 0, 0): return launch_fwd_wbf<1, 4, 4, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 6, 0, 0): return launch_fwd_wbf<1, 4, 4, 4, 1, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 7, 0, 0): return launch_fwd_wbf<1, 4, 4, 4, 2, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 1, 0, 0): return launch_fwd_wbf<3, 8, 4, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 2, 0, 0): return launch_fwd_wbf<3, 8, 8, 1, 4, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 3, 0, 0): return launch_fwd_wbf<3, 8, 8, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 4, 0, 0): return launch_fwd_wbf<3, 8, 8, 1, 2, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 5, 0, 0): return launch_fwd_wbf<3, 4, 4, 2, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    default: return NLAM_EUNSUP;
     }
 }
 #endif
@@ -6061,14 +6116,15 @@ namespace {
 // wide_cfg's three workgroup shapes as the template arguments <NWV, FB> of the fp32 wide kernels
 template <typename F>
 int32_t pick_wide(const WideCfg& cfg, F&& f) {
-    if (cfg.nwv == 4) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{});
-    if (cfg.fb == 1) return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{});
-    return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
+    if (cfg.nwv == 4 && cfg.fb == 1) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{});
+    if (cfg.nwv == 8 && cfg.fb == 1) return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{});
+    if (cfg.nwv == 8 && cfg.fb == 2) return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
+    return NLAM_EUNSUP;
 }
 }  // namespace
 
-int32_t nlam_detail::fwd_wide(const nlam_mlp_fwd_t* p, hipStream_t stream) {
-    const WideCfg cfg = wide_cfg(p->hid > p->dout ? p->hid : p->dout);
+int32_t nlam_detail::fwd_wide(const nlam_mlp_fwd_t* p, int plan, hipStream_t stream) {   // plan: fwd_wide_plan's code, <NWV, FB>
+    const WideCfg cfg = {NLAM_MLPW_NWV(plan), NLAM_MLPW_FB(plan)};
     if ((p->flags & NLAM_F_WPACK_READY) == 0) {
         pack_jobs_t jobs;
         build_fwd_wide_jobs(p, jobs);
@@ -6206,9 +6262,10 @@ int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream) {
     if (p->rows == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (mlp_is_wide(p)) {
-        if (bwd_wbf_ns(p) > 0) return nlam_detail::bwd_wbf(p, stream);   // split-bf16 matrix path (nlam_wbf.inc)
-        if (p->flags & NLAM_F_ACC_DSRC0) return NLAM_EUNSUP;
-        return nlam_detail::bwd_wide(p, stream);
+        const int plan = bwd_wide_plan(p);   // (NLAM_F_ACC_DSRC0 outside the split-bf16 family: NLAM_EUNSUP)
+        if (plan < 0) return plan;
+        if (NLAM_MLPW_KERNEL(plan) != NLAM_MLPW_WIDE) return nlam_detail::bwd_wbf(p, plan, stream);   // split-bf16 matrix path (nlam_wbf.inc)
+        return nlam_detail::bwd_wide(p, plan, stream);
     }
     if (p->flags & NLAM_F_ACC_DSRC0) return NLAM_EUNSUP;
     return nlam_detail::bwd_narrow(p, stream);
@@ -6228,53 +6285,46 @@ int32_t launch_bwd_wbf(bool v4, int blocks, size_t lds, hipStream_t stream, cons
 }
 }  // namespace
 
-int32_t nlam_detail::bwd_wbf(const nlam_mlp_bwd_t* p, hipStream_t stream) {
-    const int wns = bwd_wbf_ns(p);
-    const WbfBwdPlan pl = wbf_bwd_choose(bwd_wide_maxw(p));
+int32_t nlam_detail::bwd_wbf(const nlam_mlp_bwd_t* p, int plan, hipStream_t stream) {
+    // which instantiation: `plan`, bwd_wide_plan's code (what nlam_mlp_bwd_wide_plan answers with)
+    const int wns = NLAM_MLPW_NS(plan);
+    const bool v4 = (plan & NLAM_MLPW_V4) != 0, sbf = (plan & NLAM_MLPW_SBF) != 0;
+    const WbfBwdPlan pl = wbf_bwd_choose(bwd_wide_maxw(p));   // the geometry of the code's plan
+    if (NLAM_MLPW_KERNEL(plan) == NLAM_MLPW_WBF && pl.cfg != NLAM_MLPW_PLAN(plan)) return NLAM_EINVAL;
     if ((p->flags & NLAM_F_WPACK_READY) == 0) {
         packbf_jobs_t jobs;
         const long most = build_bwd_wbf_jobs(p, wns, jobs);
         launch_pack_bf(jobs, most, wns, stream);
     }
-    if (bwd_edge_ok(p)) {
+    if (NLAM_MLPW_KERNEL(plan) == NLAM_MLPW_EDGE) {
         const dim3 egrid(nlam_mlp_bwd_blocks(p)), eblock(512);
         if (wns == 3) return launch<mlp_bwd_edge_kernel<3, 256, false>>(egrid, eblock, bwd_edge_lds<3, 256>(), stream, *p);
-        if (p->flags & NLAM_F_STORE_BF16) return launch<mlp_bwd_edge_kernel<1, 512, true>>(egrid, eblock, bwd_edge_lds<1, 512>(), stream, *p);
+        if (sbf) return launch<mlp_bwd_edge_kernel<1, 512, true>>(egrid, eblock, bwd_edge_lds<1, 512>(), stream, *p);
         return launch<mlp_bwd_edge_kernel<1, 512, false>>(egrid, eblock, bwd_edge_lds<1, 512>(), stream, *p);
     }
     const size_t lds = bwd_wbf_lds(p, wns, pl);
     const int wblocks = nlam_mlp_bwd_blocks(p) / pl.rg;
-    bool v4 = nlam_detail::wbf_v4 != 0 && p->hid % 4 == 0 && p->dout % 4 == 0 && p->dz2_ld == 0;
-    for (int s_ = 0; s_ < p->nsrc; ++s_) v4 = v4 && p->src[s_].width % 4 == 0;
-    // pl.cfg -> <NS, NW, FG, FB, RT, SBF>: the instantiations that exist, one per line
-    if (p->flags & NLAM_F_STORE_BF16) {
-        if (wns != 1 || p->hid % 32 != 0 || p->dout % 32 != 0 || p->dz2_ld != 0 || pl.cfg == 1) return NLAM_EUNSUP;
-        switch (pl.cfg) {
-        case 2: return launch_bwd_wbf<1, 8, 8, 1, 2, true>(v4, wblocks, lds, stream, *p);
-        case 5: return launch_bwd_wbf<1, 4, 4, 2, 1, true>(v4, wblocks, lds, stream, *p);
-        default: return launch_bwd_wbf<1, 8, 8, 2, 1, true>(v4, wblocks, lds, stream, *p);
-        }
-    }
-    if (wns == 1) {
-        switch (pl.cfg) {
-        case 1: return launch_bwd_wbf<1, 8, 4, 1, 2, false>(v4, wblocks, lds, stream, *p);
-        case 2: return launch_bwd_wbf<1, 8, 8, 1, 2, false>(v4, wblocks, lds, stream, *p);
-        case 5: return launch_bwd_wbf<1, 4, 4, 2, 1, false>(v4, wblocks, lds, stream, *p);
-        default: return launch_bwd_wbf<1, 8, 8, 2, 1, false>(v4, wblocks, lds, stream, *p);
-        }
-    }
-    switch (pl.cfg) {
-    case 1: return launch_bwd_wbf<3, 8, 4, 1, 2, false>(v4, wblocks, lds, stream, *p);
-    case 2: return launch_bwd_wbf<3, 8, 8, 1, 2, false>(v4, wblocks, lds, stream, *p);
-    case 5: return launch_bwd_wbf<3, 4, 4, 2, 1, false>(v4, wblocks, lds, stream, *p);
-    default: return launch_bwd_wbf<3, 8, 8, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    // (terms executed, plan, bf16 storage) -> <NS, NW, FG, FB, RT, SBF>: the instantiations that exist, one per line
+    switch (NLAM_MLPW_CODE(0, wns, NLAM_MLPW_PLAN(plan), 0, 0) | (sbf ? NLAM_MLPW_SBF : 0)) {
+    case NLAM_MLPW_CODE(0, 1, 2, 0, 0) | NLAM_MLPW_SBF: return launch_bwd_wbf<1, 8, 8, 1, 2, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 3, 0, 0) | NLAM_MLPW_SBF: return launch_bwd_wbf<1, 8, 8, 2, 1, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 5, 0, 0) | NLAM_MLPW_SBF: return launch_bwd_wbf<1, 4, 4, 2, 1, true>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 1, 0, 0): return launch_bwd_wbf<1, 8, 4, 1, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 2, 0, 0): return launch_bwd_wbf<1, 8, 8, 1, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 3, 0, 0): return launch_bwd_wbf<1, 8, 8, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 1, 5, 0, 0): return launch_bwd_wbf<1, 4, 4, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 1, 0, 0): return launch_bwd_wbf<3, 8, 4, 1, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 2, 0, 0): return launch_bwd_wbf<3, 8, 8, 1, 2, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 3, 0, 0): return launch_bwd_wbf<3, 8, 8, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    case NLAM_MLPW_CODE(0, 3, 5, 0, 0): return launch_bwd_wbf<3, 4, 4, 2, 1, false>(v4, wblocks, lds, stream, *p);
+    default: return NLAM_EUNSUP;
     }
 }
 #endif
 
 #if NLAM_IN_TU(3)
-int32_t nlam_detail::bwd_wide(const nlam_mlp_bwd_t* p, hipStream_t stream) {
-    const WideCfg cfg = wide_cfg(bwd_wide_maxw(p));
+int32_t nlam_detail::bwd_wide(const nlam_mlp_bwd_t* p, int plan, hipStream_t stream) {   // plan: bwd_wide_plan's code, <NWV, FB>
+    const WideCfg cfg = {NLAM_MLPW_NWV(plan), NLAM_MLPW_FB(plan)};
     if ((p->flags & NLAM_F_WPACK_READY) == 0) {
         pack_jobs_t jobs;
         build_bwd_wide_jobs(p, jobs);

@@ -1307,6 +1307,9 @@ int fwd_wbf_ns(const nlam_mlp_fwd_t* p) {
     for (int s = 0; s < p->nsrc; ++s)
         if (p->src[s].width % 4 != 0) return 0;
     if (p->hid % 4 != 0) return 0;
+    // the aggregation of these kernels (block_segment_reduce) writes whole float4s of a receiver's row: with an output width that
+    // is no multiple of 4 its last dout % 4 columns would never be written -- the fp32 kernels reduce element by element
+    if (p->aggr != nullptr && p->dout % 4 != 0) return 0;
     if (p->flags & NLAM_F_PRE_ADD)   // addends of width hid, whole 32-feature blocks, no PropagationNet sender term
         for (int s = 1; s < p->nsrc; ++s)
             if (p->src[s].width != p->hid || p->hid % 32 != 0 || (p->flags & NLAM_F_ADD_SRC1)) return 0;
