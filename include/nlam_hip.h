@@ -461,8 +461,13 @@ int32_t nlam_mlp_bwd(const nlam_mlp_bwd_t* p, void* hip_stream);
  * (wpack_floats >= the workspace query; nothing is packed, the weights are read in nn.Linear layout).  Matrix modes: one bf16
  * term for NLAM_F_MM_BF16X1, three terms for every other mode (f32 and bf16x2 included).  Not served (NLAM_EUNSUP):
  * NLAM_F_PRE_ADD, NLAM_F_STORE_BF16, NLAM_F_ACC_DSRC0, NLAM_F_LEAF_WGRAD, concatenated pieces (ncat > 0).  The backward needs
- * z1, dz1 and dz2 (dz2_ld 0 or dout) and writes nlam_mlp_bwd_gemm_blocks(p) rows of vec_partials.  Workspace queries return
- * the floats, or the NLAM_EINVAL / NLAM_EUNSUP the launch would return. */
+ * z1, dz1 and dz2 (dz2_ld 0 or dout) and writes nlam_mlp_bwd_gemm_blocks(p) rows of vec_partials (always 256; blocks without
+ * rows hold zeros).  Workspace queries return the floats, or the NLAM_EINVAL / NLAM_EUNSUP the launch would return; a forward
+ * with z1 == NULL keeps z1 in the workspace (the query grows by batch * rows * hid).  Every sum has a fixed order and the results
+ * are bit-identical run to run, EXCEPT over NLAM_TILE_SPLIT tiles: the pieces of such a receiver are added with atomicAdd, in no
+ * fixed order, into a destination the caller must have zeroed -- this applies to both `aggr` (forward) and every dmode-3 `dsrc`
+ * (backward).  rows == 0 returns 0 without a workspace: `aggr` rows and dmode-3 `dsrc` rows of the receivers the tile list covers
+ * and the vec_partials rows are written as zeros, nothing else is written. */
 int64_t nlam_mlp_fwd_gemm_workspace_floats(const nlam_mlp_fwd_t* p);
 int64_t nlam_mlp_bwd_gemm_workspace_floats(const nlam_mlp_bwd_t* p);
 int32_t nlam_mlp_bwd_gemm_blocks(const nlam_mlp_bwd_t* p);

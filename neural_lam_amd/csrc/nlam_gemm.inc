@@ -14,7 +14,10 @@
 //             dX  = dz1 W1 (+ residual gradients), per source scattered (dmode 1), tile-row order (2) or staged for the
 //                   segment sum (3)                         gemm_kernel (W1 read as (k, n)) + tile_segsum_kernel
 //             db1, db2, dgamma, dbeta partial rows         colsum_partials_kernel (fixed row blocks, fixed order)
-// Every reduction has a fixed order: the results are bit-identical run to run.
+// Every reduction but one has a fixed order: the results are bit-identical run to run.  The exception are tile lists with
+// NLAM_TILE_SPLIT tiles (the one-pass split mode): tile_segsum_kernel adds each piece of such a receiver with atomicAdd, in no
+// fixed order, into a destination the CALLER must have zeroed -- `aggr` in the forward and every dmode-3 `dsrc` in the backward
+// (ops.py allocates both with torch.zeros on that path).  The virtual split + nlam_split_combine keeps the fixed order.
 //
 // gemm_kernel: 128 x 128 output tiles, 256 threads (2 x 2 waves of 64 x 64), K staged through LDS in steps of 32 (fp32,
 // register-prefetched one step ahead), products on v_mfma_f32_32x32x16_bf16 with each operand split into NS bf16 terms and

@@ -1,10 +1,11 @@
-"""Shared machinery of the kernel-level fused-MLP suites (test_mlp_narrow_kernels.py, test_mlp_wide_kernels.py): the case
-record, the problem builder, the float64 math of the contract of include/nlam_hip.h with its first-order error budget, the two
-comparison functions, the launch-descriptor fillers and the device-buffer helper with NaN fill and NaN guard rows.  A plain module,
-imported by both files; nothing here is collected by pytest."""
+"""Shared machinery of the kernel-level MLP suites (test_mlp_narrow_kernels.py, test_mlp_wide_kernels.py,
+test_mlp_gemm_kernels.py): the case record, the problem builder, the float64 math of the contract of include/nlam_hip.h with its
+first-order error budget, the two comparison functions, the tiers' problems and the CPU stand-in for a kernel, the
+launch-descriptor fillers and the device-buffer helper with NaN fill and NaN guard rows.  A plain module, imported by the three
+files; nothing here is collected by pytest."""
 import ctypes as C
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from types import SimpleNamespace as NS
 
 import numpy as np
@@ -76,6 +77,9 @@ class Case:
     sbf: bool = False          # NLAM_F_STORE_BF16: z1 / xhat (forward) and dz1 / dz2 (backward) are rows of bf16
     acc0: bool = False         # NLAM_F_ACC_DSRC0: dsrc[0] is pre-filled and added to
     tune: tuple = ()           # (key, value) pairs for nlam_set_tuning (the wide file's fixture sets and restores them)
+    ldw1_pad: int = 0          # floats between rows of W1 beyond the width sum, without NLAM_F_PRE_ADD (the tiled-GEMM family)
+    ln_beta: bool = True       # False: LayerNorm without ln_b (ln_b = NULL)
+    rowseg: bool = False       # aggregation without a tile list (tiles = NULL): every row is its own segment, through rowptr
 
     def __str__(self):
         return self.name
@@ -117,7 +121,7 @@ def build_problem(case, seed, kind, irange=4):
     gen = torch.Generator().manual_seed(seed)
     c = case
     P = NS(case=c, batch=c.batch, hid=c.hid, dout=c.dout, nsrc=len(c.widths), eps=EPS, irange=irange)
-    P.tiles = P.rowptr = P.scale = P.seg_of_row = P.comb = P.out_idx = None
+    P.tiles = P.rowptr = P.scale = P.seg_of_row = P.comb = P.out_idx = P.rowptr_dev = P.inv_deg_dev = None
     P.nseg = P.nseg_rows = 0
     P.has_split = False
     if c.graph:
@@ -141,6 +145,11 @@ def build_problem(case, seed, kind, irange=4):
         assert int((tiles[:, 1] < 32).sum()) >= 2   # tiles of fewer than 32 rows made of whole receivers
     else:
         P.rows = c.rows
+        if c.rowseg:   # no tile list: tile t is rows 32 t .. 32 t + 31, every row a segment of its own
+            P.nseg = P.nseg_rows = c.rows
+            P.rowptr_dev, P.inv_deg_dev = torch.arange(c.rows + 1), torch.ones(c.rows)
+            P.seg_of_row = torch.arange(c.rows)
+            P.scale = P.deg = torch.ones(c.rows, dtype=torch.float64)
     P.ntiles = P.tiles.shape[0] if P.tiles is not None else -(-P.rows // 32)
     rows = P.rows
     P.srcs = []
@@ -169,7 +178,7 @@ def build_problem(case, seed, kind, irange=4):
         if c.dmode[k] == 1:
             assert idx is None or idx.unique().numel() == nr == rows, "dmode 1 scatters through a unique index"
         if c.dmode[k] == 3:
-            assert c.graph and c.roles[k] == "r"
+            assert (c.graph and c.roles[k] == "r") or (c.rowseg and idx is None)
     if c.cat:   # src[0] = the row-wise concatenation of pieces
         assert sum(c.cat) == c.widths[0] and len(c.widths) == 1
         X = P.srcs[0].S
@@ -182,7 +191,7 @@ def build_problem(case, seed, kind, irange=4):
             P.pieces.append(piece.contiguous())
             off += w
     kg = c.widths[0] if c.pre else sum(c.widths)   # columns of W1 that go through GEMM1
-    P.kg, P.ldw1 = kg, (kg + c.ldw1_extra if c.pre else kg)
+    P.kg, P.ldw1 = kg, (kg + c.ldw1_extra if c.pre else kg + c.ldw1_pad)
     if kind == "int":
         P.W1 = _values(gen, (c.hid, P.ldw1), 0, "int", irange)
         P.W2 = _values(gen, (c.dout, c.hid), 0, "int", irange)
@@ -205,6 +214,8 @@ def build_problem(case, seed, kind, irange=4):
         gs = 2.0 ** torch.randint(-3, 4, (c.dout,), generator=gen).double()
         P.gamma = ((1.0 + 0.3 * torch.randn((c.dout,), generator=gen, dtype=torch.float64)) * gs).float().double()
         P.beta = (torch.randn((c.dout,), generator=gen, dtype=torch.float64) * gs).float().double()
+    if not c.ln_beta:
+        P.beta = torch.zeros_like(P.beta)
     P.out_rows = rows
     if c.out_perm:
         P.out_idx = P.csr.perm.long() if c.graph else torch.randperm(rows, generator=gen)
@@ -271,6 +282,13 @@ def forward_math(P, dt=torch.float64, ns=0, z1_given=None, defect=None):
         X = X.clone()
         r = 127 if X.shape[1] > 128 else X.shape[1] - 2
         X[:, r] = X[:, r + 1]
+    # the tiled-GEMM family's own: operands concatenated on load, row tiles that straddle batch items, ragged column tiles
+    if defect == "boundary_column_from_neighbour":   # the first column of source 1 attributed to source 0: read behind source 0's row
+        X = X.clone()
+        X[..., c.widths[0]] = torch.roll(xs[0][..., 0], -1, 1)
+    if defect == "second_item_first_row_from_first_item":   # the first row of the second batch item, with the first item's batch offset
+        X = X.clone()
+        X[1, 0] = X[0, 0]
     if defect == "drop_third_term":   # x as two bf16 terms
         x1 = X.to(torch.bfloat16).to(dt)
         X = x1 + (X - x1).to(torch.bfloat16).to(dt)
@@ -280,7 +298,11 @@ def forward_math(P, dt=torch.float64, ns=0, z1_given=None, defect=None):
     z1 = X @ W1g.T + f(P.b1)
     for a in adds:
         z1 = z1 + a
-    A1 = X.abs() @ W1g.abs().T + f(P.b1).abs() + sum(a.abs() for a in adds)
+    if defect == "last_column_tile_without_bias":   # the ragged last 128-column tile of z1
+        z1 = z1.clone()
+        n0 = 128 * ((c.hid - 1) // 128)
+        z1[..., n0:] -= f(P.b1)[n0:]
+    A1 =X.abs() @ W1g.abs().T + f(P.b1).abs() + sum(a.abs() for a in adds)
     E_z1 = (U * (P.kg + len(adds) + 2) + MODE_TERM[ns]) * A1
     z1_stored, E_z1_stored = z1, E_z1
     if c.sbf:
@@ -362,7 +384,8 @@ def backward_math(P, saved, dt=torch.float64, ns=0, defect=None, nblk=1):
         go = f(P.g_out)[:, P.out_idx] if P.out_idx is not None else f(P.g_out)
     dm, E_dm = go, torch.zeros_like(zero)
     if P.g_aggr is not None:
-        ga = (f(P.g_aggr) * f(P.scale)[None, :, None])[:, P.seg_of_row]
+        sc = torch.ones_like(P.scale) if defect == "mean_scale_missing_in_backward" else P.scale
+        ga = (f(P.g_aggr) * f(sc)[None, :, None])[:, P.seg_of_row]
         dm = go + ga
         E_dm = (U * ga.abs() if c.mean else 0) + (U * dm.abs() if P.g_out is not None else 0) + E_dm
     val, bud = {}, {}
@@ -382,6 +405,8 @@ def backward_math(P, saved, dt=torch.float64, ns=0, defect=None, nblk=1):
         dz2, E_dz2 = dm, E_dm
     W2 = f(P.W2)
     dh = dz2 @ W2
+    if defect == "w2_untransposed_in_dz1":   # the (dout, hid) rows of W2 read as (hid, dout) rows
+        dh = dz2 @ W2.reshape(c.hid, c.dout).T
     E_dh = E_dz2 @ W2.abs() + (U * (c.dout + 2) + MODE_TERM[ns]) * (dz2.abs() @ W2.abs())
     if c.no_act:
         dz1, E_dz1 = dh, E_dh
@@ -415,6 +440,9 @@ def backward_math(P, saved, dt=torch.float64, ns=0, defect=None, nblk=1):
         if mode == 0:
             continue
         if mode == 1 and idx is not None:
+            if defect == "dmode1_scatter_through_wrong_index":   # another source's index (identity where that source has none)
+                other = P.srcs[(k + 1) % P.nsrc].idx
+                idx = other if (other is not None and other.unique().numel() == P.rows) else torch.arange(P.rows)
             o, E_o = torch.empty_like(dx), torch.empty_like(E_dx)
             o[:, idx], E_o[:, idx] = dx, E_dx
             dx, E_dx = o, E_o
@@ -500,9 +528,9 @@ def describe_fwd(P, a):
         p.src[k].ptr, p.src[k].idx, p.src[k].bstride, p.src[k].width = a(f"src{k}"), a(f"idx{k}"), s.bstride, s.width
     p.nsrc, p.batch, p.rows, p.ntiles, p.tiles = P.nsrc, P.batch, P.rows, P.ntiles, a("tiles")
     p.W1, p.b1, p.W2, p.b2 = a("W1"), a("b1"), a("W2"), a("b2")
-    p.ln_w, p.ln_b = (a("gamma"), a("beta")) if c.ln else (None, None)
+    p.ln_w, p.ln_b = (a("gamma"), a("beta") if c.ln_beta else None) if c.ln else (None, None)
     p.eps, p.hid, p.dout, p.flags = 1e-5, c.hid, c.dout, case_flags(c)
-    p.ldw1 = P.ldw1 if c.pre else 0
+    p.ldw1 = P.ldw1 if (c.pre or c.ldw1_pad) else 0
     if c.want_out:
         p.out, p.out_idx, p.out_bstride = a("out"), a("out_idx"), P.out_rows * c.dout
     if c.aggregate:
@@ -531,12 +559,12 @@ def describe_bwd(P, a, lib):
     p.nsrc, p.batch, p.rows, p.ntiles, p.tiles = P.nsrc, P.batch, P.rows, P.ntiles, a("tiles")
     p.W1, p.W2, p.ln_w = a("W1"), a("W2"), a("gamma") if c.ln else None
     p.hid, p.dout, p.flags, p.nseg_total = c.hid, c.dout, case_flags(c, backward=True), P.nseg
-    p.ldw1 = P.ldw1 if c.pre else 0
+    p.ldw1 = P.ldw1 if (c.pre or c.ldw1_pad) else 0
     if c.g_out:
         p.g_out, p.out_idx, p.out_bstride = a("g_out"), a("out_idx"), P.out_rows * c.dout
     if c.g_aggr:
         p.g_aggr, p.seg_of_row = a("g_aggr"), a("seg_of_row")
-    if c.graph:
+    if c.graph or c.rowseg:
         p.rowptr, p.inv_deg = a("rowptr"), a("inv_deg")
     p.z1 = a("z1")
     if c.ln:
@@ -575,6 +603,7 @@ class Dev:
                 self.t[n] = f32(getattr(P, n))
         if P.tiles is not None:
             self.t["tiles"] = i32(P.tiles)
+        if P.rowptr_dev is not None:
             self.t["rowptr"], self.t["inv_deg"], self.t["seg_of_row"] = i32(P.rowptr_dev), f32(P.inv_deg_dev), i32(P.seg_of_row)
             if P.comb is not None:
                 self.comb = [i32(x) for x in P.comb]
@@ -624,3 +653,118 @@ def _same(a, b):
 
 def _saved_dev(res):
     return {n: res[n].cuda() for n in ("z1", "xhat", "rstd") if n in res}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the tiers' problems and references, and the CPU stand-in for a kernel (shared by the wide and the tiled-GEMM files)
+# ---------------------------------------------------------------------------------------------------------------------------
+def int_problem(case, seed):
+    """Tier (a): the largest integer range of 4, 2, 1 for which every sum of absolute values of the quantities compared exactly
+    stays below 2^24 (exact_headroom, float64): every partial sum, in any order, is then an exact fp32 value."""
+    for r in (4, 2, 1):
+        P = build_problem(case, seed, "int", irange=r)
+        if exact_headroom(P) < 2.0 ** 24:
+            return P
+    raise AssertionError(f"{case}: no integer range keeps the sums below 2^24")
+
+
+def exact_headroom(P):
+    c = P.case
+    xs = _gathered(P, torch.float64, None)
+    X = xs[0] if c.pre else torch.cat(xs, -1)
+    W1 = P.W1[:, : P.kg].abs()
+    A = X.abs() @ W1.T + P.b1.abs() + sum(a.abs() for a in (xs[1:] if c.pre else []))
+    top = float(A.max())
+    chain = c.no_act and not c.ln and not c.mean
+    if c.ln or c.mean:
+        return top
+    go = P.g_out.abs() if P.g_out is not None else 0
+    if P.g_out is not None and P.out_idx is not None:
+        go = go[:, P.out_idx]
+    dm = go + (P.g_aggr.abs()[:, P.seg_of_row] if P.g_aggr is not None else 0)
+    top = max(top, float(dm.sum((0, 1)).max()))   # db2
+    if not chain:
+        return top
+    Y = A @ P.W2.abs().T + P.b2.abs() + (xs[1].abs() if c.add1 else 0)
+    top = max(top, float(Y.max()) + (float(xs[0].abs().max()) if c.add0 else 0))
+    if c.aggregate:
+        top = max(top, float(_segsum(Y, P.seg_of_row, P.nseg).max()))
+    dh = dm @ P.W2.abs()
+    dX = dh @ W1 + float(dm.max())
+    top = max(top, float(dh.sum((0, 1)).max()), float(dX.max()))
+    if 3 in c.dmode:
+        top = max(top, float(_segsum(dX, P.seg_of_row, P.nseg).max()))
+    return top
+
+
+def rand_problem(case, seed):
+    """Tier (b): the budget is first order in 1 / (var + eps), so the pre-LayerNorm row variance must be well above eps."""
+    P = build_problem(case, seed, "rand")
+    if case.ln:
+        forward_math(P)
+        assert P.var_min > 1e3 * P.eps, f"{case}: a row variance of {P.var_min:.3g} is too close to eps for a first-order bound"
+    return P
+
+
+def exact_reference(case, ref, forward):
+    """Tier (a): the float64 values as the kernel must store them -- with bf16 storage, rounded once to nearest even."""
+    if forward and case.sbf:
+        ref = {**ref, "z1": to_bf16(ref["z1"])}
+    return ref
+
+
+def low_reference(P, ns):
+    """Tier (c): z1 of the probe.  Three terms and fp32 keep every term of W1: the float64 value; one term keeps the leading
+    one: +-count + integers."""
+    ref, _ = forward_math(P)
+    z1 = ref["z1"]
+    if ns == 1:
+        P1 = replace_weights(P, torch.sign(P.W1))
+        z1 = forward_math(P1)[0]["z1"]
+    assert float(z1.abs().max()) < (LOW_ONES + 16) * LOW_W and torch.equal(z1.float().double(), z1), "the probe's z1 must be an exact fp32 value"
+    return to_bf16(z1) if P.case.sbf else z1
+
+
+def replace_weights(P, W1):
+    Q = type(P)(**vars(P))
+    Q.W1 = W1
+    return Q
+
+
+def replace_case(P, **kw):
+    Q = type(P)(**vars(P))
+    Q.case = replace(P.case, **kw)
+    return Q
+
+
+STANDIN_NBLK = 16
+
+
+def standin_run(case, kind, defect=None, ns_claimed=0, nblk=STANDIN_NBLK):
+    """The MLP in torch fp32 on the CPU (bf16 rounding where the case stores bf16) with an optional defect, compared like a kernel ->
+    names of the failing quantities, forward first.  nblk: the workgroups the stand-in deals the rows of the four vectors to."""
+    P = int_problem(case, 7) if kind == "int" else rand_problem(case, 7) if kind == "rand" else build_problem(case, 7, kind)
+    ref_f, bud_f = forward_math(P, ns=ns_claimed)
+    got_f, _ = forward_math(P, torch.float32, defect=defect)
+    if kind == "low":
+        return [] if torch.equal(got_f["z1"].double(), low_reference(P, ns_claimed)) else ["z1"]
+    saved = {k: got_f[k] for k in ("z1", "xhat", "rstd") if k in got_f}
+    ref_b, bud_b = backward_math(P, {k: v.double() for k, v in saved.items()}, ns=ns_claimed, nblk=nblk)
+    got_b, _ = backward_math(P, saved, torch.float32, defect=defect)
+    c = case
+    dm = 0   # a case may have g_out only, g_aggr only, or both
+    if P.g_out is not None:
+        dm = P.g_out[:, P.out_idx] if P.out_idx is not None else P.g_out
+    if P.g_aggr is not None:
+        dm = dm + (P.g_aggr * P.scale[None, :, None])[:, P.seg_of_row]
+    dm = dm.float()
+    # the four vectors as a kernel leaves them: per-workgroup partial sums of what it holds in fp32, summed in float64
+    unrounded = got_b if not c.sbf else backward_math(replace_case(P, sbf=False), saved, torch.float32, defect=defect)[0]
+    rows = {"db1": unrounded["dz1"], "db2": unrounded["dz2"]}
+    if c.ln:
+        rows.update(dgamma=dm * saved["xhat"], dbeta=dm)
+    got_b.update(block_vectors(P, rows, nblk, skip=1 if defect == "skip_vec_partials_block" else None))
+    if kind == "int":
+        return (compare_exact(got_f, exact_reference(c, ref_f, True), exact_quantities(c, True))
+                + compare_exact(got_b, ref_b, exact_quantities(c, False)))
+    return compare_bounded(got_f, ref_f, bud_f) + compare_bounded(got_b, ref_b, bud_b)

@@ -30,9 +30,10 @@ import torch
 
 from neural_lam_amd import _lib as L
 
-from mlp_kernel_ref import (LOW_ONES, LOW_W, Case, Dev, _combine, _gathered, _same, _segsum, _stream, _written, backward_math,
-                            block_vectors, build_problem, compare_bounded, compare_exact, describe_bwd, describe_fwd, dsrc_rows,
-                            exact_quantities, forward_math, to_bf16)
+from mlp_kernel_ref import (Case, Dev, _combine, _same, _stream, _written, backward_math, build_problem,  # noqa: F401
+                            compare_bounded, compare_exact, describe_bwd, describe_fwd, dsrc_rows, exact_headroom, exact_quantities,
+                            exact_reference, forward_math, int_problem, low_reference, rand_problem, replace_case, standin_run,
+                            to_bf16)
 
 gpu = pytest.mark.gpu
 
@@ -290,52 +291,8 @@ CASE_BY_NAME = {c.name: c for c in CASES}
 assert len(CASE_BY_NAME) == len(CASES)
 
 
-def int_problem(case, seed):
-    """Tier (a): the largest integer range of 4, 2, 1 for which every sum of absolute values of the quantities compared exactly
-    stays below 2^24 (exact_headroom, float64): every partial sum, in any order, is then an exact fp32 value."""
-    for r in (4, 2, 1):
-        P = build_problem(case, seed, "int", irange=r)
-        if exact_headroom(P) < 2.0 ** 24:
-            return P
-    raise AssertionError(f"{case}: no integer range keeps the sums below 2^24")
-
-
-def exact_headroom(P):
-    c = P.case
-    xs = _gathered(P, torch.float64, None)
-    X = xs[0] if c.pre else torch.cat(xs, -1)
-    W1 = P.W1[:, : P.kg].abs()
-    A = X.abs() @ W1.T + P.b1.abs() + sum(a.abs() for a in (xs[1:] if c.pre else []))
-    top = float(A.max())
-    chain = c.no_act and not c.ln and not c.mean
-    if c.ln or c.mean:
-        return top
-    go = P.g_out.abs() if P.g_out is not None else 0
-    if P.g_out is not None and P.out_idx is not None:
-        go = go[:, P.out_idx]
-    dm = go + (P.g_aggr.abs()[:, P.seg_of_row] if P.g_aggr is not None else 0)
-    top = max(top, float(dm.sum((0, 1)).max()))   # db2
-    if not chain:
-        return top
-    Y = A @ P.W2.abs().T + P.b2.abs() + (xs[1].abs() if c.add1 else 0)
-    top = max(top, float(Y.max()) + (float(xs[0].abs().max()) if c.add0 else 0))
-    if c.aggregate:
-        top = max(top, float(_segsum(Y, P.seg_of_row, P.nseg).max()))
-    dh = dm @ P.W2.abs()
-    dX = dh @ W1 + float(dm.max())
-    top = max(top, float(dh.sum((0, 1)).max()), float(dX.max()))
-    if 3 in c.dmode:
-        top = max(top, float(_segsum(dX, P.seg_of_row, P.nseg).max()))
-    return top
-
-
-def rand_problem(case, seed):
-    """Tier (b): the budget is first order in 1 / (var + eps), so the pre-LayerNorm row variance must be well above eps."""
-    P = build_problem(case, seed, "rand")
-    if case.ln:
-        forward_math(P)
-        assert P.var_min > 1e3 * P.eps, f"{case}: a row variance of {P.var_min:.3g} is too close to eps for a first-order bound"
-    return P
+# (int_problem, exact_headroom, rand_problem, low_reference, standin_run and replace_case live in mlp_kernel_ref.py: the tiled-GEMM
+# file uses them too)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -345,7 +302,6 @@ STANDIN_1536 = Case("standin_k1536", 0, 0, (512, 512, 512), 512, 512, graph="mix
                     dmode=(1, 2, 3), g_aggr=True)
 STANDIN_512 = Case("standin_k512", 0, 0, (256, 128, 128), 320, 256, graph="split9", add0=True, aggregate=True, out_perm=True,
                    dmode=(1, 2, 3), g_aggr=True, acc0=True)
-STANDIN_NBLK = 16
 DEFECTS = ["drop_input_column", "swap_gather_indices", "omit_residual", "tile_last_row_not_aggregated", "rstd_without_eps",
            "sigmoid_for_silu_derivative", "skip_vec_partials_block", "drop_w1_third_term",
            "supertile_last_row_from_neighbour", "drop_dout_block_in_gemm2", "dsrc0_overwritten", "z1_truncated_bf16"]
@@ -353,63 +309,6 @@ FIRST = {"drop_input_column": "z1", "swap_gather_indices": "z1", "omit_residual"
          "rstd_without_eps": "rstd", "sigmoid_for_silu_derivative": "dz1", "skip_vec_partials_block": "db1", "drop_w1_third_term": "z1",
          "supertile_last_row_from_neighbour": "z1", "drop_dout_block_in_gemm2": "xhat", "dsrc0_overwritten": "dsrc0",
          "z1_truncated_bf16": "z1"}
-
-
-def exact_reference(case, ref, forward):
-    """Tier (a): the float64 values as the kernel must store them -- with bf16 storage, rounded once to nearest even."""
-    if forward and case.sbf:
-        ref = {**ref, "z1": to_bf16(ref["z1"])}
-    return ref
-
-
-def low_reference(P, ns):
-    """Tier (c): z1 of the probe.  Three terms and fp32 keep every term of W1: the float64 value; one term keeps the leading
-    one: +-count + integers."""
-    ref, _ = forward_math(P)
-    z1 = ref["z1"]
-    if ns == 1:
-        P1 = replace_weights(P, torch.sign(P.W1))
-        z1 = forward_math(P1)[0]["z1"]
-    assert float(z1.abs().max()) < (LOW_ONES + 16) * LOW_W and torch.equal(z1.float().double(), z1), "the probe's z1 must be an exact fp32 value"
-    return to_bf16(z1) if P.case.sbf else z1
-
-
-def replace_weights(P, W1):
-    Q = type(P)(**vars(P))
-    Q.W1 = W1
-    return Q
-
-
-def standin_run(case, kind, defect=None, ns_claimed=0):
-    """The MLP in torch fp32 on the CPU (bf16 rounding where the case stores bf16) with an optional defect, compared like a kernel ->
-    names of the failing quantities, forward first."""
-    P = int_problem(case, 7) if kind == "int" else rand_problem(case, 7) if kind == "rand" else build_problem(case, 7, kind)
-    ref_f, bud_f = forward_math(P, ns=ns_claimed)
-    got_f, _ = forward_math(P, torch.float32, defect=defect)
-    if kind == "low":
-        return [] if torch.equal(got_f["z1"].double(), low_reference(P, ns_claimed)) else ["z1"]
-    saved = {k: got_f[k] for k in ("z1", "xhat", "rstd") if k in got_f}
-    ref_b, bud_b = backward_math(P, {k: v.double() for k, v in saved.items()}, ns=ns_claimed, nblk=STANDIN_NBLK)
-    got_b, _ = backward_math(P, saved, torch.float32, defect=defect)
-    c = case
-    go = P.g_out[:, P.out_idx] if P.out_idx is not None else P.g_out
-    dm = (go + (P.g_aggr * P.scale[None, :, None])[:, P.seg_of_row]).float()
-    # the four vectors as a kernel leaves them: per-workgroup partial sums of what it holds in fp32, summed in float64
-    unrounded = got_b if not c.sbf else backward_math(replace_case(P, sbf=False), saved, torch.float32, defect=defect)[0]
-    rows ={"db1": unrounded["dz1"], "db2": unrounded["dz2"]}
-    if c.ln:
-        rows.update(dgamma=dm * saved["xhat"], dbeta=dm)
-    got_b.update(block_vectors(P, rows, STANDIN_NBLK, skip=1 if defect == "skip_vec_partials_block" else None))
-    if kind == "int":
-        return (compare_exact(got_f, exact_reference(c, ref_f, True), exact_quantities(c, True))
-                + compare_exact(got_b, ref_b, exact_quantities(c, False)))
-    return compare_bounded(got_f, ref_f, bud_f) + compare_bounded(got_b, ref_b, bud_b)
-
-
-def replace_case(P, **kw):
-    Q = type(P)(**vars(P))
-    Q.case = replace(P.case, **kw)
-    return Q
 
 
 @pytest.mark.parametrize("case", [STANDIN_512, STANDIN_1536], ids=str)
