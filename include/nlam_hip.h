@@ -538,7 +538,16 @@ int32_t nlam_wgrad(const nlam_wgrad_t* p, void* hip_stream);
  * the split-bf16 wide family with fp32 operands; NLAM_EUNSUP otherwise (launch them one by one). */
 int32_t nlam_wgrad_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream);
 
-/* out[b, s, :] = scale(s) * sum_{q in [ptr[s], ptr[s+1])} in[b, order[q], :]   (order NULL = q) */
+/* out[b, s, :] = scale(s) * sum_{q in [ptr[s], ptr[s+1])} in[b, order[q], :]   (order NULL = q, scale NULL = 1; `order` may name a
+ * row more than once; an empty segment is written as zeros).  Which of the three fp32 kernels runs -- it decides the summation
+ * order, not the contract -- is what nlam_segment_sum_groups answers: the lane groups that share a segment.  With
+ * rows = in_bstride / width (0 when in_bstride is 0: a shared input's row count is not known),
+ *   width % 4 == 0, width / 4 a divisor of 64 of at most 32 (width 4, 8, 16, 32, 64 or 128) and rows >= 16 * nseg (segments of
+ *   16+ rows on average): segment_sum_split_kernel<S>, S = 4 lane groups for width <= 64, S = 2 for width 128 -- group g sums rows
+ *   g, g + S, ... of the segment, eight in flight, and the groups are combined in a fixed order;
+ *   everything else: 1 = segment_sum_kernel, one thread per (segment, 4 columns), 16-byte accesses when width % 4 == 0.
+ * nlam_segment_sum, _acc and _add take the same kernel for the same (in_bstride, nseg, width).  NLAM_EINVAL for width < 1 or nseg < 0. */
+int32_t nlam_segment_sum_groups(int64_t in_bstride, int32_t nseg, int32_t width);
 int32_t nlam_segment_sum(const float* in, int64_t in_bstride, const int32_t* ptr, const int32_t* order,
                          const float* scale, float* out, int32_t nseg, int32_t width, int32_t batch,
                          void* hip_stream);
@@ -600,8 +609,9 @@ int32_t nlam_reduce_jobs_waves(void);
 /* Node-level product of the factorised edge MLP (NLAM_F_PRE_ADD) and its data gradient:
  *   out[r][h] (+)= sum_c x[r][c] * W[h * ldn + c * ldk],   r < rows, h < n, c < k
  * (forward: W = W1 + column offset, ldn = row stride of W1, ldk = 1; backward: the transposed product with
- * ldn = 1, ldk = row stride of W1).  x (rows, k) and out (rows, n) are contiguous; k, n in {32, 64, 128};
- * matrix mode from flags (NLAM_F_MM_BF16X1..3; the fp32-MFMA mode is not instantiated: NLAM_EUNSUP). */
+ * ldn = 1, ldk = row stride of W1).  x (rows, k) and out (rows, n) are contiguous and 16-byte aligned; k, n multiples of 32 up to
+ * 64, or multiples of 64 (n % 128 == 0: k a multiple of 32) up to nlam_max_width(), see nlam_linear_plan; rows of out past
+ * `rows` are not written; matrix mode from flags (NLAM_F_MM_BF16X1..3; the fp32-MFMA mode is not instantiated: NLAM_EUNSUP). */
 typedef struct {
     const float* x;
     const float* W;
@@ -617,6 +627,44 @@ typedef struct {
     float* out2;           /* strides (the sender- and the receiver-side product of a layer whose senders are its receivers)   */
 } nlam_linear_t;
 int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream);
+/* Which kernel instantiation nlam_linear launches for *p under the current tuning (nlam_set_tuning), host logic, no launch -- or the
+ * NLAM_EINVAL / NLAM_EUNSUP the launch would return.  nlam_linear switches on this code, so the two cannot disagree.  rows == 0
+ * gives NLAM_LINP_EMPTY (the launch returns 0 and writes nothing).  Otherwise the code is a bit field:
+ *   NLAM_LINP_KERNEL(c)  NLAM_LINP_BF    linear_bf_kernel<KB, MB, NS>: k, n <= 64, W staged once per persistent workgroup, one wave =
+ *                                        one 32-row tile, any ldn / ldk and any 4-byte alignment of W
+ *                        NLAM_LINP_BFW   linear_bfw_kernel<NS>: k, n multiples of 64 up to nlam_max_width(), 64 x 64 weight blocks,
+ *                                        any ldn / ldk and any 4-byte alignment of W (the strip kernel)
+ *                        NLAM_LINP_GEMM  linear_gemm_kernel<NS, WN, TA, SK>: n % 128 == 0, k % 32 == 0, both up to nlam_max_width(),
+ *                                        and a layout it can read: ldk == 1 with ldn % 4 == 0 and W (and W2) 16-byte aligned, or
+ *                                        ldn == 1 (NLAM_LINP_TA); taken where NLAM_TUNE_LIN_GEMM says so.  A shape only this
+ *                                        kernel serves (k % 64 != 0) in a layout it cannot read is NLAM_EUNSUP
+ *   NLAM_LINP_NS(c)      bf16 terms per operand the kernel EXECUTES: always the 1, 2 or 3 that flags request
+ *   NLAM_LINP_KB(c), NLAM_LINP_MB(c)   NLAM_LINP_BF only: k / 32 and n / 32, 1 or 2
+ *   NLAM_LINP_RESIDENT   NLAM_LINP_BFW only: k <= 256 and NLAM_TUNE_LIN_WGS > 0 -- an output pair's whole weight strip stays in LDS and
+ *                        at most NLAM_TUNE_LIN_WGS workgroups walk rounds of eight 32-row tiles; otherwise the strip is streamed
+ *                        through two LDS buffers
+ *   NLAM_LINP_WN(c)      NLAM_LINP_GEMM only: 2 = 128-row tiles (rows >= the threshold of NLAM_TUNE_LIN_GEMM, default 32 768), 1 = 64-row
+ *                        tiles.  Row tiles are padded to a multiple of eight; the workgroups of the padding return at once
+ *   NLAM_LINP_SK(c)      NLAM_LINP_GEMM only: K = 16 steps per staged chunk, 4 (one term, 64-row tiles, k % 64 == 0) or 2
+ *   NLAM_LINP_TA         NLAM_LINP_GEMM only: the transposed layout (ldn == 1)
+ *   NLAM_LINP_DUAL       the launch also computes out2 from W2 (NLAM_LINP_BFW and NLAM_LINP_GEMM) */
+#define NLAM_LINP_BF           1
+#define NLAM_LINP_BFW          2
+#define NLAM_LINP_GEMM         3
+#define NLAM_LINP_KERNEL(c)    ((c) & 3)
+#define NLAM_LINP_NS(c)        (((c) >> 2) & 3)
+#define NLAM_LINP_KB(c)        (((c) >> 4) & 3)
+#define NLAM_LINP_MB(c)        (((c) >> 6) & 3)
+#define NLAM_LINP_RESIDENT     (1 << 8)
+#define NLAM_LINP_WN(c)        (((c) >> 9) & 3)
+#define NLAM_LINP_SK(c)        (((c) >> 11) & 7)
+#define NLAM_LINP_TA           (1 << 14)
+#define NLAM_LINP_DUAL         (1 << 15)
+#define NLAM_LINP_EMPTY        (1 << 16)
+#define NLAM_LINP_CODE(kernel, ns)     ((kernel) | ((ns) << 2))
+#define NLAM_LINP_BF_SHAPE(kb, mb)     (((kb) << 4) | ((mb) << 6))
+#define NLAM_LINP_GEMM_SHAPE(wn, sk)   (((wn) << 9) | ((sk) << 11))
+int32_t nlam_linear_plan(const nlam_linear_t* p);
 /* 1 when nlam_mlp_fwd / nlam_mlp_bwd / nlam_linear have a factorised (NLAM_F_PRE_ADD) kernel for this problem, else 0
  * (only nsrc, the source widths, hid, dout, flags, ntiles and batch of *p are read) */
 int32_t nlam_pre_add_supported(const nlam_mlp_fwd_t* p);

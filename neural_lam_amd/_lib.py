@@ -71,6 +71,26 @@ def mlpw_fields(code):
     return code & 3, (code >> 2) & 3, (code >> 4) & 7, (code >> 7) & 15, (code >> 11) & 3, code & (MLPW_V4 | MLPW_SBF | MLPW_EMPTY)
 
 
+# nlam_linear_plan codes (include/nlam_hip.h, NLAM_LINP_*): the instantiation an nlam_linear launch runs
+LINP_BF, LINP_BFW, LINP_GEMM = 1, 2, 3
+LINP_RESIDENT, LINP_TA, LINP_DUAL, LINP_EMPTY = 1 << 8, 1 << 14, 1 << 15, 1 << 16
+
+
+def linp_bf(ns, kb, mb):
+    """linear_bf_kernel<KB, MB, NS>"""
+    return LINP_BF | (ns << 2) | (kb << 4) | (mb << 6)
+
+
+def linp_bfw(ns, resident, dual=False):
+    """linear_bfw_kernel<NS>, resident or streamed weight strip"""
+    return LINP_BFW | (ns << 2) | (LINP_RESIDENT if resident else 0) | (LINP_DUAL if dual else 0)
+
+
+def linp_gemm(ns, wn, sk, ta=False, dual=False):
+    """linear_gemm_kernel<NS, WN, TA, SK>"""
+    return LINP_GEMM | (ns << 2) | (wn << 9) | (sk << 11) | (LINP_TA if ta else 0) | (LINP_DUAL if dual else 0)
+
+
 TILE_SPLIT = 1 << 30
 # training-loss kinds (NLAM_LOSS_*), keyed by the reference's metric names (metrics.DEFINED_METRICS)
 LOSS_KINDS = {"mse": 1, "mae": 2, "wmse": 3, "wmae": 4, "nll": 5, "crps_gauss": 6}
@@ -142,6 +162,8 @@ EXPORTS = [
     "nlam_mlp_bwd_group_blocks",
     "nlam_wgrad_group",
     "nlam_linear",
+    "nlam_linear_plan",
+    "nlam_segment_sum_groups",
     "nlam_pre_add_supported",
     "nlam_step_tail_fwd",
     "nlam_step_tail_bwd",
@@ -741,6 +763,10 @@ def load():
     lib.nlam_pre_add_supported.restype = i32
     lib.nlam_linear.argtypes = [C.POINTER(Linear), vp]
     lib.nlam_linear.restype = i32
+    lib.nlam_linear_plan.argtypes = [C.POINTER(Linear)]
+    lib.nlam_linear_plan.restype = i32
+    lib.nlam_segment_sum_groups.argtypes = [i64, i32, i32]
+    lib.nlam_segment_sum_groups.restype = i32
     lib.nlam_standardize.argtypes = [C.POINTER(StdJobs), vp]
     lib.nlam_standardize.restype = i32
     if lib.nlam_abi_version() != ABI_VERSION:

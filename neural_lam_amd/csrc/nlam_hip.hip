@@ -6852,28 +6852,18 @@ int32_t launch_lin_gemm(bool ta, dim3 grid, hipStream_t stream, const nlam_linea
 
 extern "C" {
 
-int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
-    NLAM_RANGE("nlam_linear");
+// which instantiation nlam_linear launches (the code nlam_linear_plan answers with), or the error the launch returns
+int32_t nlam_linear_plan(const nlam_linear_t* p) {
     if (p == nullptr || p->x == nullptr || p->W == nullptr || p->out == nullptr || p->rows < 0 || p->k < 1 || p->n < 1) return NLAM_EINVAL;
-    if (p->rows == 0) return 0;
+    if (p->rows == 0) return NLAM_LINP_EMPTY;
     const int ns = (int)((p->flags & NLAM_F_MM_MASK) >> NLAM_F_MM_SHIFT);
     if (ns == 0 || p->k % 32 != 0 || p->n % 32 != 0) return NLAM_EUNSUP;
     if (((reinterpret_cast<uintptr_t>(p->x) | reinterpret_cast<uintptr_t>(p->out)) & 15) != 0) return NLAM_EINVAL;
     if ((p->W2 == nullptr) != (p->out2 == nullptr)) return NLAM_EINVAL;
     if (p->W2 != nullptr && (p->k <= 64 && p->n <= 64)) return NLAM_EUNSUP;   // the dual form exists for the wide kernel only
+    const int dual = p->W2 != nullptr ? NLAM_LINP_DUAL : 0;
     const int KB = p->k / 32, MB = p->n / 32;
-    const long ntiles = (p->rows + 31) / 32;
-    const int blocks = (int)(ntiles < kMaxGridBlocks ? ntiles : kMaxGridBlocks);
-    const size_t lds = (size_t)ns * MB * 2 * KB * 64 * 16 + (size_t)kFwdWaves * 32 * kStgStride * sizeof(float);
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (KB <= 2 && MB <= 2)
-        return pick<1, 2>(KB, [&](auto kb) {
-            return pick<1, 2>(MB, [&](auto mb) {
-                return pick_else<1, 3, 2>(ns, [&](auto nsc) {
-                    return launch<linear_bf_kernel<kb, mb, nsc>>(dim3(blocks), dim3(kFwdThreads), lds, stream, *p);
-                });
-            });
-        });
+    if (KB <= 2 && MB <= 2) return NLAM_LINP_CODE(NLAM_LINP_BF, ns) | NLAM_LINP_BF_SHAPE(KB, MB);
     if (nlam_detail::lin_gemm != 0 && p->n % 128 == 0 && p->k <= kMaxWide && p->n <= kMaxWide && lin_gemm_layout(p) != 0 &&
         // where it wins (profiles/round5/linear_bench.log, isolated launches): one term everywhere (1.3-2.1x); two / three terms
         // -- 114 KB of LDS, one workgroup per CU -- on the mesh-level products up to K = 256 (1.4-1.5x) and on the grid-level
@@ -6881,24 +6871,60 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
         // nlam_set_tuning(NLAM_TUNE_LIN_GEMM, 2) forces it everywhere it applies (tests).
         (ns == 1 || nlam_detail::lin_gemm == 2 || (p->rows >= nlam_detail::lin_gemm_big_rows ? p->k >= 512 : p->k <= 256))) {
         // LDS-tiled GEMM (linear_gemm_kernel): 128 x 128 tiles from 32 768 rows, 64-row tiles below
-        const bool ta = lin_gemm_layout(p) == 2;
+        const int ta = lin_gemm_layout(p) == 2 ? NLAM_LINP_TA : 0;
         const bool big = p->rows >= nlam_detail::lin_gemm_big_rows;
         const long bm = big ? 128 : 64;
         const long nrt = (p->rows + bm - 1) / bm;
         const long nftt = (long)(p->n / 128) * (p->W2 != nullptr ? 2 : 1);
-        const long nwg = (nrt + 7) / 8 * 8 * nftt;
-        if (nwg > 0x7fffffffL) return NLAM_EUNSUP;
-        const dim3 grid((unsigned)nwg);
-        if (big) return pick_else<1, 3, 2>(ns, [&](auto nsc) { return launch_lin_gemm<nsc, 2, 2>(ta, grid, stream, *p); });
-        if (ns == 3 || ns == 2) return pick<3, 2>(ns, [&](auto nsc) { return launch_lin_gemm<nsc, 1, 2>(ta, grid, stream, *p); });
+        if ((nrt + 7) / 8 * 8 * nftt > 0x7fffffffL) return NLAM_EUNSUP;
         // one term, 64-row tiles: 64-column chunks (66 KB of LDS, two workgroups per CU)
-        if (p->k % 64 == 0 && NLAM_LIN_SK == 4) return launch_lin_gemm<1, 1, 4>(ta, grid, stream, *p);
-        return launch_lin_gemm<1, 1, 2>(ta, grid, stream, *p);
+        const int sk = (!big && ns == 1 && p->k % 64 == 0 && NLAM_LIN_SK == 4) ? 4 : 2;
+        return NLAM_LINP_CODE(NLAM_LINP_GEMM, ns) | NLAM_LINP_GEMM_SHAPE(big ? 2 : 1, sk) | ta | dual;
     }
     if (p->k % 64 == 0 && p->n % 64 == 0 && p->k <= kMaxWide && p->n <= kMaxWide) {
-        // 64 x 64 weight blocks streamed through two LDS buffers (linear_bfw_kernel)
+        // 64 x 64 weight blocks streamed through two LDS buffers (linear_bfw_kernel), or the output pair's whole weight strip in LDS
+        const bool resident = p->k / 64 <= kLinResidentChunks && nlam_detail::lin_resident_wgs > 0;
+        return NLAM_LINP_CODE(NLAM_LINP_BFW, ns) | (resident ? NLAM_LINP_RESIDENT : 0) | dual;
+    }
+    return NLAM_EUNSUP;
+}
+
+int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_linear");
+    const int plan = nlam_linear_plan(p);   // the instantiation; only the launch shapes are decided here
+    if (plan < 0) return plan;
+    if (plan & NLAM_LINP_EMPTY) return 0;
+    const int ns = NLAM_LINP_NS(plan);
+    const long ntiles = (p->rows + 31) / 32;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    switch (NLAM_LINP_KERNEL(plan)) {
+    case NLAM_LINP_BF: {
+        const int KB = NLAM_LINP_KB(plan), MB = NLAM_LINP_MB(plan);
+        const int blocks = (int)(ntiles < kMaxGridBlocks ? ntiles : kMaxGridBlocks);
+        const size_t lds = (size_t)ns * MB * 2 * KB * 64 * 16 + (size_t)kFwdWaves * 32 * kStgStride * sizeof(float);
+        return pick<1, 2>(KB, [&](auto kb) {
+            return pick<1, 2>(MB, [&](auto mb) {
+                return pick_else<1, 3, 2>(ns, [&](auto nsc) {
+                    return launch<linear_bf_kernel<kb, mb, nsc>>(dim3(blocks), dim3(kFwdThreads), lds, stream, *p);
+                });
+            });
+        });
+    }
+    case NLAM_LINP_GEMM: {
+        const bool ta = (plan & NLAM_LINP_TA) != 0;
+        const bool big = NLAM_LINP_WN(plan) == 2;
+        const long bm = big ? 128 : 64;
+        const long nrt = (p->rows + bm - 1) / bm;
+        const long nftt = (long)(p->n / 128) * (p->W2 != nullptr ? 2 : 1);
+        const dim3 grid((unsigned)((nrt + 7) / 8 * 8 * nftt));
+        if (big) return pick_else<1, 3, 2>(ns, [&](auto nsc) { return launch_lin_gemm<nsc, 2, 2>(ta, grid, stream, *p); });
+        if (ns == 3 || ns == 2) return pick<3, 2>(ns, [&](auto nsc) { return launch_lin_gemm<nsc, 1, 2>(ta, grid, stream, *p); });
+        if (NLAM_LINP_SK(plan) == 4) return launch_lin_gemm<1, 1, 4>(ta, grid, stream, *p);
+        return launch_lin_gemm<1, 1, 2>(ta, grid, stream, *p);
+    }
+    case NLAM_LINP_BFW: {
         const int kc_all = p->k / 64;
-        const bool resident = kc_all <= kLinResidentChunks && nlam_detail::lin_resident_wgs > 0;   // the output pair's whole weight strip stays in LDS
+        const bool resident = (plan & NLAM_LINP_RESIDENT) != 0;   // the output pair's whole weight strip stays in LDS
         nlam_linear_t q = *p;
         q.flags = (q.flags & ~kLinResidentFlag) | (resident ? kLinResidentFlag : 0u);
         const size_t wlds = (size_t)(resident ? kc_all : 2) * ns * 2 * 4 * 64 * 16 + (size_t)kFwdWaves * 32 * kStgStride * sizeof(float);
@@ -6912,7 +6938,8 @@ int32_t nlam_linear(const nlam_linear_t* p, void* hip_stream) {
             return launch<linear_bfw_kernel<nsc>>(dim3(wbx, wby), dim3(kFwdThreads), wlds, stream, q);
         });
     }
-    return NLAM_EUNSUP;
+    default: return NLAM_EUNSUP;
+    }
 }
 
 }  // extern "C"
@@ -7187,28 +7214,35 @@ __global__ void segment_sum_bf16_kernel(const unsigned short* in, long in_bstrid
     }
 }
 
+// lane groups per segment: segments of 16+ rows on average (known when the input has its own batch stride) are shared by
+// several groups of width / 4 lanes (segment_sum_split_kernel<S>), everything else is one thread per (segment, float4 column)
+int32_t nlam_segment_sum_groups(int64_t in_bstride, int32_t nseg, int32_t width) {
+    if (width < 1 || nseg < 0) return NLAM_EINVAL;
+    const int w4 = width / 4;
+    const long rows = in_bstride > 0 ? in_bstride / width : 0;
+    if ((width & 3) == 0 && w4 <= 32 && 64 % w4 == 0 && rows >= 16L * nseg) return w4 <= 16 ? 4 : 2;
+    return 1;
+}
+
 static int32_t segment_sum_launch(const float* in, int64_t in_bstride, const int32_t* ptr, const int32_t* order, const float* scale,
                                   float* out, int32_t nseg, int32_t width, int32_t batch, int accumulate, void* hip_stream,
                                   const float* extra = nullptr) {
     if (in == nullptr || ptr == nullptr || out == nullptr || nseg < 0 || width < 1 || batch < 1) return NLAM_EINVAL;
     if (nseg == 0) return 0;
-    // segments of 16+ rows on average (known when the input has its own batch stride): several lane groups per segment
     const int w4 = width / 4;
-    const long rows = in_bstride > 0 ? in_bstride / width : 0;
-    if ((width & 3) == 0 && w4 <= 32 && 64 % w4 == 0 && rows >= 16L * nseg) {
-        const int S = w4 <= 16 ? 4 : 2;
-        const int blk = elementwise_blocks((long)batch * nseg * S * w4, 256 * 16);
-        if (S == 4)
-            hipLaunchKernelGGL(segment_sum_split_kernel<4>, dim3(blk), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
-                               order, scale, out, nseg, width, batch, accumulate, extra);
-        else
-            hipLaunchKernelGGL(segment_sum_split_kernel<2>, dim3(blk), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride, ptr,
-                               order, scale, out, nseg, width, batch, accumulate, extra);
-        return (int32_t)hipGetLastError();
+    switch (nlam_segment_sum_groups(in_bstride, nseg, width)) {
+    case 4:
+        hipLaunchKernelGGL(segment_sum_split_kernel<4>, dim3(elementwise_blocks((long)batch * nseg * 4 * w4, 256 * 16)), dim3(256), 0,
+                           (hipStream_t)hip_stream, in, (long)in_bstride, ptr, order, scale, out, nseg, width, batch, accumulate, extra);
+        break;
+    case 2:
+        hipLaunchKernelGGL(segment_sum_split_kernel<2>, dim3(elementwise_blocks((long)batch * nseg * 2 * w4, 256 * 16)), dim3(256), 0,
+                           (hipStream_t)hip_stream, in, (long)in_bstride, ptr, order, scale, out, nseg, width, batch, accumulate, extra);
+        break;
+    default:
+        hipLaunchKernelGGL(segment_sum_kernel, dim3(elementwise_blocks((long)batch * nseg * ((width + 3) / 4), 256 * 16)), dim3(256), 0,
+                           (hipStream_t)hip_stream, in, (long)in_bstride, ptr, order, scale, out, nseg, width, batch, accumulate, extra);
     }
-    const int blocks = elementwise_blocks((long)batch * nseg * ((width + 3) / 4), 256 * 16);
-    hipLaunchKernelGGL(segment_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, in, (long)in_bstride,
-                       ptr, order, scale, out, nseg, width, batch, accumulate, extra);
     return (int32_t)hipGetLastError();
 }
 
