@@ -51,6 +51,10 @@
  *   nlam_eval_metrics, nlam_eval_workspace_floats
  *       the evaluation tensors of validation_step / test_step (models/module.py:546-576, :607-681): per-step loss,
  *       per-variable masked MSE / MAE / mean std, per-node loss maps; one pass over the rollout + a fixed-order reduction.
+ *   nlam_forecast_init, nlam_forecast_head, nlam_forecast_tail, nlam_forecast_finish, nlam_forecast_workspace_floats
+ *       a forecast of any length as replays of ONE recorded AR step: a lead counter in device memory ties the data path
+ *       (this lead's forcing window and boundary truth, cut from the resident series) to the inference step tail, which
+ *       rotates the state in place and writes this lead's physical fields, valid time and verification sums.
  *   nlam_window_moments, nlam_moments_workspace_doubles
  *       the per-sample means and second moments of npyfilesmeps/compute_standardization_stats.py (values and
  *       standardized one-step differences), read in place from the resident series of the data path.
@@ -928,6 +932,75 @@ typedef struct {
 int64_t nlam_window_len(int64_t n_state_times, int64_t n_forcing_times, int32_t ar_steps, int32_t num_past_forcing_steps,
                         int32_t num_future_forcing_steps);
 int32_t nlam_window_batch(const nlam_window_t* p, void* hip_stream);
+
+/* A forecast to any lead time as replays of ONE recorded AR step (neural_lam_amd/forecast.py).  A captured launch cannot change its
+ * pointers between replays, so everything that depends on the lead time is addressed on the device through a counter:
+ *   start (batch) int64   the time index t0 of the LATEST initial state of each forecast
+ *   lead  (1)     int32   k, the number of lead times already produced
+ * Lead k + 1 is valid at time index t0 + k + 1: its forcing window reads times t0 + k + 1 - past .. t0 + k + 1 + future
+ * (feature-major / window-minor, forcing_windowed[b][n][f * window + w], as nlam_window_batch), its boundary truth is the state
+ * at t0 + k + 1.  Time indices are clamped into [0, n_times) instead of faulting, as in nlam_window_batch.  The series are those of
+ * nlam_window_t; the state statistics are required (the outputs are de-standardised with them), the forcing pair with d_forcing > 0.
+ *   nlam_forecast_init    prev_prev = standardised state at t0 - 1, prev = at t0 (both (batch, nodes, d_state)); *lead = 0.
+ *   nlam_forecast_head    reads *lead; writes this lead's standardised forcing_windowed (batch, nodes, d_forcing * window) and
+ *                         truth (batch, nodes, d_state): (x - mean) / std, IEEE sub + div -- the bits of nlam_window_batch.
+ *   nlam_forecast_tail    reads *lead; one pass per element over the network output delta (batch * nodes, delta_ld), delta_ld =
+ *                         d_state or 2 * d_state with a std head, with dstd / dmean / bmask / clamp_* as in nlam_step_tail_t:
+ *                           new = the pred of nlam_step_tail_ext_fwd(target = NULL) on (delta, prev, truth): the same device
+ *                                 function, the same bits
+ *                           prev_prev[e] = prev[e];  prev[e] = new                       the state rotates in place
+ *                           out_state[b][k][n][f] = new * state_std[f] + state_mean[f]   physical units
+ *                           out_std[b][k][n][f]   = softplus(raw) * state_std[f]         with a std head
+ *                           valid_times[b][k]     = times[t0 + k + 1], or that (clamped) index when times == NULL
+ *                           sq / ab given: per-workgroup partial sums of row_weight[n] * (new - truth)^2 and
+ *                                 row_weight[n] * |new - truth| into workspace (standardised units: the sq / ab of nlam_eval_metrics)
+ *                         If *lead >= max_lead the kernel writes nothing at all.
+ *   nlam_forecast_finish  one small launch, always: adds the partials in a fixed order into sq[b][k][f] / ab[b][k][f] (bit-identical
+ *                         run to run), then increments *lead (not beyond max_lead).  One thread reads the counter and writes it; no
+ *                         other launch writes it (nlam_forecast_init aside, which does not read it).
+ * No allocation, no host synchronisation.  clamp_mode_host is HOST memory, read during the call.  NLAM_EINVAL (before any launch)
+ * for null required pointers, sizes < 1, delta_ld not in {d_state, 2 * d_state}, out_std given exactly when there is no std head,
+ * a short workspace; NLAM_EUNSUP for d_state > NLAM_LOSS_MAX_VARS, with sq / ab for d_state > NLAM_EVAL_MAX_VARS, and for a
+ * (nodes x row) block of 2^31 floats or more. */
+typedef struct {
+    const float* state;          /* (n_times, nodes, d_state) */
+    const float* forcing;        /* (n_times, nodes, d_forcing) or NULL when d_forcing == 0 */
+    const int64_t* times;        /* (n_times) time stamps (ns) or NULL */
+    const int64_t* start;        /* device (batch): t0 */
+    int32_t* lead;               /* device (1): k */
+    const float* state_mean;     /* (d_state) */
+    const float* state_std;      /* (d_state) */
+    const float* forcing_mean;   /* (d_forcing), required when d_forcing > 0 */
+    const float* forcing_std;    /* (d_forcing) */
+    float* prev;                 /* (batch, nodes, d_state) standardised state at the latest lead: init writes, tail rotates */
+    float* prev_prev;            /* (batch, nodes, d_state) the one before */
+    float* forcing_windowed;     /* head: (batch, nodes, d_forcing * window), or NULL when d_forcing == 0 */
+    float* truth;                /* head writes, tail reads: (batch, nodes, d_state) */
+    const float* delta;          /* tail: (batch * nodes, delta_ld) the network output */
+    const float* dstd;           /* tail: (d_state) or NULL (1) */
+    const float* dmean;          /* tail: (d_state) or NULL (0) */
+    const float* bmask;          /* tail: (nodes) */
+    const float* row_weight;     /* tail: (nodes) interior mask / #interior nodes, read with sq / ab */
+    const int32_t* clamp_mode_host;   /* tail: HOST (d_state) NLAM_CLAMP_*, or NULL: none */
+    const float* clamp_lo;       /* (d_state) */
+    const float* clamp_hi;       /* (d_state) */
+    float* out_state;            /* tail: (batch, max_lead, nodes, d_state) physical units */
+    float* out_std;              /* tail: (batch, max_lead, nodes, d_state); non-NULL exactly when delta_ld == 2 * d_state */
+    int64_t* valid_times;        /* tail: (batch, max_lead) or NULL */
+    float* sq;                   /* tail + finish: (batch, max_lead, d_state) or NULL */
+    float* ab;                   /* tail + finish: (batch, max_lead, d_state) or NULL */
+    float* workspace;            /* tail + finish, with sq / ab: nlam_forecast_workspace_floats(batch, nodes, d_state) floats */
+    int64_t workspace_floats;
+    int64_t n_times;
+    int32_t nodes, d_state, d_forcing, batch;
+    int32_t max_lead, num_past_forcing_steps, num_future_forcing_steps, delta_ld;
+} nlam_forecast_t;
+int32_t nlam_forecast_init(const nlam_forecast_t* p, void* hip_stream);
+int32_t nlam_forecast_head(const nlam_forecast_t* p, void* hip_stream);
+int32_t nlam_forecast_tail(const nlam_forecast_t* p, void* hip_stream);
+int32_t nlam_forecast_finish(const nlam_forecast_t* p, void* hip_stream);
+/* floats of nlam_forecast_t.workspace for these sizes; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP for nvars > NLAM_EVAL_MAX_VARS */
+int64_t nlam_forecast_workspace_floats(int32_t batch, int32_t nodes, int32_t nvars);
 
 /* The same batch launch over STRIDED series: forecast-type and ensemble datastores (weather_dataset.py:135-200, :235-254,
  * :303-342, :399-418).  Element (sample s, member m, step j) of a series -- one contiguous (nodes x d) block -- sits at

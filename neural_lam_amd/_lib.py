@@ -189,6 +189,11 @@ EXPORTS = [
     "nlam_adamw_step_resident_ema",
     "nlam_adamw_step_controlled_ema",
     "nlam_flat_swap",
+    "nlam_forecast_init",
+    "nlam_forecast_head",
+    "nlam_forecast_tail",
+    "nlam_forecast_finish",
+    "nlam_forecast_workspace_floats",
 ]
 
 
@@ -371,6 +376,49 @@ class Window(C.Structure):
         ("num_past_forcing_steps", C.c_int32),
         ("num_future_forcing_steps", C.c_int32),
         ("_pad", C.c_int32),
+    ]
+
+
+class Forecast(C.Structure):
+    """nlam_forecast_t: one recorded AR step replayed per lead time; ``clamp_mode_host`` points at HOST memory."""
+    _fields_ = [
+        ("state", C.c_void_p),
+        ("forcing", C.c_void_p),
+        ("times", C.c_void_p),
+        ("start", C.c_void_p),
+        ("lead", C.c_void_p),
+        ("state_mean", C.c_void_p),
+        ("state_std", C.c_void_p),
+        ("forcing_mean", C.c_void_p),
+        ("forcing_std", C.c_void_p),
+        ("prev", C.c_void_p),
+        ("prev_prev", C.c_void_p),
+        ("forcing_windowed", C.c_void_p),
+        ("truth", C.c_void_p),
+        ("delta", C.c_void_p),
+        ("dstd", C.c_void_p),
+        ("dmean", C.c_void_p),
+        ("bmask", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("clamp_mode_host", C.c_void_p),
+        ("clamp_lo", C.c_void_p),
+        ("clamp_hi", C.c_void_p),
+        ("out_state", C.c_void_p),
+        ("out_std", C.c_void_p),
+        ("valid_times", C.c_void_p),
+        ("sq", C.c_void_p),
+        ("ab", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("n_times", C.c_int64),
+        ("nodes", C.c_int32),
+        ("d_state", C.c_int32),
+        ("d_forcing", C.c_int32),
+        ("batch", C.c_int32),
+        ("max_lead", C.c_int32),
+        ("num_past_forcing_steps", C.c_int32),
+        ("num_future_forcing_steps", C.c_int32),
+        ("delta_ld", C.c_int32),
     ]
 
 
@@ -725,6 +773,11 @@ def load():
     lib.nlam_window_batch.restype = i32
     lib.nlam_window_batch_ens.argtypes = [C.POINTER(WindowEns), vp]
     lib.nlam_window_batch_ens.restype = i32
+    for entry in (lib.nlam_forecast_init, lib.nlam_forecast_head, lib.nlam_forecast_tail, lib.nlam_forecast_finish):
+        entry.argtypes = [C.POINTER(Forecast), vp]
+        entry.restype = i32
+    lib.nlam_forecast_workspace_floats.argtypes = [i32, i32, i32]
+    lib.nlam_forecast_workspace_floats.restype = i64
     lib.nlam_window_moments.argtypes = [C.POINTER(Moments), vp]
     lib.nlam_window_moments.restype = i32
     lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]

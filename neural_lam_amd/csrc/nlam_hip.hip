@@ -3823,6 +3823,24 @@ struct StepTailTables {
     static size_t lds_bytes(int width) { return (size_t)width * (3 * sizeof(float2) + sizeof(int)); }
 };
 
+// the prediction of one element: the rescaled delta, the (clamped) new state, the boundary mix.  One function for the training /
+// evaluation tail below and the forecast tail (nlam_forecast.inc), so that both give the same bits.
+template <bool HAS_CLAMP, typename TAB>
+__device__ __forceinline__ float step_tail_pred(const TAB& tab, float dl, float pr, float tr, float bm, int f) {
+    const float2 af = tab.aff[f];
+    const float r = dl * af.x + af.y;
+    float nw = pr + r;
+    if constexpr (HAS_CLAMP) {
+        const int m = tab.mode[f];
+        if (m != NLAM_CLAMP_NONE) {
+            float dr, dp;
+            const float2 l = tab.lim[f];
+            nw = clamped_new(m, pr, r, l.x, l.y, dr, dp);
+        }
+    }
+    return bm * tr + (1.f - bm) * nw;
+}
+
 template <int KIND, bool HAS_CLAMP, bool HAS_STD>
 __global__ __launch_bounds__(256) void step_tail_ext_fwd_kernel(const StepTailExtArgs a) {
     const StepTailTables<KIND, HAS_CLAMP, HAS_STD> tab(a);
@@ -3836,19 +3854,7 @@ __global__ __launch_bounds__(256) void step_tail_ext_fwd_kernel(const StepTailEx
     const float* __restrict__ row_weight = p.row_weight;
     // one element: the prediction (and its std) out, this element's weighted loss entry back
     auto elem = [&](float dl, float raw, float pr, float tr, float tg, int f, int n, float& pv, float& sd) {
-        const float2 af = tab.aff[f];
-        const float r = dl * af.x + af.y;
-        float nw = pr + r;
-        if constexpr (HAS_CLAMP) {
-            const int m = tab.mode[f];
-            if (m != NLAM_CLAMP_NONE) {
-                float dr, dp;
-                const float2 l = tab.lim[f];
-                nw = clamped_new(m, pr, r, l.x, l.y, dr, dp);
-            }
-        }
-        const float bm = bmask[n];
-        pv = bm * tr + (1.f - bm) * nw;
+        pv = step_tail_pred<HAS_CLAMP>(tab, dl, pr, tr, bmask[n], f);
         sd = 0.f;
         if constexpr (HAS_STD) sd = softplus_fwd(raw);
         if (!has_loss) return 0.f;
@@ -7490,6 +7496,10 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 }
 
 }  // extern "C"
+#endif
+
+#if NLAM_IN_TU(1)
+#include "nlam_forecast.inc"   // beside the step-tail kernels: the forecast tail shares step_tail_pred and StepTailTables
 #endif
 
 #if NLAM_IN_TU(5)

@@ -1,0 +1,284 @@
+"""Forecast to any lead time by replaying ONE recorded AR step.
+
+``ARForecaster.forward`` under ``torch.no_grad()`` wants the forcing windows and boundary states of the whole horizon
+materialised, records every AR step again when it is captured, and returns standardised, stacked predictions.  ``Forecast``
+is the product form: the series stay where ``DeviceWeatherDataset`` keeps them, a lead counter in device memory ties the data
+path to the inference step tail (``nlam_forecast_head`` / ``_tail`` / ``_finish``, include/nlam_hip.h), and one recorded step
+
+    head -> predictor(prev, prev_prev, forcing, raw_delta=True) -> tail -> finish
+
+is replayed ``max_lead`` times.  The graph, the memory besides the output and the host work per lead do not depend on the
+horizon, and the horizon does not depend on the rollout length the model was trained with.
+
+    fc = Forecast(step, dataset, max_lead=240, batch_size=2, verify=True)
+    res = fc.run(starts)            # ForecastResult of device tensors, no host synchronisation
+    res.state                       # (B, L, N, F) physical units
+    res.rmse(step.state_std)        # (L, F) per-lead RMSE in physical units (verify=True)
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import _lib as L
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def plan_forecast(n_times, num_past_forcing_steps, num_future_forcing_steps, max_lead):
+    """``(off, n_starts)``: sample ``i`` has its initial states at times ``i + off - 2`` and ``i + off - 1`` (``off = max(2, past)``,
+    so ``t0 = i + off - 1``), and the ``n_starts`` valid samples are those whose last forcing window ends inside the series,
+    ``t0 + max_lead + future <= n_times - 1`` -- the arithmetic of ``nlam_window_len`` with ``ar_steps = max_lead``.  No GPU."""
+    n_times, past, fut, max_lead = int(n_times), int(num_past_forcing_steps), int(num_future_forcing_steps), int(max_lead)
+    if n_times < 1 or past < 0 or fut < 0 or max_lead < 1:
+        raise ValueError(f"plan_forecast: n_times {n_times} and max_lead {max_lead} must be >= 1, the forcing steps ({past}, {fut}) >= 0")
+    off = max(2, past)
+    return off, max(0, n_times - (off + max_lead + fut) + 1)
+
+
+def check_starts(starts, n_starts):
+    """Host sample indices as an int64 tensor, negative ones counted from the end; IndexError outside ``[0, n_starts)``."""
+    host = torch.as_tensor(starts, dtype=torch.int64).reshape(-1)
+    host = torch.where(host < 0, host + n_starts, host)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n_starts):
+        raise IndexError(f"forecast start out of range: {n_starts} valid starts for this series and horizon")
+    return host
+
+
+class ForecastResult(NamedTuple):
+    """Device tensors of one ``Forecast.run``: ``state`` (B, L, N, F) in physical units, ``std`` (B, L, N, F) the predicted std
+    in physical units or None, ``valid_times`` (B, L) int64 (time stamps, or time indices for a dataset without them), ``sq`` /
+    ``ab`` (B, L, F) the masked grid means of the squared / absolute error against the analysis in standardised units (the
+    ``sq`` / ``ab`` of ``nlam_eval_metrics``), or None without ``verify``."""
+    state: torch.Tensor
+    std: Optional[torch.Tensor]
+    valid_times: torch.Tensor
+    sq: Optional[torch.Tensor]
+    ab: Optional[torch.Tensor]
+
+    def rmse(self, state_std):
+        """(L, F) ``sqrt(mean_b sq) * state_std``: the rescaling of the reference's test epoch (models/module.py)."""
+        if self.sq is None:
+            raise ValueError("ForecastResult.rmse needs the verification sums: Forecast(..., verify=True)")
+        return torch.sqrt(torch.mean(self.sq, dim=0)) * state_std
+
+
+def _loaded_hip_runtime():
+    """The HIP runtime this process already runs on (torch's), for the two graph queries below."""
+    with open("/proc/self/maps") as maps:
+        paths = sorted({line.split()[-1] for line in maps if "libamdhip64" in line})
+    if not paths:
+        raise RuntimeError("no HIP runtime is loaded in this process")
+    return C.CDLL(paths[0])
+
+
+def _kernel_nodes(graph: "torch.cuda.CUDAGraph") -> int:
+    """Kernel nodes of a captured (``keep_graph=True``) graph: hipGraphGetNodes + hipGraphNodeGetType."""
+    hip = _loaded_hip_runtime()
+    raw = C.c_void_p(graph.raw_cuda_graph())
+    n = C.c_size_t(0)
+    if hip.hipGraphGetNodes(raw, None, C.byref(n)) != 0:
+        raise RuntimeError("hipGraphGetNodes failed")
+    nodes = (C.c_void_p * max(1, n.value))()
+    if hip.hipGraphGetNodes(raw, nodes, C.byref(n)) != 0:
+        raise RuntimeError("hipGraphGetNodes failed")
+    kernels = 0
+    for i in range(n.value):
+        kind = C.c_int(-1)
+        if hip.hipGraphNodeGetType(C.c_void_p(nodes[i]), C.byref(kind)) != 0:
+            raise RuntimeError("hipGraphNodeGetType failed")
+        kernels += kind.value == 0   # hipGraphNodeTypeKernel
+    return kernels
+
+
+class Forecast:
+    """A forecast engine over a trained ``ForecasterStep`` and a ``DeviceWeatherDataset`` of plain analysis series.
+
+    ``step``: its predictor, boundary mask, interior weights and statistics are used; the predictor must satisfy
+    ``can_return_raw_delta()`` or ``can_fuse_ext_tail()`` (GraphLAM, Hi-LAM, Hi-LAM-Parallel, with or without output clamps and a
+    predicted std; ValueError otherwise, Graph-EFM included).  ``dataset``: ``dataset.kernel == "nlam_window_batch"`` (forecast-type
+    and ensemble layouts: ValueError); its ``ar_steps`` is ignored, the horizon is ``max_lead``.  ``verify=True`` also scores
+    every lead against the analysis (``ForecastResult.sq`` / ``ab``).  ``use_graph=False`` issues the same launches eagerly.
+    ``autocast_dtype``: the predictor call alone runs under ``torch.autocast`` with it.  Weights changed in place between two
+    ``run`` calls (a training step, ``load_state_dict``, ``with tr.ema_weights():``) are honoured by the second call: the recorded
+    step reads the parameters where they live and the static embeddings are recomputed by every ``run``."""
+
+    def __init__(self, step, dataset, max_lead, batch_size=1, verify=False, use_graph=True, autocast_dtype=None):
+        from .models import ARForecaster
+
+        forecaster = getattr(step, "forecaster", None)
+        if not isinstance(forecaster, ARForecaster):
+            raise ValueError("Forecast needs a ForecasterStep over an ARForecaster")
+        predictor = forecaster.predictor
+        raw = getattr(predictor, "can_return_raw_delta", lambda: False)()
+        ext = getattr(predictor, "can_fuse_ext_tail", lambda: False)()
+        if not (raw or ext):
+            raise ValueError(f"Forecast: {type(predictor).__name__} cannot hand its raw network output to the forecast tail (it needs "
+                             "can_return_raw_delta() or can_fuse_ext_tail(): a graph model with a per-variable diff_std, and "
+                             "NLAM_FUSED_CLAMPED_TAIL on for output clamps or a predicted std; Graph-EFM is not served)")
+        if getattr(dataset, "kernel", None) != "nlam_window_batch":
+            raise ValueError("Forecast reads plain analysis series (dataset.kernel == 'nlam_window_batch'): forecast-type and ensemble "
+                             "datasets are not served")
+        self.max_lead, self.batch_size = int(max_lead), int(batch_size)
+        if self.max_lead < 1 or self.batch_size < 1:
+            raise ValueError(f"Forecast: max_lead {max_lead} and batch_size {batch_size} must be >= 1")
+        dev = getattr(getattr(dataset, "state", None), "device", dataset.device)   # with its index: "cuda" names the current device
+        if dev.type != "cuda" or any(p.device != dev for p in predictor.parameters()) or step.state_mean.device != dev:
+            raise RuntimeError(f"Forecast runs on the GPU that holds the dataset ({dev}): move the step there (there is no CPU fallback)")
+        self.step, self.dataset, self.predictor = step, dataset, predictor
+        self.verify, self.use_graph, self.autocast_dtype = bool(verify), bool(use_graph), autocast_dtype
+        self.past, self.future = dataset.num_past_forcing_steps, dataset.num_future_forcing_steps
+        self.n_times = int(dataset._n_times)
+        self.off, self.n_starts = plan_forecast(self.n_times, self.past, self.future, self.max_lead)
+        B, Lm = self.batch_size, self.max_lead
+        N, F = int(dataset.state.shape[1]), int(dataset.state.shape[2])
+        dfo = 0 if dataset.forcing is None else int(dataset.forcing.shape[2])
+        if N != predictor.num_grid_nodes or F != step.state_mean.numel() or (dfo > 0 and step.forcing_mean is None):
+            raise ValueError(f"Forecast: the dataset's series ({N} nodes, {F} state and {dfo} forcing variables) do not fit the step")
+        self.has_std = bool(predictor.output_std)
+        if self.verify and F > L.EVAL_MAX_VARS:
+            raise ValueError(f"Forecast(verify=True): at most {L.EVAL_MAX_VARS} state variables, got {F}")
+        self._lib = L.load()
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.start = torch.zeros((B,), device=dev, dtype=torch.int64)
+        self.lead = torch.zeros((1,), device=dev, dtype=torch.int32)
+        self.prev, self.prev_prev = torch.zeros((B, N, F), **f32), torch.zeros((B, N, F), **f32)
+        self.truth = torch.zeros((B, N, F), **f32)
+        self.forcing = torch.zeros((B, N, dfo * (self.past + self.future + 1)), **f32)
+        self.out_state = torch.empty((B, Lm, N, F), **f32)
+        self.out_std = torch.empty((B, Lm, N, F), **f32) if self.has_std else None
+        self.valid_times = torch.zeros((B, Lm), device=dev, dtype=torch.int64)
+        self.sq = self.ab = self.workspace = None
+        if self.verify:
+            self.sq, self.ab = torch.zeros((B, Lm, F), **f32), torch.zeros((B, Lm, F), **f32)
+            self.workspace = torch.empty((int(self._lib.nlam_forecast_workspace_floats(B, N, F)),), **f32)
+        self._bmask = forecaster.boundary_mask.reshape(-1).contiguous()
+        self._clamp = predictor.clamp_tables()
+        p = L.Forecast()
+        p.state, p.forcing, p.times = _ptr(dataset.state), _ptr(dataset.forcing), _ptr(dataset.times)
+        p.start, p.lead = _ptr(self.start), _ptr(self.lead)
+        p.state_mean, p.state_std = _ptr(step.state_mean), _ptr(step.state_std)
+        if dfo > 0:
+            p.forcing_mean, p.forcing_std = _ptr(step.forcing_mean), _ptr(step.forcing_std)
+            p.forcing_windowed = _ptr(self.forcing)
+        p.prev, p.prev_prev, p.truth = _ptr(self.prev), _ptr(self.prev_prev), _ptr(self.truth)
+        p.dstd, p.dmean = _ptr(predictor.diff_std), _ptr(predictor.diff_mean)
+        p.bmask, p.row_weight = _ptr(self._bmask), _ptr(step.interior_weight)
+        if self._clamp is not None:
+            p.clamp_mode_host, p.clamp_lo, p.clamp_hi = C.addressof(self._clamp.mode), _ptr(self._clamp.lo), _ptr(self._clamp.hi)
+        p.out_state, p.out_std, p.valid_times = _ptr(self.out_state), _ptr(self.out_std), _ptr(self.valid_times)
+        p.sq, p.ab, p.workspace = _ptr(self.sq), _ptr(self.ab), _ptr(self.workspace)
+        p.workspace_floats = 0 if self.workspace is None else self.workspace.numel()
+        p.n_times, p.nodes, p.d_state, p.d_forcing, p.batch = self.n_times, N, F, dfo, B
+        p.max_lead, p.num_past_forcing_steps, p.num_future_forcing_steps = Lm, self.past, self.future
+        p.delta_ld = 2 * F if self.has_std else F
+        self._p = p
+        self._static = None     # persistent copies of the predictor's static embeddings: the recorded step reads these
+        self._graph = None
+        self._delta = None      # the recorded step's network output (kept alive with the graph)
+        self._launches = None
+
+    # ---- one lead time ----
+    def _entry(self, name):
+        from .ops import _stream
+
+        L.check(getattr(self._lib, name)(C.byref(self._p), _stream()), name)
+
+    def _one_lead(self):
+        """head -> predictor -> tail -> finish on the current stream; every launch reads the lead counter on the device."""
+        self._entry("nlam_forecast_head")
+        cast = (torch.autocast(device_type="cuda", dtype=self.autocast_dtype) if self.autocast_dtype is not None
+                else contextlib.nullcontext())
+        with cast:
+            delta, _ = self.predictor(self.prev, self.prev_prev, self.forcing, raw_delta=True)
+        delta = delta.float().contiguous()
+        if tuple(delta.shape) != (self.batch_size, self._p.nodes, self._p.delta_ld):
+            raise RuntimeError(f"Forecast: the predictor returned {tuple(delta.shape)}")
+        self._p.delta = _ptr(delta)
+        self._entry("nlam_forecast_tail")
+        self._entry("nlam_forecast_finish")
+        return delta
+
+    @contextlib.contextmanager
+    def _static_installed(self):
+        """The predictor reads the persistent static embeddings (``BaseGraphModel._static``, as inside ``static_cache``)."""
+        old = self.predictor._static
+        self.predictor._static = self._static
+        try:
+            yield
+        finally:
+            self.predictor._static = old
+
+    def _refresh_static(self):
+        """The static embeddings from the CURRENT weights into the buffers the recorded step reads."""
+        new = self.predictor.compute_static_embeddings()
+        if self._static is None:
+            self._static = {k: [t.clone() for t in v] if isinstance(v, (list, tuple)) else v.clone() for k, v in new.items()}
+            return
+        for k, v in new.items():
+            if isinstance(v, (list, tuple)):
+                for dst, src in zip(self._static[k], v):
+                    dst.copy_(src)
+            else:
+                self._static[k].copy_(v)
+
+    def _record(self):
+        """Warm the step up (two eager leads on a side stream), then record it once."""
+        cur = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._one_lead()
+        cur.wait_stream(side)
+        graph = torch.cuda.CUDAGraph(keep_graph=True)
+        with torch.cuda.graph(graph):
+            self._delta = self._one_lead()
+        self._launches = _kernel_nodes(graph)
+        graph.instantiate()
+        self._graph = graph
+
+    @property
+    def launches_per_lead(self):
+        """Kernel nodes of the recorded step (it is recorded on first use); None with ``use_graph=False``."""
+        if not self.use_graph:
+            return None
+        if self._graph is None:
+            with torch.no_grad():
+                self._refresh_static()
+                with self._static_installed():
+                    self._record()
+        return self._launches
+
+    # ---- the forecast ----
+    def run(self, starts, leads=None):
+        """Forecast ``leads`` (default and at most ``max_lead``) steps ahead from the dataset samples ``starts`` (``batch_size``
+        of them, the indices ``dataset.batch`` takes; host indices are validated: IndexError; a device int64 tensor is used
+        as it is).  No host synchronisation.  The result's tensors are the engine's buffers: the next ``run`` overwrites them,
+        and with ``leads < max_lead`` the slots from ``leads`` on are unspecified."""
+        leads = self.max_lead if leads is None else int(leads)
+        if not 1 <= leads <= self.max_lead:
+            raise ValueError(f"Forecast.run: leads {leads} outside [1, {self.max_lead}]")
+        if not (isinstance(starts, torch.Tensor) and starts.is_cuda):
+            starts = check_starts(starts, self.n_starts).to(self.dataset.device)
+        starts = starts.to(torch.int64).reshape(-1)
+        if starts.numel() != self.batch_size:
+            raise ValueError(f"Forecast.run: {starts.numel()} starts for batch_size {self.batch_size}")
+        with torch.no_grad():
+            self._refresh_static()
+            with self._static_installed():
+                if self.use_graph and self._graph is None:
+                    self._record()
+                torch.add(starts, self.off - 1, out=self.start)   # t0 of every forecast
+                self._entry("nlam_forecast_init")
+                for _ in range(leads):
+                    if self.use_graph:
+                        self._graph.replay()
+                    else:
+                        self._one_lead()
+        return ForecastResult(self.out_state, self.out_std, self.valid_times, self.sq, self.ab)
