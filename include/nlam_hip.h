@@ -55,6 +55,10 @@
  *       a forecast of any length as replays of ONE recorded AR step: a lead counter in device memory ties the data path
  *       (this lead's forcing window and boundary truth, cut from the resident series) to the inference step tail, which
  *       rotates the state in place and writes this lead's physical fields, valid time and verification sums.
+ *   nlam_philox_normal_fill, nlam_latent_sample, nlam_ens_scores, nlam_ens_scores_workspace_floats
+ *       sampled ensembles inside that recorded step (Graph-EFM): the reparameterised draw of the latent variable from a
+ *       counter-based generator keyed by the lead counter, and the ensemble verification of every lead (ensemble-mean error,
+ *       spread, the two terms of fair CRPS, rank histogram, mean and spread fields) as one reduction over the member axis.
  *   nlam_window_moments, nlam_moments_workspace_doubles
  *       the per-sample means and second moments of npyfilesmeps/compute_standardization_stats.py (values and
  *       standardized one-step differences), read in place from the resident series of the data path.
@@ -1001,6 +1005,80 @@ int32_t nlam_forecast_tail(const nlam_forecast_t* p, void* hip_stream);
 int32_t nlam_forecast_finish(const nlam_forecast_t* p, void* hip_stream);
 /* floats of nlam_forecast_t.workspace for these sizes; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP for nvars > NLAM_EVAL_MAX_VARS */
 int64_t nlam_forecast_workspace_floats(int32_t batch, int32_t nodes, int32_t nvars);
+
+/* Sampled ensembles inside the recorded forecast step (neural_lam_amd/forecast.py, EnsembleForecast): batch = starts * members,
+ * batch item b = s * members + m (member-minor), every start repeated `members` times in nlam_forecast_t.start.
+ *
+ * The generator is Philox4x32-10 (Salmon et al. 2011, the constants of Random123): counter (c0, c1, c2, c3), key = (low, high)
+ * word of a 64-bit seed.  The four output words x become four standard normals z by two Box-Muller pairs:
+ *   u_i = ((x_i >> 9) + 0.5) * 2^-23            exact in fp32, never 0 or 1
+ *   r = sqrtf(-2 logf(u_0)), z_0 = r cospif(2 u_1), z_1 = r sinpif(2 u_1); (z_2, z_3) the same from (u_2, u_3)
+ *   nlam_philox_normal_fill   out[i], i < n: element i % 4 of counter (i / 4, c1, c2, c3).  NLAM_EINVAL for out == NULL or
+ *                             n < 0, NLAM_EUNSUP for n > 2^34; n == 0 launches nothing.
+ *   nlam_latent_sample        reads *lead = k (nothing is written once k >= max_lead).  params (batch, rows, P) are the
+ *                             parameters of the prior: P = latent_dim with diagonal = 0 (std 1), P = 2 latent_dim with
+ *                             diagonal = 1 (mean | std_raw, std = 1e-4 + softplus(std_raw)).
+ *                               latent[b][e] = mean + std * z          e < rows * latent_dim
+ *                             noise_in == NULL: z is element e % 4 of counter (e / 4, k, b % members, low word of start[b])
+ *                             under *seed, and goes to noise_out[k][b][e] when noise_out is given; noise_in given: z =
+ *                             noise_in[k][b][e] (both (max_lead, batch, rows, latent_dim)).  NLAM_EINVAL for null required
+ *                             pointers, sizes < 1, batch not a multiple of members, diagonal outside {0, 1}; NLAM_EUNSUP for
+ *                             batch > 65535 or rows * latent_dim >= 2^31.
+ *   nlam_ens_scores           after nlam_forecast_tail, before nlam_forecast_finish; reads *lead = k (nothing is written once
+ *                             k >= max_lead) and never writes it.  prev / truth (starts * members, nodes, d_state) are the
+ *                             standardised new states and the analysis (the truth of member 0 is used); w_n = row_weight[n],
+ *                             M = members, xbar the member mean, y the truth:
+ *                               ens_sq[s][k][f]   = sum_n w_n (xbar - y)^2
+ *                               ens_var[s][k][f]  = sum_n w_n / (M - 1) sum_m (x_m - xbar)^2            0 for M = 1
+ *                               ens_abs[s][k][f]  = sum_n w_n / M sum_m |x_m - y|
+ *                               ens_pair[s][k][f] = sum_n w_n / (M (M - 1)) sum_{i<j} |x_i - x_j|       0 for M = 1
+ *                                                   (fair CRPS = ens_abs - ens_pair)
+ *                               rank_hist[s][k][f][r], r = 0 .. M: the nodes with w_n != 0 whose truth has exactly r
+ *                                                   members strictly below it (a member equal to the truth is not below)
+ *                               out_mean[s][k][n][f]   = xbar * state_std[f] + state_mean[f]
+ *                               out_spread[s][k][n][f] = sqrt(sum_m (x_m - xbar)^2 / (M - 1)) * state_std[f]
+ *                             Per-workgroup partial sums in the workspace, one finishing launch that adds them in a fixed
+ *                             order: no floating-point atomics, bit-identical from run to run.  NLAM_EINVAL for null
+ *                             pointers (all are required), sizes < 1, a short workspace; NLAM_EUNSUP for members >
+ *                             NLAM_ENS_MAX_MEMBERS, d_state > NLAM_EVAL_MAX_VARS, starts > 65535, nodes * d_state >= 2^31.
+ * Every check comes before any launch; no allocation, no host synchronisation. */
+#define NLAM_ENS_MAX_MEMBERS 64
+typedef struct {
+    const float* params;      /* (batch, rows, P) */
+    const float* noise_in;    /* (max_lead, batch, rows, latent_dim) or NULL: draw */
+    float* noise_out;         /* (max_lead, batch, rows, latent_dim) or NULL */
+    float* latent;            /* (batch, rows, latent_dim) */
+    const int64_t* start;     /* device (batch): t0, as nlam_forecast_t.start */
+    const int32_t* lead;      /* device (1): k, only read */
+    const uint64_t* seed;     /* device (1): required when noise_in == NULL */
+    int32_t batch, members, rows, latent_dim;
+    int32_t diagonal, max_lead;
+} nlam_latent_sample_t;
+int32_t nlam_philox_normal_fill(float* out, int64_t n, uint64_t seed, uint32_t c1, uint32_t c2, uint32_t c3, void* hip_stream);
+int32_t nlam_latent_sample(const nlam_latent_sample_t* p, void* hip_stream);
+typedef struct {
+    const float* prev;         /* (starts * members, nodes, d_state) standardised states of this lead */
+    const float* truth;        /* (starts * members, nodes, d_state) standardised analysis */
+    const float* row_weight;   /* (nodes) */
+    const float* state_mean;   /* (d_state) */
+    const float* state_std;    /* (d_state) */
+    const int32_t* lead;       /* device (1): k, only read */
+    float* ens_sq;             /* (starts, max_lead, d_state) */
+    float* ens_var;            /* (starts, max_lead, d_state) */
+    float* ens_abs;            /* (starts, max_lead, d_state) */
+    float* ens_pair;           /* (starts, max_lead, d_state) */
+    int32_t* rank_hist;        /* (starts, max_lead, d_state, members + 1) */
+    float* out_mean;           /* (starts, max_lead, nodes, d_state) physical units */
+    float* out_spread;         /* (starts, max_lead, nodes, d_state) physical units */
+    float* workspace;          /* nlam_ens_scores_workspace_floats(starts, members, nodes, d_state) floats */
+    int64_t workspace_floats;
+    int32_t starts, members, nodes, d_state;
+    int32_t max_lead, _pad;
+} nlam_ens_scores_t;
+int32_t nlam_ens_scores(const nlam_ens_scores_t* p, void* hip_stream);
+/* floats of nlam_ens_scores_t.workspace; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP for members > NLAM_ENS_MAX_MEMBERS or
+ * nvars > NLAM_EVAL_MAX_VARS */
+int64_t nlam_ens_scores_workspace_floats(int32_t starts, int32_t members, int32_t nodes, int32_t nvars);
 
 /* The same batch launch over STRIDED series: forecast-type and ensemble datastores (weather_dataset.py:135-200, :235-254,
  * :303-342, :399-418).  Element (sample s, member m, step j) of a series -- one contiguous (nodes x d) block -- sits at

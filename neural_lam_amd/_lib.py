@@ -100,6 +100,7 @@ LOSS_MAX_VARS = 4096
 CLAMP_NONE, CLAMP_BOTH, CLAMP_LOWER, CLAMP_UPPER = 0, 1, 2, 3
 EVAL_MAX_MAPS = 32    # NLAM_EVAL_MAX_MAPS: lead times of one nlam_eval_metrics call's loss maps
 EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
+ENS_MAX_MEMBERS = 64  # NLAM_ENS_MAX_MEMBERS: members of one nlam_ens_scores call
 MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
 # learning-rate schedules of nlam_adamw_step_controlled (NLAM_SCHED_*) and the words of its control block
 SCHED_KINDS = {"constant": 1, "warmup_cosine": 2, "warmup_linear": 3}
@@ -194,6 +195,10 @@ EXPORTS = [
     "nlam_forecast_tail",
     "nlam_forecast_finish",
     "nlam_forecast_workspace_floats",
+    "nlam_philox_normal_fill",
+    "nlam_latent_sample",
+    "nlam_ens_scores",
+    "nlam_ens_scores_workspace_floats",
 ]
 
 
@@ -419,6 +424,54 @@ class Forecast(C.Structure):
         ("num_past_forcing_steps", C.c_int32),
         ("num_future_forcing_steps", C.c_int32),
         ("delta_ld", C.c_int32),
+    ]
+
+
+class LatentSample(C.Structure):
+    """nlam_latent_sample_t: the reparameterised draw of one lead for every batch item of an ensemble forecast."""
+
+    _fields_ = [
+        ("params", C.c_void_p),
+        ("noise_in", C.c_void_p),
+        ("noise_out", C.c_void_p),
+        ("latent", C.c_void_p),
+        ("start", C.c_void_p),
+        ("lead", C.c_void_p),
+        ("seed", C.c_void_p),
+        ("batch", C.c_int32),
+        ("members", C.c_int32),
+        ("rows", C.c_int32),
+        ("latent_dim", C.c_int32),
+        ("diagonal", C.c_int32),
+        ("max_lead", C.c_int32),
+    ]
+
+
+class EnsScores(C.Structure):
+    """nlam_ens_scores_t: the ensemble verification of one lead."""
+
+    _fields_ = [
+        ("prev", C.c_void_p),
+        ("truth", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("state_mean", C.c_void_p),
+        ("state_std", C.c_void_p),
+        ("lead", C.c_void_p),
+        ("ens_sq", C.c_void_p),
+        ("ens_var", C.c_void_p),
+        ("ens_abs", C.c_void_p),
+        ("ens_pair", C.c_void_p),
+        ("rank_hist", C.c_void_p),
+        ("out_mean", C.c_void_p),
+        ("out_spread", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("starts", C.c_int32),
+        ("members", C.c_int32),
+        ("nodes", C.c_int32),
+        ("d_state", C.c_int32),
+        ("max_lead", C.c_int32),
+        ("_pad", C.c_int32),
     ]
 
 
@@ -778,6 +831,14 @@ def load():
         entry.restype = i32
     lib.nlam_forecast_workspace_floats.argtypes = [i32, i32, i32]
     lib.nlam_forecast_workspace_floats.restype = i64
+    lib.nlam_philox_normal_fill.argtypes = [vp, i64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    lib.nlam_philox_normal_fill.restype = i32
+    lib.nlam_latent_sample.argtypes = [C.POINTER(LatentSample), vp]
+    lib.nlam_latent_sample.restype = i32
+    lib.nlam_ens_scores.argtypes = [C.POINTER(EnsScores), vp]
+    lib.nlam_ens_scores.restype = i32
+    lib.nlam_ens_scores_workspace_floats.argtypes = [i32, i32, i32, i32]
+    lib.nlam_ens_scores_workspace_floats.restype = i64
     lib.nlam_window_moments.argtypes = [C.POINTER(Moments), vp]
     lib.nlam_window_moments.restype = i32
     lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]

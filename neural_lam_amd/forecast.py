@@ -14,6 +14,16 @@ horizon, and the horizon does not depend on the rollout length the model was tra
     res = fc.run(starts)            # ForecastResult of device tensors, no host synchronisation
     res.state                       # (B, L, N, F) physical units
     res.rmse(step.state_std)        # (L, F) per-lead RMSE in physical units (verify=True)
+
+``EnsembleForecast`` is the same engine over ``starts x members``: with a Graph-EFM predictor every lead draws each member's latent
+sample on the device (``nlam_latent_sample``, a counter-based generator keyed by a seed and counted by lead, member and start
+time), and one more launch per lead scores the ensemble (``nlam_ens_scores``: ensemble-mean error, spread, fair CRPS, rank
+histogram, mean and spread fields).
+
+    ens = EnsembleForecast(step, dataset, max_lead=40, members=16, seed=7)
+    res = ens.run([0])              # EnsembleResult
+    res.members                     # (S, M, L, N, F) physical units;  res.mean, res.spread (S, L, N, F)
+    res.crps(step.state_std)        # (L, F) fair CRPS;  res.rmse(...), res.spread_skill(), res.rank_hist
 """
 from __future__ import annotations
 
@@ -108,6 +118,8 @@ class Forecast:
     ``run`` calls (a training step, ``load_state_dict``, ``with tr.ema_weights():``) are honoured by the second call: the recorded
     step reads the parameters where they live and the static embeddings are recomputed by every ``run``."""
 
+    _serves_latent = False
+
     def __init__(self, step, dataset, max_lead, batch_size=1, verify=False, use_graph=True, autocast_dtype=None):
         from .models import ARForecaster
 
@@ -117,6 +129,8 @@ class Forecast:
         predictor = forecaster.predictor
         raw = getattr(predictor, "can_return_raw_delta", lambda: False)()
         ext = getattr(predictor, "can_fuse_ext_tail", lambda: False)()
+        if getattr(predictor, "draws_latent", False) and not self._serves_latent:
+            raw = ext = False   # a predictor that samples: EnsembleForecast
         if not (raw or ext):
             raise ValueError(f"Forecast: {type(predictor).__name__} cannot hand its raw network output to the forecast tail (it needs "
                              "can_return_raw_delta() or can_fuse_ext_tail(): a graph model with a per-variable diff_std, and "
@@ -189,18 +203,28 @@ class Forecast:
 
         L.check(getattr(self._lib, name)(C.byref(self._p), _stream()), name)
 
+    def _autocast(self):
+        return (torch.autocast(device_type="cuda", dtype=self.autocast_dtype) if self.autocast_dtype is not None
+                else contextlib.nullcontext())
+
+    def _network(self):
+        """The predictor's raw output for the current lead."""
+        with self._autocast():
+            delta, _ = self.predictor(self.prev, self.prev_prev, self.forcing, raw_delta=True)
+        return delta
+
+    def _after_tail(self):
+        """Launches between the tail and the finish of a lead (none here)."""
+
     def _one_lead(self):
         """head -> predictor -> tail -> finish on the current stream; every launch reads the lead counter on the device."""
         self._entry("nlam_forecast_head")
-        cast = (torch.autocast(device_type="cuda", dtype=self.autocast_dtype) if self.autocast_dtype is not None
-                else contextlib.nullcontext())
-        with cast:
-            delta, _ = self.predictor(self.prev, self.prev_prev, self.forcing, raw_delta=True)
-        delta = delta.float().contiguous()
+        delta = self._network().float().contiguous()
         if tuple(delta.shape) != (self.batch_size, self._p.nodes, self._p.delta_ld):
             raise RuntimeError(f"Forecast: the predictor returned {tuple(delta.shape)}")
         self._p.delta = _ptr(delta)
         self._entry("nlam_forecast_tail")
+        self._after_tail()
         self._entry("nlam_forecast_finish")
         return delta
 
@@ -269,6 +293,11 @@ class Forecast:
         starts = starts.to(torch.int64).reshape(-1)
         if starts.numel() != self.batch_size:
             raise ValueError(f"Forecast.run: {starts.numel()} starts for batch_size {self.batch_size}")
+        self._replay(starts, leads)
+        return ForecastResult(self.out_state, self.out_std, self.valid_times, self.sq, self.ab)
+
+    def _replay(self, starts, leads):
+        """``leads`` leads from the device sample indices ``starts`` (one per batch item) into the engine's buffers."""
         with torch.no_grad():
             self._refresh_static()
             with self._static_installed():
@@ -281,4 +310,206 @@ class Forecast:
                         self._graph.replay()
                     else:
                         self._one_lead()
-        return ForecastResult(self.out_state, self.out_std, self.valid_times, self.sq, self.ab)
+
+
+class EnsembleResult(NamedTuple):
+    """Device tensors of one ``EnsembleForecast.run`` (the engine's buffers, cut to the ``leads`` that ran; batch item
+    ``b = s * M + m``).  The raw fields are those of ``ForecastResult`` over the ``S * M`` batch plus the ensemble launch's; the
+    accessors below give them their ensemble shapes.  Sums are in standardised units, fields in physical units."""
+    state: torch.Tensor
+    out_std: Optional[torch.Tensor]
+    times: torch.Tensor
+    sq: Optional[torch.Tensor]
+    ab: Optional[torch.Tensor]
+    mean: torch.Tensor                 # (S, leads, N, F) ensemble mean
+    spread: torch.Tensor               # (S, leads, N, F) sqrt of the unbiased member variance
+    ens_sq: Optional[torch.Tensor]     # (S, leads, F) sum_n w_n (xbar - y)^2
+    ens_var: Optional[torch.Tensor]    # (S, leads, F) sum_n w_n * unbiased member variance
+    ens_abs: Optional[torch.Tensor]    # (S, leads, F) sum_n w_n / M sum_m |x_m - y|
+    ens_pair: Optional[torch.Tensor]   # (S, leads, F) sum_n w_n / (M (M - 1)) sum_{i<j} |x_i - x_j|
+    rank_hist: Optional[torch.Tensor]  # (S, leads, F, M + 1) int32
+    noise: Optional[torch.Tensor]      # (leads, S * M, R, latent_dim) the standard-normal draws (record_noise / latent_noise)
+    n_members: int
+
+    def _per_member(self, t):
+        return None if t is None else t.view(t.shape[0] // self.n_members, self.n_members, *t.shape[1:])
+
+    @property
+    def members(self):
+        """(S, M, leads, N, F) member fields."""
+        return self._per_member(self.state)
+
+    @property
+    def std(self):
+        """(S, M, leads, N, F) predicted std of a std head, or None."""
+        return self._per_member(self.out_std)
+
+    @property
+    def valid_times(self):
+        """(S, leads)."""
+        return self._per_member(self.times)[:, 0]
+
+    @property
+    def member_sq(self):
+        """(S, M, leads, F): ``ForecastResult.sq`` of every member."""
+        return self._per_member(self.sq)
+
+    @property
+    def member_ab(self):
+        return self._per_member(self.ab)
+
+    def _scores(self):
+        if self.ens_sq is None:
+            raise ValueError("EnsembleResult: the scores need EnsembleForecast(..., verify=True)")
+
+    def rmse(self, state_std):
+        """(leads, F) RMSE of the ensemble mean in physical units: ``sqrt(mean_s ens_sq) * state_std``."""
+        self._scores()
+        return torch.sqrt(torch.mean(self.ens_sq, dim=0)) * state_std
+
+    def crps(self, state_std):
+        """(leads, F) fair CRPS in physical units: ``mean_s (ens_abs - ens_pair) * state_std``."""
+        self._scores()
+        return torch.mean(self.ens_abs - self.ens_pair, dim=0) * state_std
+
+    def spread_skill(self):
+        """(leads, F) ``sqrt((M + 1) / M * mean_s ens_var) / sqrt(mean_s ens_sq)``: 1 for a calibrated ensemble."""
+        self._scores()
+        M = self.n_members
+        return torch.sqrt((M + 1) / M * torch.mean(self.ens_var, dim=0)) / torch.sqrt(torch.mean(self.ens_sq, dim=0))
+
+
+class EnsembleForecast(Forecast):
+    """``members`` forecasts from each of ``n_starts`` initial times, as ONE recorded step over the batch ``n_starts * members``:
+
+        head -> embed + prior parameters -> nlam_latent_sample -> decoder -> tail -> nlam_ens_scores -> finish
+
+    replayed per lead.  The predictor is a Graph-EFM (``GraphEFM``, ``GraphEFMMultiScale``; ``can_return_raw_delta()``): every
+    lead draws a new latent sample per member from Philox4x32-10 keyed by ``seed`` and counted by (lead, member, start time),
+    so the forecast of ``(seed, start, member)`` has the same bits with and without the graph, from run to run and whatever
+    other starts share the batch.  A deterministic predictor (whatever ``Forecast`` takes) is accepted too, without the sampling
+    launch: its members are identical by construction (the baseline of the ensemble launch's cost).
+    ``verify``: the per-member sums of ``Forecast`` and the ensemble scores; the mean and spread fields are always written.
+    ``record_noise``: keep every lead's draws (``EnsembleResult.noise``).  Members are always kept: the member fields take
+    ``4 S M L N F`` bytes (twice that with a std head), mean and spread ``8 S L N F``."""
+
+    _serves_latent = True
+
+    def __init__(self, step, dataset, max_lead, members, n_starts=1, seed=0, verify=True, use_graph=True, autocast_dtype=None,
+                 record_noise=False):
+        members, n_starts = int(members), int(n_starts)
+        if not 1 <= members <= L.ENS_MAX_MEMBERS:
+            raise ValueError(f"EnsembleForecast: members {members} outside [1, {L.ENS_MAX_MEMBERS}]")
+        if n_starts < 1:
+            raise ValueError(f"EnsembleForecast: n_starts {n_starts} must be >= 1")
+        super().__init__(step, dataset, max_lead, batch_size=n_starts * members, verify=verify, use_graph=use_graph,
+                         autocast_dtype=autocast_dtype)
+        S, M, B, Lm = n_starts, members, n_starts * members, self.max_lead
+        N, F = self._p.nodes, self._p.d_state
+        if F > L.EVAL_MAX_VARS:
+            raise ValueError(f"EnsembleForecast: at most {L.EVAL_MAX_VARS} state variables, got {F}")
+        self.members, self.starts_per_run, self.record_noise = M, S, bool(record_noise)
+        dev = self.start.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.mean, self.spread = torch.empty((S, Lm, N, F), **f32), torch.empty((S, Lm, N, F), **f32)
+        self.ens_sq, self.ens_var, self.ens_abs, self.ens_pair = (torch.zeros((S, Lm, F), **f32) for _ in range(4))
+        self.rank_hist = torch.zeros((S, Lm, F, M + 1), device=dev, dtype=torch.int32)
+        self.ens_workspace = torch.empty((int(self._lib.nlam_ens_scores_workspace_floats(S, M, N, F)),), **f32)
+        e = L.EnsScores()
+        e.prev, e.truth, e.row_weight = _ptr(self.prev), _ptr(self.truth), _ptr(step.interior_weight)
+        e.state_mean, e.state_std, e.lead = _ptr(step.state_mean), _ptr(step.state_std), _ptr(self.lead)
+        e.ens_sq, e.ens_var, e.ens_abs, e.ens_pair = (_ptr(t) for t in (self.ens_sq, self.ens_var, self.ens_abs, self.ens_pair))
+        e.rank_hist, e.out_mean, e.out_spread = _ptr(self.rank_hist), _ptr(self.mean), _ptr(self.spread)
+        e.workspace, e.workspace_floats = _ptr(self.ens_workspace), self.ens_workspace.numel()
+        e.starts, e.members, e.nodes, e.d_state, e.max_lead = S, M, N, F, Lm
+        self._e = e
+        self.samples = bool(getattr(self.predictor, "draws_latent", False))
+        self.noise = self.latent = self.seed = None
+        self._given = False      # which of the two recordings is installed: noise drawn on the device / read from self.noise
+        self._recorded = {}
+        if self.samples:
+            R, D = int(self.predictor.latent_spatial_dim), int(self.predictor.latent_dim)
+            self.latent = torch.zeros((B, R, D), **f32)
+            self.seed = torch.zeros((1,), device=dev, dtype=torch.int64)
+            self._set_seed(seed)
+            if self.record_noise:
+                self.noise = torch.zeros((Lm, B, R, D), **f32)
+            s = L.LatentSample()
+            s.latent, s.start, s.lead, s.seed = _ptr(self.latent), _ptr(self.start), _ptr(self.lead), _ptr(self.seed)
+            s.noise_out = _ptr(self.noise)
+            s.batch, s.members, s.rows, s.latent_dim, s.max_lead = B, M, R, D, Lm
+            s.diagonal = int(self.predictor.prior_model.output_dist == "diagonal")
+            self._s = s
+        self._kept = None   # the recorded step's prior parameters (kept alive with the graph, like its network output)
+
+    def _set_seed(self, seed):
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.seed.fill_(seed - (1 << 64) if seed >= (1 << 63) else seed)   # the 64 bits, in the int64 the device word is kept as
+
+    def _network(self):
+        if not self.samples:
+            return super()._network()
+        from .ops import _stream
+
+        pred, s = self.predictor, self._s
+        with self._autocast():
+            grid_emb, graph_emb = pred.embedd_grid_and_graph(self.prev, self.prev_prev, self.forcing)
+            params = pred.prior_params(grid_emb, graph_emb)
+        params = params.float().contiguous()
+        if tuple(params.shape) != (s.batch, s.rows, s.latent_dim * (2 if s.diagonal else 1)):
+            raise RuntimeError(f"EnsembleForecast: the prior returned parameters of shape {tuple(params.shape)}")
+        s.params = _ptr(params)
+        L.check(self._lib.nlam_latent_sample(C.byref(s), _stream()), "nlam_latent_sample")
+        self._kept = params
+        with self._autocast():
+            return pred.decoder(grid_emb, self.latent, graph_emb, raw=True)
+
+    def _after_tail(self):
+        from .ops import _stream
+
+        L.check(self._lib.nlam_ens_scores(C.byref(self._e), _stream()), "nlam_ens_scores")
+
+    def _install(self, given):
+        """Install the recording that draws the noise (``given`` False) or reads it from ``self.noise`` (True)."""
+        if given and self.noise is None:
+            self.noise = torch.zeros((self.max_lead, *self.latent.shape), device=self.latent.device, dtype=torch.float32)
+        if given != self._given:
+            self._recorded[self._given] = (self._graph, self._delta, self._launches, self._kept)
+            self._graph, self._delta, self._launches, self._kept = self._recorded.pop(given, (None, None, None, None))
+            self._given = given
+        self._s.noise_in = _ptr(self.noise) if given else None
+        self._s.noise_out = None if given or not self.record_noise else _ptr(self.noise)
+
+    def run(self, starts, leads=None, seed=None, latent_noise=None):
+        """``leads`` leads (default and at most ``max_lead``) from the dataset samples ``starts`` (``n_starts`` of them, as
+        ``Forecast.run`` takes them), every one as ``members`` forecasts.  ``seed``: a new 64-bit seed (kept for later runs; no new
+        recording).  ``latent_noise`` (leads, n_starts * members, R, latent_dim): the standard-normal noise to use in place of
+        the generator's.  No host synchronisation; the result's tensors are the engine's buffers."""
+        leads = self.max_lead if leads is None else int(leads)
+        if not 1 <= leads <= self.max_lead:
+            raise ValueError(f"EnsembleForecast.run: leads {leads} outside [1, {self.max_lead}]")
+        if not (isinstance(starts, torch.Tensor) and starts.is_cuda):
+            starts = check_starts(starts, self.n_starts).to(self.dataset.device)
+        starts = starts.to(torch.int64).reshape(-1)
+        if starts.numel() != self.starts_per_run:
+            raise ValueError(f"EnsembleForecast.run: {starts.numel()} starts for n_starts {self.starts_per_run}")
+        if latent_noise is not None:
+            if not self.samples:
+                raise ValueError("EnsembleForecast.run: latent_noise for a predictor that draws none")
+            if tuple(latent_noise.shape) != (leads, *self.latent.shape):
+                raise ValueError(f"EnsembleForecast.run: latent_noise of shape {tuple(latent_noise.shape)}, expected "
+                                 f"{(leads, *self.latent.shape)}")
+            if not latent_noise.is_cuda:
+                raise RuntimeError("EnsembleForecast.run: latent_noise must be on the GPU (there is no CPU fallback)")
+        if self.samples:
+            self._install(latent_noise is not None)
+            if latent_noise is not None:
+                self.noise[:leads].copy_(latent_noise)
+            if seed is not None:
+                self._set_seed(seed)
+        self._replay(starts.repeat_interleave(self.members), leads)
+        cut = lambda t, dim=1: None if t is None else t.narrow(dim, 0, leads)   # noqa: E731
+        scores = (self.ens_sq, self.ens_var, self.ens_abs, self.ens_pair, self.rank_hist) if self.verify else (None,) * 5
+        noise = self.noise if self.samples and (self.record_noise or latent_noise is not None) else None
+        return EnsembleResult(cut(self.out_state), cut(self.out_std), cut(self.valid_times), cut(self.sq), cut(self.ab),
+                              cut(self.mean), cut(self.spread), *(cut(t) for t in scores), cut(noise, 0), self.members)

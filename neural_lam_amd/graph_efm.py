@@ -131,14 +131,36 @@ class BaseGraphEFM(StepPredictor):
         graph_emb.setdefault("m2m", [])   # hierarchical model without intra-level layers (:785-786)
         return grid_emb, graph_emb
 
-    def forward(self, prev_state, prev_prev_state, forcing, latent_noise=None):
-        """:415-471."""
+    draws_latent = True   # a probabilistic predictor: the deterministic engines (Forecast, the fused rollout tails) do not take it
+
+    def can_return_raw_delta(self) -> bool:
+        """True when ``forward(..., raw_delta=True)`` may hand the decoder's raw output to ``nlam_forecast_tail``: the conditions
+        ``BaseGraphModel`` states for itself in ``can_return_raw_delta`` / ``can_fuse_ext_tail`` -- a per-variable ``diff_std``, and
+        ``FUSED_CLAMPED_TAIL`` on for output clamps or a predicted std."""
+        from . import models
+
+        no_clamp = self.clamp_lower_upper_idx.numel() + self.clamp_lower_idx.numel() + self.clamp_upper_idx.numel() == 0
+        return self.diff_std.dim() == 1 and ((no_clamp and not self.output_std) or models.FUSED_CLAMPED_TAIL)
+
+    def prior_params(self, grid_prev_emb, graph_emb):
+        """The prior's parameter tensor (B, latent_spatial_dim, latent_dim | 2 latent_dim) on the embedded grid: what
+        ``prior_model.compute_dist_params`` returns and ``nlam_latent_sample`` reads."""
+        return self.prior_model.compute_dist_params(grid_prev_emb, graph_emb=graph_emb)
+
+    def forward(self, prev_state, prev_prev_state, forcing, latent_noise=None, raw_delta=False, latent=None):
+        """:415-471.  ``latent``: used as the sample (the prior is not evaluated).  ``raw_delta=True``: the decoder's raw output
+        (``BaseGraphLatentDecoder.forward(raw=True)``) in place of the clamped state, and None for the std."""
         grid_prev_emb, graph_emb = self.embedd_grid_and_graph(prev_state, prev_prev_state, forcing)
-        prior_dist = self.prior_model(grid_prev_emb, graph_emb=graph_emb)
-        if latent_noise is None:
-            latent_samples = prior_dist.rsample()
+        if latent is not None:
+            latent_samples = latent
         else:
-            latent_samples = prior_dist.mean + prior_dist.stddev * latent_noise
+            prior_dist = self.prior_model(grid_prev_emb, graph_emb=graph_emb)
+            if latent_noise is None:
+                latent_samples = prior_dist.rsample()
+            else:
+                latent_samples = prior_dist.mean + prior_dist.stddev * latent_noise
+        if raw_delta:
+            return self.decoder(grid_prev_emb, latent_samples, graph_emb, raw=True), None
         mean_delta, pred_std = self.decoder(grid_prev_emb, latent_samples, graph_emb)
         rescaled_mean_delta = mean_delta * self.diff_std + self.diff_mean
         return self.get_clamped_new_state(rescaled_mean_delta, prev_state), pred_std

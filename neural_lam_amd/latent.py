@@ -100,7 +100,9 @@ class BaseGraphLatentDecoder(nn.Module):
     def combine_with_latent(self, original_grid_rep, latent_rep, residual_grid_rep, graph_emb):
         raise NotImplementedError("combine_with_latent not implemented")
 
-    def forward(self, grid_rep, latent_samples, graph_emb):
+    def forward(self, grid_rep, latent_samples, graph_emb, raw=False):
+        """``raw=True``: ``state_params`` unsplit, (B, N, F) or (B, N, 2 F) with the std head before its softplus -- the row
+        layout ``nlam_forecast_tail`` takes (``delta_ld``)."""
         latent_emb = self.latent_embedder(latent_samples)
         if self.grid_update_mlp.fully_fused and grid_rep.is_cuda:
             residual_grid_rep, _ = self.grid_update_mlp.forward_fused(self._resid_geom, grid_rep)   # base_decoder.py:160
@@ -108,6 +110,8 @@ class BaseGraphLatentDecoder(nn.Module):
             residual_grid_rep = grid_rep + self.grid_update_mlp(grid_rep)
         combined = self.combine_with_latent(grid_rep, latent_emb, residual_grid_rep, graph_emb)
         state_params = self.param_map(combined)
+        if raw:
+            return state_params
         if self.output_std:
             mean_delta, std_raw = state_params.chunk(2, dim=-1)
             return mean_delta, nn.functional.softplus(std_raw)

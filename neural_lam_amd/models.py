@@ -660,7 +660,8 @@ class ARForecaster(nn.Module):
         preds, stds = [], []
         cache = self.predictor.static_cache() if hasattr(self.predictor, "static_cache") else contextlib.nullcontext()
         fused_tail = (loss_spec is not None and FUSED_STATE_UPDATE and init_states.is_cuda and init_states.dtype == torch.float32
-                      and boundary_states.dtype == torch.float32 and getattr(self.predictor, "can_return_raw_delta", lambda: False)())
+                      and boundary_states.dtype == torch.float32 and getattr(self.predictor, "can_return_raw_delta", lambda: False)()
+                      and not getattr(self.predictor, "draws_latent", False))   # Graph-EFM keeps its own tail in a rollout
         ext_tail = self.takes_ext_tail(init_states, boundary_states)
         losses = []
         if ext_tail and loss_spec is not None:

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Ensemble engine (neural_lam_amd/forecast.py, EnsembleForecast) against the deterministic engine, one process, alternating.
+
+    python tools/ensemble_bench.py [--config cfg2] [--members 4 16] [--leads 40] [--rounds 3] [--out profiles/ensemble/bench.json]
+    python tools/ensemble_bench.py --kernels-only      # under rocprofv3 --kernel-trace --stats: the two launches alone
+
+Route "forecast": ``Forecast(step, data, L, batch_size=M, verify=True).run([start] * M)`` with the configuration's GraphLAM.
+Route "ensemble": ``EnsembleForecast(step, data, L, members=M).run([start])`` with the same predictor: the same batch, the same
+network, plus nlam_ens_scores and its finishing pass per lead (no sampling launch: the predictor is deterministic).
+Route "efm": the engine with a GraphEFMMultiScale on the configuration's graph and width, in absolute terms.
+Per route: ms per lead (HIP events around a synchronised window of ``--repeats`` forecasts; median over the alternating rounds and
+the rounds' spread max - min), kernel launches per lead and peak memory above what the routes share (model and resident series).
+The two new launches alone: 50 of them recorded into one graph and replayed between two events, with their minimum bytes
+(nlam_ens_scores: 4 S N F (M + 3) + 8 S N F; nlam_latent_sample: parameters in, latent out) over that time.
+"""
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default="cfg2")
+    ap.add_argument("--members", type=int, nargs="+", default=[4, 16])
+    ap.add_argument("--leads", type=int, default=40)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=2, help="forecasts per timed window")
+    ap.add_argument("--kernels-only", action="store_true", help="launch nlam_ens_scores and nlam_latent_sample alone (for a kernel trace)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+
+    import bench
+    from forecast_bench import event_ms, kernel_ms
+    from neural_lam_amd import _lib as L
+    from neural_lam_amd import graph_efm
+    from neural_lam_amd import models as hm
+    from neural_lam_amd.data import DeviceWeatherDataset
+    from neural_lam_amd.forecast import EnsembleForecast, Forecast
+
+    dev = torch.device("cuda:0")
+    cfg = bench.CONFIGS[args.config]
+    ds, graph, _, _, step, _ = bench.build(cfg, dev)
+    N, F, DF = ds.num_grid_points, cfg["ns"], cfg["nf"]
+    n_times = args.leads + 8
+    g = torch.Generator().manual_seed(123)
+    state = torch.randn(n_times, N, F, generator=g).to(dev)
+    forcing = torch.randn(n_times, N, DF, generator=g).to(dev)
+    data = DeviceWeatherDataset(state, forcing, None, ar_steps=1, num_past_forcing_steps=1, num_future_forcing_steps=1,
+                                standardization=step.standardization_stats())
+    torch.manual_seed(42)
+    efm = graph_efm.GraphEFMMultiScale(ds, graph=graph, hidden_dim=cfg["d"])
+    efm_step = hm.ForecasterStep(hm.ARForecaster(efm, ds), ds, standardize=True).to(dev)
+    torch.cuda.synchronize()
+    shared = torch.cuda.memory_allocated()
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)   # noqa: E731
+    out = {"config": args.config, "nodes": N, "state_vars": F, "leads": args.leads, "rounds": args.rounds, "repeats": args.repeats,
+           "source_stamp": L.source_stamp(), "device": torch.cuda.get_device_name(0), "shared_bytes": shared, "members": {}}
+
+    for M in args.members:
+        row = {}
+        engines = {}
+        for name, make in (("forecast", lambda: Forecast(step, data, args.leads, batch_size=M, verify=True)),
+                           ("ensemble", lambda: EnsembleForecast(step, data, args.leads, members=M)),
+                           ("efm", lambda: EnsembleForecast(efm_step, data, args.leads, members=M))):
+            torch.cuda.synchronize()
+            before = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            eng = make()
+            run = (lambda e=eng: e.run([0] * M)) if name == "forecast" else (lambda e=eng: e.run([0]))
+            if args.kernels_only and name == "forecast":
+                continue
+            run()
+            torch.cuda.synchronize()
+            engines[name] = (eng, run)
+            row[name] = {"launches_per_lead": eng.launches_per_lead, "peak_bytes": torch.cuda.max_memory_allocated() - before}
+        if not args.kernels_only:
+            ms = {name: [] for name in engines}
+            for _ in range(args.rounds):
+                for name, (_, run) in engines.items():
+                    ms[name].append(event_ms(run, args.repeats) / args.leads)
+            for name in ms:
+                row[name].update(ms_per_lead=statistics.median(ms[name]), ms_per_lead_rounds=ms[name], spread_ms=max(ms[name]) - min(ms[name]))
+            row["ensemble_minus_forecast_ms"] = row["ensemble"]["ms_per_lead"] - row["forecast"]["ms_per_lead"]
+            row["efm"]["ms_per_lead_and_member"] = row["efm"]["ms_per_lead"] / M
+        # the two launches alone (the counter at 0: they write slot 0)
+        ens, efm_eng = engines["ensemble"][0], engines["efm"][0]
+        ens.run([0], leads=1)
+        ens.lead.zero_()
+        scores_ms = kernel_ms(lambda: L.check(ens._lib.nlam_ens_scores(C.byref(ens._e), stream()), "nlam_ens_scores"))
+        scores_bytes = 4 * N * F * (M + 3) + 8 * N * F
+        efm_eng.run([0], leads=1)
+        efm_eng.lead.zero_()
+        params = torch.randn(M, efm_eng._s.rows, efm_eng._s.latent_dim * (2 if efm_eng._s.diagonal else 1), generator=g).to(dev)
+        efm_eng._s.params = C.c_void_p(params.data_ptr())
+        sample_ms = kernel_ms(lambda: L.check(efm_eng._lib.nlam_latent_sample(C.byref(efm_eng._s), stream()), "nlam_latent_sample"))
+        sample_bytes = 4 * (params.numel() + efm_eng.latent.numel())
+        row["kernels"] = {"ens_scores_and_finish": {"ms": scores_ms, "min_bytes": scores_bytes, "gb_per_s": scores_bytes / scores_ms / 1e6},
+                          "latent_sample": {"ms": sample_ms, "min_bytes": sample_bytes, "gb_per_s": sample_bytes / sample_ms / 1e6,
+                                            "rows": efm_eng._s.rows, "latent_dim": efm_eng._s.latent_dim}}
+        out["members"][str(M)] = row
+        del engines, ens, efm_eng
+        torch.cuda.empty_cache()
+
+    text = json.dumps(out, indent=1)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
