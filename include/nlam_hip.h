@@ -59,6 +59,9 @@
  *       sampled ensembles inside that recorded step (Graph-EFM): the reparameterised draw of the latent variable from a
  *       counter-based generator keyed by the lead counter, and the ensemble verification of every lead (ensemble-mean error,
  *       spread, the two terms of fair CRPS, rank histogram, mean and spread fields) as one reduction over the member axis.
+ *   nlam_latent_kl_fwd, nlam_latent_kl_bwd, nlam_latent_kl_workspace_floats
+ *       the variational training objective of Graph-EFM: the reparameterised posterior draw from that generator and the KL
+ *       divergence from the prior as one pass with a fixed-order reduction, and its elementwise backward.
  *   nlam_window_moments, nlam_moments_workspace_doubles
  *       the per-sample means and second moments of npyfilesmeps/compute_standardization_stats.py (values and
  *       standardized one-step differences), read in place from the resident series of the data path.
@@ -1079,6 +1082,58 @@ int32_t nlam_ens_scores(const nlam_ens_scores_t* p, void* hip_stream);
 /* floats of nlam_ens_scores_t.workspace; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP for members > NLAM_ENS_MAX_MEMBERS or
  * nvars > NLAM_EVAL_MAX_VARS */
 int64_t nlam_ens_scores_workspace_floats(int32_t starts, int32_t members, int32_t nodes, int32_t nvars);
+
+/* The posterior draw and the KL term of the Graph-EFM training objective (Oskarsson et al. 2024, section 3; models.EFMForecaster)
+ * inside the recorded training step.  With D = latent_dim, u = 1e-4, pq (batch, rows, 2 D) the encoder's parameters (always
+ * diagonal) and pp (batch, rows, P) the prior's -- P = D with diagonal = 0 (std 1), P = 2 D with diagonal = 1 -- per element
+ * e < rows * D of batch item b:
+ *     mu_q = pq[.., :D], s_q = u + softplus(pq[.., D:]);   mu_p = pp[.., :D], s_p = u + softplus(pp[.., D:]) or 1
+ *   nlam_latent_kl_fwd        latent[b][e] = mu_q + s_q eps,   eps[b][e] = eps
+ *                             kl[b]   = sum_e log(s_p / s_q) + (s_q^2 + (mu_q - mu_p)^2) / (2 s_p^2) - 1/2
+ *                                       (evaluated as 1/2 (r^2 + n^2) - 1/2 - log r, r = s_q / s_p, n = (mu_q - mu_p) / s_p:
+ *                                       exactly 0 where q == p)
+ *                             kl_term = *kl_weight * sum_b kl[b]
+ *                             noise_in == NULL: eps is element e % 4 of the Philox counter (e / 4, t, b, low word of *draw)
+ *                             under *seed (the generator and the Box-Muller pairs of nlam_latent_sample); *draw is only read.
+ *                             noise_in given: eps = noise_in[b][e].  Per-workgroup partial sums in the workspace and one
+ *                             finishing workgroup that adds them in a fixed order (an item's partials in block order, then the
+ *                             items): no floating-point atomics, bit-identical from run to run.
+ *   nlam_latent_kl_bwd        elementwise, from the same pq, pp and the eps the forward wrote; g = g_latent[b][e] (0 for
+ *                             g_latent == NULL), w = *g_kl_term * *kl_weight, dlt = mu_q - mu_p:
+ *                               g_pq[.., :D] = g + w dlt / s_p^2
+ *                               g_pq[.., D:] = (g eps + w (s_q / s_p^2 - 1 / s_q)) softplus'(pq[.., D:])
+ *                               g_pp[.., :D] = -w dlt / s_p^2                                             unless g_pp == NULL
+ *                               g_pp[.., D:] = w (1 / s_p - (s_q^2 + dlt^2) / s_p^3) softplus'(pp[.., D:])   diagonal = 1
+ *                             softplus and its derivative are those of the step tails (beta 1, threshold 20, derivative 1 above).
+ * Both: 16-byte accesses where the buffers involved are 16-byte aligned (the parameter matrices also need D % 4 == 0), single
+ * elements otherwise; every check before any launch; no allocation, no host synchronisation.  NLAM_EINVAL for null required
+ * pointers (fwd: pq, pp, eps, kl_weight, latent, kl, kl_term, workspace, and seed and draw when noise_in == NULL; bwd: pq, pp,
+ * eps, kl_weight, g_kl_term, g_pq), sizes < 1, diagonal outside {0, 1}, t < 0, a short workspace; NLAM_EUNSUP for
+ * batch > 65535 or rows * latent_dim >= 2^31. */
+typedef struct {
+    const float* pq;           /* (batch, rows, 2 latent_dim) */
+    const float* pp;           /* (batch, rows, P) */
+    const float* noise_in;     /* (batch, rows, latent_dim) or NULL: draw */
+    const float* kl_weight;    /* device (1) */
+    const uint64_t* seed;      /* device (1): required when noise_in == NULL; the 64 bits of the key (a signed word carries the same) */
+    const int64_t* draw;       /* device (1): required when noise_in == NULL; only read */
+    float* eps;                /* (batch, rows, latent_dim): written by fwd, read by bwd */
+    float* latent;             /* fwd: (batch, rows, latent_dim) */
+    float* kl;                 /* fwd: (batch) */
+    float* kl_term;            /* fwd: device (1) */
+    float* workspace;          /* fwd: nlam_latent_kl_workspace_floats(batch, rows, latent_dim) floats */
+    int64_t workspace_floats;
+    const float* g_latent;     /* bwd: (batch, rows, latent_dim) or NULL: zero */
+    const float* g_kl_term;    /* bwd: device (1) */
+    float* g_pq;               /* bwd: (batch, rows, 2 latent_dim) */
+    float* g_pp;               /* bwd: (batch, rows, P) or NULL */
+    int32_t batch, rows, latent_dim, diagonal;
+    int32_t t, _pad;           /* t: the AR step, word 1 of the counter */
+} nlam_latent_kl_t;
+int32_t nlam_latent_kl_fwd(const nlam_latent_kl_t* p, void* hip_stream);
+int32_t nlam_latent_kl_bwd(const nlam_latent_kl_t* p, void* hip_stream);
+/* floats of nlam_latent_kl_t.workspace: one per workgroup; NLAM_EINVAL for sizes < 1 */
+int64_t nlam_latent_kl_workspace_floats(int32_t batch, int32_t rows, int32_t latent_dim);
 
 /* The same batch launch over STRIDED series: forecast-type and ensemble datastores (weather_dataset.py:135-200, :235-254,
  * :303-342, :399-418).  Element (sample s, member m, step j) of a series -- one contiguous (nodes x d) block -- sits at

@@ -199,6 +199,9 @@ EXPORTS = [
     "nlam_latent_sample",
     "nlam_ens_scores",
     "nlam_ens_scores_workspace_floats",
+    "nlam_latent_kl_fwd",
+    "nlam_latent_kl_bwd",
+    "nlam_latent_kl_workspace_floats",
 ]
 
 
@@ -471,6 +474,35 @@ class EnsScores(C.Structure):
         ("nodes", C.c_int32),
         ("d_state", C.c_int32),
         ("max_lead", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class LatentKl(C.Structure):
+    """nlam_latent_kl_t: the posterior draw and the KL term of one AR step of the Graph-EFM training objective."""
+
+    _fields_ = [
+        ("pq", C.c_void_p),
+        ("pp", C.c_void_p),
+        ("noise_in", C.c_void_p),
+        ("kl_weight", C.c_void_p),
+        ("seed", C.c_void_p),
+        ("draw", C.c_void_p),
+        ("eps", C.c_void_p),
+        ("latent", C.c_void_p),
+        ("kl", C.c_void_p),
+        ("kl_term", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("g_latent", C.c_void_p),
+        ("g_kl_term", C.c_void_p),
+        ("g_pq", C.c_void_p),
+        ("g_pp", C.c_void_p),
+        ("batch", C.c_int32),
+        ("rows", C.c_int32),
+        ("latent_dim", C.c_int32),
+        ("diagonal", C.c_int32),
+        ("t", C.c_int32),
         ("_pad", C.c_int32),
     ]
 
@@ -839,6 +871,12 @@ def load():
     lib.nlam_ens_scores.restype = i32
     lib.nlam_ens_scores_workspace_floats.argtypes = [i32, i32, i32, i32]
     lib.nlam_ens_scores_workspace_floats.restype = i64
+    lib.nlam_latent_kl_fwd.argtypes = [C.POINTER(LatentKl), vp]
+    lib.nlam_latent_kl_fwd.restype = i32
+    lib.nlam_latent_kl_bwd.argtypes = [C.POINTER(LatentKl), vp]
+    lib.nlam_latent_kl_bwd.restype = i32
+    lib.nlam_latent_kl_workspace_floats.argtypes = [i32, i32, i32]
+    lib.nlam_latent_kl_workspace_floats.restype = i64
     lib.nlam_window_moments.argtypes = [C.POINTER(Moments), vp]
     lib.nlam_window_moments.restype = i32
     lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]

@@ -16,8 +16,10 @@ invisible in the results:
   * ``forward`` takes an optional ``latent_noise`` (standard-normal, shape of the latent): the reparameterised sample is
     ``mean + std * noise`` -- what ``Normal.rsample`` computes -- so a test can hand over the noise the reference drew.
 
-Like the reference (models/__init__.py:15) these models are not entries of ``MODELS``: there is no training objective
-for them in the reference yet.
+Like the reference (models/__init__.py:15) these models are not entries of ``MODELS``.  The reference stops at exposing
+``encoder`` and ``prior_model``; here ``models.EFMForecaster`` / ``models.EFMForecasterStep`` train them with the variational
+objective of the Graph-EFM paper (posterior sample, KL term, rollout on posterior samples; ``posterior_params`` is the encoder's
+side of it), and ``forecast.EnsembleForecast`` draws and scores ensembles from the trained weights.
 """
 from __future__ import annotations
 
@@ -147,6 +149,13 @@ class BaseGraphEFM(StepPredictor):
         ``prior_model.compute_dist_params`` returns and ``nlam_latent_sample`` reads."""
         return self.prior_model.compute_dist_params(grid_prev_emb, graph_emb=graph_emb)
 
+    def posterior_params(self, prev_state, prev_prev_state, forcing, target_state, graph_emb):
+        """The variational posterior's parameter tensor (B, latent_spatial_dim, 2 latent_dim): the encoder (always diagonal) on
+        the grid embedded together with the state it is to explain -- the counterpart of ``prior_params``, and the other input
+        of ``nlam_latent_kl_fwd``.  ``graph_emb`` is what ``embedd_grid_and_graph`` returned for the same step."""
+        grid_current_emb = self.embedd_grid_with_target(prev_state, prev_prev_state, forcing, target_state)
+        return self.encoder.compute_dist_params(grid_current_emb, graph_emb=graph_emb)
+
     def forward(self, prev_state, prev_prev_state, forcing, latent_noise=None, raw_delta=False, latent=None):
         """:415-471.  ``latent``: used as the sample (the prior is not evaluated).  ``raw_delta=True``: the decoder's raw output
         (``BaseGraphLatentDecoder.forward(raw=True)``) in place of the clamped state, and None for the std."""
@@ -159,6 +168,12 @@ class BaseGraphEFM(StepPredictor):
                 latent_samples = prior_dist.rsample()
             else:
                 latent_samples = prior_dist.mean + prior_dist.stddev * latent_noise
+        return self.decode(grid_prev_emb, graph_emb, latent_samples, prev_state, raw_delta=raw_delta)
+
+    def decode(self, grid_prev_emb, graph_emb, latent_samples, prev_state, raw_delta=False):
+        """The second half of ``forward`` on embeddings the caller already holds (models.EFMForecaster embeds once per step for
+        prior, encoder and decoder): the sample decoded into (new state, predicted std | None), or with ``raw_delta=True`` into
+        (the decoder's raw output, None)."""
         if raw_delta:
             return self.decoder(grid_prev_emb, latent_samples, graph_emb, raw=True), None
         mean_delta, pred_std = self.decoder(grid_prev_emb, latent_samples, graph_emb)

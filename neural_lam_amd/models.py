@@ -955,8 +955,6 @@ class ForecasterStep(nn.Module):
         with this step's ``loss`` and its std.  ``steps_to_log``: the 1-based lead times of the test loss maps
         (``val_steps_to_log``); those beyond the rollout are skipped, as in the reference.  No host synchronisation and no
         data-dependent shape: the call can be captured (trainer.graphed_eval_step).  Returns an ``EvalResult``."""
-        from .ops import eval_metrics
-
         if phase not in ("val", "test"):
             raise ValueError(f"evaluate: phase must be 'val' or 'test', got {phase!r}")
         with torch.no_grad():
@@ -965,14 +963,267 @@ class ForecasterStep(nn.Module):
             if standardize:
                 init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
             prediction, pred_std = self.forecaster(init_states, forcing, target_states)
-            prediction = prediction.float().contiguous()
-            if pred_std is not None:
-                pred_std = pred_std.float().contiguous()
-            T = prediction.shape[1]
-            test = phase == "test"
-            map_steps = tuple(int(k) for k in steps_to_log if int(k) <= T) if test else ()
-            m = eval_metrics(prediction, target_states.float().contiguous(), pred_std, self.per_var_std, self.interior_weight,
-                             self.loss_kind, [k - 1 for k in map_steps], want_mae=test, want_std=test and pred_std is not None)
-            time_step_loss = torch.mean(m["step_loss"], dim=0)
-            return EvalResult(phase, prediction, time_step_loss, torch.mean(time_step_loss), m["sq"], m.get("ab"), m.get("maps"),
-                              m.get("std_mean"), map_steps)
+            return EvalResult(*self._eval_fields(prediction, pred_std, target_states, phase, steps_to_log))
+
+    def _eval_fields(self, prediction, pred_std, target_states, phase, steps_to_log):
+        """The arguments of ``EvalResult`` for a finished rollout: every metric of the step in one ``nlam_eval_metrics`` pass."""
+        from .ops import eval_metrics
+
+        prediction = prediction.float().contiguous()
+        if pred_std is not None:
+            pred_std = pred_std.float().contiguous()
+        T = prediction.shape[1]
+        test = phase == "test"
+        map_steps = tuple(int(k) for k in steps_to_log if int(k) <= T) if test else ()
+        m = eval_metrics(prediction, target_states.float().contiguous(), pred_std, self.per_var_std, self.interior_weight,
+                         self.loss_kind, [k - 1 for k in map_steps], want_mae=test, want_std=test and pred_std is not None)
+        time_step_loss = torch.mean(m["step_loss"], dim=0)
+        return (phase, prediction, time_step_loss, torch.mean(time_step_loss), m["sq"], m.get("ab"), m.get("maps"),
+                m.get("std_mean"), map_steps)
+
+
+class EFMForecaster(ARForecaster):
+    """The rollout of the Graph-EFM training objective (Oskarsson et al. 2024, section 3) over a ``GraphEFM`` /
+    ``GraphEFMMultiScale`` predictor.  Per AR step t:
+
+        embed the grid and the static graph features (the static ones once per rollout, shared by prior, encoder and decoder)
+        pp = predictor.prior_params(..)              pq = predictor.posterior_params(.., target_t, ..)
+        z, kl_t = ops.LatentKLFunction(pq, pp, ..)   (z = mu_q + s_q eps; kl_t = kl_weight * sum_b KL(q || p))
+        raw = decoder(z); new state, loss term = the step tail (rescale, clamps, predicted std, boundary overwrite)
+
+    and the new state is the next step's ``prev_state``: the rollout follows posterior samples.  A subclass of ``ARForecaster``
+    for what it shares (the masks, ``predicts_std``, being what ``forecast.EnsembleForecast`` accepts), a ``forward`` of its own:
+    ``ARForecaster.forward`` keeps Graph-EFM off the fused tails and is untouched.
+
+    The static embeddings are not registered for the rollout-shared gradient hand-over (``ops.rollout_shared_reset``): that
+    hand-over serves one fused edge launch per AR step, here a step has up to three consumers of an embedding (prior, encoder,
+    decoder), one of which a constant prior drops, so autograd adds their gradients as it does for ``ForecasterStep`` over a
+    Graph-EFM.  ``forward`` clears whatever another model registered."""
+
+    def forward(self, init_states, forcing_features, boundary_states, loss_spec=None, kl_words=None, latent_noise=None):
+        """``loss_spec = (target_states, var_std (F,) | None, row_weight (N,), scale, kind)`` as ``ARForecaster.forward`` takes
+        it; ``kl_words = (kl_weight, seed, draw)``, the device words of ``EFMForecasterStep``; ``latent_noise`` (B, T, R, D):
+        standard-normal noise in place of the generator's.  Returns (prediction (B, T, N, F), pred_std | None, likelihood,
+        kl): the two terms of the loss, weights included; ``self.last_kl`` keeps the unweighted (T, B) KL per item.  Without
+        ``kl_words`` this is ``ARForecaster.forward`` (a rollout on samples of the prior; what ``ForecasterStep`` calls)."""
+        from .ops import LatentKLFunction, LossFunction, StepTailExtFunction, StepTailFunction, rollout_shared_reset
+
+        if kl_words is None:   # not the objective: ARForecaster's rollout on samples of the prior, as for any step predictor
+            return super().forward(init_states, forcing_features, boundary_states, loss_spec)
+        if loss_spec is None or len(loss_spec) != 5:
+            raise ValueError("EFMForecaster: the objective (kl_words given) needs the five-entry loss_spec of EFMForecasterStep")
+        pred = self.predictor
+        target, consts, row_weight, scale, kind = loss_spec
+        kl_weight, seed, draw = kl_words
+        prev_prev_state, prev_state = init_states[:, 0], init_states[:, 1]
+        no_clamp = pred.clamp_tables() is None
+        raw = (FUSED_STATE_UPDATE and init_states.is_cuda and init_states.dtype == torch.float32
+               and boundary_states.dtype == torch.float32 and pred.can_return_raw_delta())
+        plain = raw and no_clamp and not pred.output_std
+        bmask = self.boundary_mask.reshape(-1)
+        preds, stds, losses, kls, kl_items = [], [], [], [], []
+        rollout_shared_reset(())
+        with pred.static_cache():
+            for i in range(forcing_features.shape[1]):
+                forcing = forcing_features[:, i]
+                grid_prev_emb, graph_emb = pred.embedd_grid_and_graph(prev_state, prev_prev_state, forcing)
+                pp = pred.prior_params(grid_prev_emb, graph_emb)
+                pq = pred.posterior_params(prev_state, prev_prev_state, forcing, target[:, i], graph_emb)
+                z, kl_t, kl_b = LatentKLFunction.apply(pq.float(), pp.float(), kl_weight, seed, draw, i,
+                                                       None if latent_noise is None else latent_noise[:, i])
+                kls.append(kl_t)
+                kl_items.append(kl_b)
+                if raw:
+                    delta, _ = pred.decode(grid_prev_emb, graph_emb, z, prev_state, raw_delta=True)
+                    if plain:
+                        new_state, loss_t = StepTailFunction.apply(delta.float(), prev_state, boundary_states[:, i], target[:, i],
+                                                                   pred.diff_std, pred.diff_mean, bmask, consts, row_weight, scale, kind)
+                        pred_std = None
+                    else:
+                        new_state, pred_std, loss_t = StepTailExtFunction.apply(
+                            delta.float(), prev_state, boundary_states[:, i], target[:, i], pred.diff_std, pred.diff_mean, bmask,
+                            consts, row_weight, scale, kind, pred.clamp_tables())
+                    losses.append(loss_t)
+                else:
+                    pred_state, pred_std = pred.decode(grid_prev_emb, graph_emb, z, prev_state)
+                    new_state = self.boundary_mask * boundary_states[:, i] + self.interior_mask * pred_state
+                preds.append(new_state)
+                if pred_std is not None:
+                    stds.append(pred_std)
+                prev_prev_state, prev_state = prev_state, new_state
+
+        def _stack(xs):
+            return xs[0].unsqueeze(1) if len(xs) == 1 else torch.stack(xs, dim=1)
+
+        prediction, pred_std = _stack(preds), (_stack(stds) if stds else None)
+        if losses:
+            lik = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+        else:   # the unfused tail: one loss pass over the rollout (its scale is the same 1 / (B T))
+            from ._lib import LOSS_MAE, LOSS_MSE
+
+            std = None if kind in (LOSS_MSE, LOSS_MAE) or pred_std is None else pred_std.float()
+            lik = LossFunction.apply(prediction.float(), target.float(), std, consts if std is None else None, row_weight, kind)
+        kl = kls[0] if len(kls) == 1 else torch.stack(kls).sum()
+        self.last_kl = torch.stack(kl_items).detach()
+        return prediction, pred_std, lik, kl
+
+    last_kl = None
+
+
+class EFMEvalResult(EvalResult):
+    """What ``EFMForecasterStep.evaluate`` returns: the ``EvalResult`` of the rollout on posterior samples (``prediction``,
+    ``time_step_loss`` .. as ``ForecasterStep.evaluate`` gives them, so ``evaluation.MetricAggregator`` and
+    ``trainer.graphed_eval_step`` take it), and the validation ELBO ``loss`` = ``likelihood`` + ``kl`` (both weighted as in
+    training), ``kl_per_item`` (T, B) unweighted, ``pred_std`` (B, T, N, F) or None."""
+
+    __slots__ = ("pred_std", "loss", "likelihood", "kl", "kl_per_item")
+
+    def __init__(self, fields, pred_std, loss, likelihood, kl, kl_per_item):
+        super().__init__(*fields)
+        self.pred_std, self.loss, self.likelihood, self.kl, self.kl_per_item = pred_std, loss, likelihood, kl, kl_per_item
+
+
+class EFMForecasterStep(ForecasterStep):
+    """The training step of Graph-EFM: ``forward(init, target, forcing) -> (prediction, loss)`` with
+
+        loss = 1 / (B T) sum_{b,t} [ lik_{b,t} + kl_beta / N_interior * KL_{b,t} ]
+
+    ``lik`` the step tail's loss term of kind ``loss`` (``nll`` by default) under the conventions of ``ForecasterStep`` (interior
+    mask, grid mean, sum over variables; the predicted std or the per-variable ``diff_std / sqrt(weight)``), ``KL`` the divergence
+    of the encoder's posterior from the prior, summed over the latent.  This is the paper's negative ELBO (``-log p + beta KL``,
+    summed over the grid) divided by the constant ``N_interior``: the same minimiser, the magnitude of ``--loss nll``, and the
+    step tails run unchanged with their ``scale``.  Standardisation, the per-variable std and the loss names are
+    ``ForecasterStep``'s (this is a subclass), so ``Trainer(step)`` takes it as it is.
+
+    Noise.  The step owns three kinds of device words: ``seed`` (the 64-bit Philox key -- the C-ABI's uint64, kept in an int64
+    buffer that carries the same 64 bits), ``draw`` (int64) and ``kl_weight`` (float, ``kl_beta / (N_interior B T)``: one word
+    per batch shape, ``kl_weight_word(B, T)``, so that an eager step or an ``evaluate`` at another shape never changes what a
+    recorded step reads).  Every ``forward`` advances ``draw`` by one on the device before its first draw, and the
+    draw of AR step t, item b is keyed by (seed; quad, t, b, draw): a replay of the captured step draws new noise and records
+    nothing again; so does every micro-batch of an accumulation window.  ``set_kl_beta`` (annealing) and ``reseed`` write the
+    words in place.  Ranks must not share noise: the key is ``noise_key(seed, rank) = (seed + rank * 0x9E3779B97F4A7C15) mod 2^64``
+    (an odd multiplier: distinct ranks give distinct keys), ``rank`` from ``torch.distributed`` unless given.
+    ``draw_state()`` / ``load_draw_state()`` carry ``{seed, draw, kl_beta}`` through ``save_checkpoint(..., extra=...)``.
+    ``last_terms``: the device scalars (likelihood, kl) of the last forward that ran, eager or replayed."""
+
+    def __init__(self, forecaster, datastore, standardize: bool = False, state_feature_weights=None, loss: str = "nll",
+                 kl_beta: float = 1.0, seed: int = 0, rank: int | None = None):
+        if not getattr(getattr(forecaster, "predictor", None), "draws_latent", False):
+            raise ValueError(f"EFMForecasterStep trains a predictor that draws a latent variable (GraphEFM, GraphEFMMultiScale), not "
+                             f"{type(getattr(forecaster, 'predictor', forecaster)).__name__}: use ForecasterStep")
+        if not isinstance(forecaster, EFMForecaster):
+            raise ValueError("EFMForecasterStep needs an EFMForecaster over the predictor")
+        super().__init__(forecaster, datastore, standardize=standardize, state_feature_weights=state_feature_weights, loss=loss)
+        if rank is None:
+            import torch.distributed as dist
+
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.rank = int(rank)
+        self.n_interior = int(self.interior_index.numel())
+        self.kl_beta, self.seed_value = float(kl_beta), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.register_buffer("seed", torch.zeros((1,), dtype=torch.int64), persistent=False)      # the 64 bits of the key
+        self.register_buffer("draw", torch.zeros((1,), dtype=torch.int64), persistent=False)
+        self.register_buffer("eval_draw", torch.full((1,), 1 << 31, dtype=torch.int64), persistent=False)
+        self.register_buffer("_terms", torch.zeros((2,), dtype=torch.float32), persistent=False)   # (likelihood, kl) of the last forward
+        self._kl_words = {}   # (B, T) -> the device float kl_beta / (N_interior B T) of the steps recorded or run at that shape
+        self._seed_device = None
+
+    @property
+    def last_terms(self):
+        """(likelihood, kl) of the last ``forward`` that ran -- eager or a replay of a recorded one: views of a device buffer the
+        forward writes, weights included, no gradient."""
+        return self._terms[0], self._terms[1]
+
+    @staticmethod
+    def noise_key(seed: int, rank: int) -> int:
+        """The Philox key of ``rank`` under ``seed``: 64 bits, distinct for distinct ranks."""
+        return (int(seed) + int(rank) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+    def kl_weight_value(self, B: int, T: int) -> float:
+        """``kl_beta / (N_interior B T)``: what the host writes into the device word of that batch shape."""
+        return self.kl_beta / (self.n_interior * B * T)
+
+    def kl_weight_word(self, B: int, T: int):
+        """The device float ``kl_beta / (N_interior B T)`` of batch shape (B, T): one word per shape, because a recorded step keeps
+        reading the word it was recorded with (its ``1 / (B T)`` is baked into the tails' ``scale`` in the same way) while an
+        eager call or ``evaluate`` at another shape runs in between.  Made on first use and then only written in place
+        (``set_kl_beta``); never made inside a capture: the recorded fill would undo ``set_kl_beta`` at every replay."""
+        dev = self.draw.device
+        if self._seed_device != dev:   # after construction / ``.to()``: the words of another device are dropped, the key is written
+            self._kl_words = {}
+            self._write_seed()
+        word = self._kl_words.get((B, T))
+        if word is None:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("EFMForecasterStep: the first call for a batch shape must run outside a stream capture (Trainer's "
+                                   "warm-up does): it writes that shape's kl_weight")
+            word = self._kl_words[(B, T)] = torch.full((1,), self.kl_weight_value(B, T), dtype=torch.float32, device=dev)
+        return word
+
+    def _write_seed(self):
+        key = self.noise_key(self.seed_value, self.rank)
+        self.seed.fill_(key - (1 << 64) if key >= (1 << 63) else key)   # the 64 bits, in the int64 the device word is kept as
+        self._seed_device = self.seed.device
+
+    def set_kl_beta(self, kl_beta: float):
+        """A new ``kl_beta`` (annealing), written in place into the device word of every batch shape seen so far: no captured step
+        is recorded again.  Not between a ``forward`` and its ``backward``: the operator saved the word (autograd then refuses)."""
+        self.kl_beta = float(kl_beta)
+        for (B, T), word in self._kl_words.items():
+            word.fill_(self.kl_weight_value(B, T))
+
+    def reseed(self, seed: int, draw: int = 0):
+        """A new seed and draw count, written in place (no new recording): the next call draws (seed, draw + 1)."""
+        self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if self._seed_device != self.draw.device:
+            self._kl_words = {}
+        self._write_seed()
+        self.draw.fill_(int(draw))
+
+    def draw_state(self) -> dict:
+        """``{seed, draw, kl_beta}`` for ``save_checkpoint(..., extra=step.draw_state())`` (reads ``draw`` back: synchronises)."""
+        return {"seed": self.seed_value, "draw": int(self.draw.item()), "kl_beta": self.kl_beta}
+
+    def load_draw_state(self, state: dict):
+        """Continue the noise sequence of a saved run (the rank's key is folded in again here)."""
+        self.reseed(int(state["seed"]), int(state["draw"]))
+        self.set_kl_beta(float(state["kl_beta"]))
+
+    def replay_state(self):
+        """The device counters ``forward`` advances: ``Trainer`` puts them back behind the warm-up passes of a recording."""
+        return [self.draw]
+
+    def _elbo(self, init_states, target_states, forcing, draw, latent_noise):
+        B, T = target_states.shape[0], target_states.shape[1]
+        kl_weight = self.kl_weight_word(B, T)
+        if latent_noise is None:
+            draw.add_(1)
+        spec = (target_states, self.per_var_std, self.interior_weight, 1.0 / (B * T), self.loss_kind)
+        return self.forecaster(init_states, forcing, target_states, loss_spec=spec, kl_words=(kl_weight, self.seed, draw),
+                               latent_noise=latent_noise)
+
+    def forward(self, init_states, target_states, forcing, standardize: bool | None = None, latent_noise=None):
+        if standardize is None:
+            standardize = self.standardize_inputs
+        if standardize:
+            init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
+        prediction, _, lik, kl = self._elbo(init_states, target_states, forcing, self.draw, latent_noise)
+        torch.stack((lik.detach().reshape(()), kl.detach().reshape(())), out=self._terms)   # one launch, recorded with the step
+        return prediction, lik + kl
+
+    def evaluate(self, init_states, target_states, forcing, phase="val", steps_to_log=(1,), standardize=None, latent_noise=None):
+        """``ForecasterStep.evaluate`` for this objective: the launches of ``forward`` under ``torch.no_grad()`` -- the rollout on
+        posterior samples -- then the metric pass of ``validation_step`` / ``test_step`` on its predictions.  Returns an
+        ``EFMEvalResult``: the ``EvalResult`` fields plus the validation ELBO and its two terms.  It draws on a counter of its own
+        (``eval_draw``, started at 2^31), so validating does not move the training run's noise sequence, and reads the
+        ``kl_weight`` word of its own batch shape.  Capturable after one eager call at that shape (trainer.graphed_eval_step)."""
+        if phase not in ("val", "test"):
+            raise ValueError(f"evaluate: phase must be 'val' or 'test', got {phase!r}")
+        with torch.no_grad():
+            if standardize is None:
+                standardize = self.standardize_inputs
+            if standardize:
+                init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
+            prediction, pred_std, lik, kl = self._elbo(init_states, target_states, forcing, self.eval_draw, latent_noise)
+            fields = self._eval_fields(prediction, pred_std, target_states, phase, steps_to_log)
+            return EFMEvalResult(fields, pred_std, lik + kl, lik, kl, self.forecaster.last_kl)

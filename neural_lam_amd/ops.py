@@ -2473,6 +2473,75 @@ class LossFunction(torch.autograd.Function):
         return dpred, None, dstd, None, None, None
 
 
+class LatentKLFunction(torch.autograd.Function):
+    """The posterior draw and the KL term of one AR step of the Graph-EFM objective (nlam_latent_kl_fwd / _bwd; the formulas are
+    in include/nlam_hip.h):
+
+    forward(pq (B, R, 2 D), pp (B, R, D | 2 D), kl_weight (device float), seed (device word: the 64 bits of the key), draw (device int64), t,
+    noise_in (B, R, D) | None) -> (z (B, R, D), kl_term scalar = kl_weight * sum_b KL_b, kl_per_item (B,)).
+    ``z = mu_q + s_q eps``; eps is drawn on the device under (seed, draw, t) unless ``noise_in`` is given, and saved for the
+    backward with pq and pp.  Gradients: pq, and pp when it requires one (a constant prior gets none); ``kl_per_item`` is not
+    differentiable.  No host synchronisation, no allocation outside torch's allocator: the call can be captured.  ``kl_weight`` is
+    saved for the backward, which multiplies it in again: writing it in place between an eager forward and its backward makes
+    autograd refuse the backward, and a replayed backward reads the word as it is then."""
+
+    @staticmethod
+    def _args(pq, pp, kl_weight, eps, t):
+        B, R, D2 = pq.shape
+        D = D2 // 2
+        if D2 != 2 * D or pp.dim() != 3 or pp.shape[:2] != (B, R) or pp.shape[2] not in (D, 2 * D):
+            raise ValueError(f"LatentKLFunction: posterior parameters {tuple(pq.shape)} against prior parameters {tuple(pp.shape)}")
+        p = L.LatentKl()
+        p.pq, p.pp, p.kl_weight, p.eps = _ptr(pq), _ptr(pp), _ptr(kl_weight), _ptr(eps)
+        p.batch, p.rows, p.latent_dim, p.diagonal, p.t = B, R, D, int(pp.shape[2] == 2 * D), int(t)
+        return p
+
+    @staticmethod
+    def forward(ctx, pq, pp, kl_weight, seed, draw, t: int, noise_in=None):
+        lib = L.load()
+        _require_gpu(pq, pp, kl_weight, noise_in)
+        if noise_in is None and not (seed.is_cuda and draw.is_cuda and seed.dtype in (torch.uint64, torch.int64) and draw.dtype == torch.int64):
+            raise RuntimeError("LatentKLFunction: seed (the 64 bits of the key, uint64 or int64) and draw (int64) are words in device memory")
+        pq, pp, noise_in = map(_cont, (pq, pp, noise_in))
+        B, R, D = pq.shape[0], pq.shape[1], pq.shape[2] // 2
+        dev = pq.device
+        eps = torch.empty((B, R, D), device=dev, dtype=torch.float32)
+        p = LatentKLFunction._args(pq, pp, kl_weight, eps, t)
+        if noise_in is not None and noise_in.shape != eps.shape:
+            raise ValueError(f"LatentKLFunction: noise of shape {tuple(noise_in.shape)} for a latent of shape {tuple(eps.shape)}")
+        z = torch.empty_like(eps)
+        kl = torch.empty((B,), device=dev, dtype=torch.float32)
+        kl_term = torch.empty((), device=dev, dtype=torch.float32)
+        nws = lib.nlam_latent_kl_workspace_floats(B, R, D)
+        if nws < 0:
+            L.check(int(nws), "nlam_latent_kl_workspace_floats")
+        ws = torch.empty((nws,), device=dev, dtype=torch.float32)
+        p.noise_in, p.latent, p.kl, p.kl_term, p.workspace, p.workspace_floats = _ptr(noise_in), _ptr(z), _ptr(kl), _ptr(kl_term), _ptr(ws), nws
+        if noise_in is None:
+            p.seed, p.draw = _ptr(seed), _ptr(draw)
+        L.check(lib.nlam_latent_kl_fwd(C.byref(p), _stream()), "nlam_latent_kl_fwd")
+        ctx.save_for_backward(pq, pp, eps, kl_weight)
+        ctx.t = int(t)
+        ctx.mark_non_differentiable(kl)
+        ctx.set_materialize_grads(False)
+        return z, kl_term, kl
+
+    @staticmethod
+    def backward(ctx, g_z, g_term, _g_kl):
+        pq, pp, eps, kl_weight = ctx.saved_tensors
+        none = (None,) * 7
+        if (g_z is None and g_term is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return none
+        gt = g_term.contiguous().to(torch.float32) if g_term is not None else torch.zeros((), device=pq.device, dtype=torch.float32)
+        gz = g_z.contiguous() if g_z is not None else None
+        g_pq = torch.empty_like(pq)
+        g_pp = torch.empty_like(pp) if ctx.needs_input_grad[1] else None
+        p = LatentKLFunction._args(pq, pp, kl_weight, eps, ctx.t)
+        p.g_latent, p.g_kl_term, p.g_pq, p.g_pp = _ptr(gz), _ptr(gt), _ptr(g_pq), _ptr(g_pp)
+        L.check(L.load().nlam_latent_kl_bwd(C.byref(p), _stream()), "nlam_latent_kl_bwd")
+        return (g_pq if ctx.needs_input_grad[0] else None, g_pp) + none[2:]
+
+
 def eval_metrics(pred, target, pred_std, var_std, interior_weight, kind, map_steps=(), want_mae=False, want_std=False):
     """The evaluation tensors of ``validation_step`` / ``test_step`` (models/module.py:491-504, :546-576, :607-681) in one pass
     over the rollout and a fixed-order reduction (nlam_eval_metrics): no autograd, no host synchronisation (capturable).

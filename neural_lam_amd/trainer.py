@@ -636,11 +636,16 @@ class Trainer:
         # a step recorded in the middle of an accumulation window (opt.lr was assigned): the warm-up passes write into the
         # flat gradient, which holds the window's sum so far -- it is put back behind the capture
         held = self.fp.grad.clone() if self.accumulate_grad_batches > 1 else None
+        # device counters the module's forward advances (EFMForecasterStep.replay_state: the draw count of its noise): the warm-up
+        # passes run and advance them, the recording does not -- put back, the first replay continues where an eager step would
+        counters = [(t, t.clone()) for t in getattr(self.module, "replay_state", lambda: ())()]
         try:
             self._warm_up_and_record()
         finally:
             if held is not None:
                 self.fp.grad.copy_(held)
+            for t, kept in counters:
+                t.copy_(kept)
 
     def _warm_up_and_record(self):
         side = torch.cuda.Stream()
