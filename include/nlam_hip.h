@@ -548,6 +548,22 @@ int32_t nlam_wgrad(const nlam_wgrad_t* p, void* hip_stream);
  * `partials` (nparts = nlam_wgrad_nparts of that member): the chunks of a `SplitMLPs` layer (gnn_layers.py:311-324).  Members of
  * the split-bf16 wide family with fp32 operands; NLAM_EUNSUP otherwise (launch them one by one). */
 int32_t nlam_wgrad_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream);
+/* The same for the NARROW fp32 family (plan NLAM_WGP_DMA: m and every source width <= 64 and % 4): the dW1 -- or the dW2 --
+ * launches of several small MLPs (the node MLPs on a 6 561-node mesh: one or two 32-row chunks per workgroup, 12-15 us a launch
+ * that is nearly all fixed cost) in ONE grid.  Member k runs on workgroups first[k] .. first[k] + nparts_k with the body of its
+ * own nlam_wgrad launch -- same nparts, same chunks per workgroup, same order of sums -- so its `partials` are bit-identical to
+ * that launch's, whatever the other members and their order.  Up to NLAM_MAX_GROUP members (passed by value: 8 x 120 bytes).
+ *   NLAM_EINVAL: ps NULL, n < 1, n > NLAM_MAX_GROUP, a member nlam_wgrad_plan calls invalid (NULL A / partials, n != sum of
+ *                the widths, ..), a NULL source, rows or batch < 1, or nparts != nlam_wgrad_nparts(member);
+ *   NLAM_EUNSUP: a member whose plan is not NLAM_WGP_DMA or whose shape nlam_wgrad_dma_group_supported refuses, or members that
+ *                differ in m, n, nsrc, a source width or flags.
+ * Members may differ in rows, batch, pointers, gather indices, batch strides and nparts.  On any error nothing is launched.
+ * nlam_wgrad_dma_group_supported: 1 when the SHAPE of `p` (m, source count and widths, flags; no pointer is read) is one the
+ * grouped kernel is built for -- the (32-column blocks per wave, sources) pairs (1, 1) with or without NLAM_F_SILU_B, (2, 2)
+ * and (3, 3) without --, else 0.  The alignment half of the plan (16-byte aligned A, sources and batch strides) is checked by
+ * the launch. */
+int32_t nlam_wgrad_dma_group_supported(const nlam_wgrad_t* p);
+int32_t nlam_wgrad_dma_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream);
 
 /* out[b, s, :] = scale(s) * sum_{q in [ptr[s], ptr[s+1])} in[b, order[q], :]   (order NULL = q, scale NULL = 1; `order` may name a
  * row more than once; an empty segment is written as zeros).  Which of the three fp32 kernels runs -- it decides the summation

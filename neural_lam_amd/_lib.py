@@ -162,6 +162,8 @@ EXPORTS = [
     "nlam_mlp_bwd_family",
     "nlam_mlp_bwd_group_blocks",
     "nlam_wgrad_group",
+    "nlam_wgrad_dma_group",
+    "nlam_wgrad_dma_group_supported",
     "nlam_linear",
     "nlam_linear_plan",
     "nlam_segment_sum_groups",
@@ -911,6 +913,10 @@ def load():
     lib.nlam_mlp_bwd_group_blocks.restype = i32
     lib.nlam_wgrad_group.argtypes = [C.POINTER(Wgrad), i32, vp]
     lib.nlam_wgrad_group.restype = i32
+    lib.nlam_wgrad_dma_group.argtypes = [C.POINTER(Wgrad), i32, vp]
+    lib.nlam_wgrad_dma_group.restype = i32
+    lib.nlam_wgrad_dma_group_supported.argtypes = [C.POINTER(Wgrad)]
+    lib.nlam_wgrad_dma_group_supported.restype = i32
     lib.nlam_pre_add_supported.argtypes = [C.POINTER(MlpFwd)]
     lib.nlam_pre_add_supported.restype = i32
     lib.nlam_linear.argtypes = [C.POINTER(Linear), vp]

@@ -90,6 +90,7 @@ namespace nlam_detail {   // launchers: external linkage, each defined in exactl
 int32_t fwd_narrow(const nlam_mlp_fwd_t* p, hipStream_t stream);   // slice 1
 int32_t bwd_narrow(const nlam_mlp_bwd_t* p, hipStream_t stream);   // slice 2
 int32_t wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t stream);   // slice 2 (plan: nlam_wgrad_plan's code)
+int32_t wgrad_dma_group(const nlam_wgrad_t* ps, int n, hipStream_t stream);   // slice 2 (members checked by nlam_wgrad_dma_group)
 int32_t fwd_wide(const nlam_mlp_fwd_t* p, int plan, hipStream_t stream);     // slice 3 (plan: nlam_mlp_fwd_wide_plan's code)
 int32_t bwd_wide(const nlam_mlp_bwd_t* p, int plan, hipStream_t stream);     // slice 3 (plan: nlam_mlp_bwd_wide_plan's code)
 int32_t fwd_wide_group(const nlam_mlp_fwd_t* ps, int n, hipStream_t stream);   // slice 3
@@ -2665,8 +2666,10 @@ constexpr int kWgTile = kWgradRows * 64;  // floats in one [32 rows][64 cols] LD
 // NS is the source count as a constant (descriptors, column offsets and validity then live in
 // registers, computed once); NS = 0 takes it from the argument (R = 1 only): every (NBW, NS) pair that
 // has no instantiation of its own.
+// The body takes its place in the launch as arguments (workgroup `wg_id` of the `wg_count` that share the problem): the plain
+// kernel passes blockIdx.x / gridDim.x, the grouped kernel (nlam_wgrad_dma_group) the position inside the member's own range.
 template <int NBW, bool SILU, int NS, int R>
-__global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgrad_t p) {
+__device__ __forceinline__ void wgrad_dma_body(const nlam_wgrad_t& p, const int wg_id, const int wg_count) {
     static_assert(NS >= 0 && NS <= NLAM_MAX_SRC && R >= 1 && (NS > 0 || R == 1), "run-time source count: one chunk per interval");
     constexpr int MS = NS > 0 ? NS : NLAM_MAX_SRC;   // sources the unrolled loops cover
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -2755,7 +2758,7 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgr
     float* const lds_row = smem + (size_t)(wave * 8) * 64;   // this wave's eight rows of tile 0, slot 0, stage 0
 
     // The sequence as (batch item, chunk inside it) cursors that advance by g chunks: no division in the loop.
-    const int g = (int)gridDim.x, c0 = xcd_slot((int)blockIdx.x, g);   // chunk c -> slot c % g: the rows an XCD gathers stay in an eighth of the tables
+    const int g = wg_count, c0 = xcd_slot(wg_id, g);   // chunk c -> slot c % g: the rows an XCD gathers stay in an eighth of the tables
     const int nseq = c0 < total_chunks ? (int)((total_chunks - c0 + g - 1) / g) : 0;   // chunks of this workgroup
     const int gq = g / cpb, gr = g % cpb;
     struct Cursor {
@@ -2877,7 +2880,7 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgr
         buf ^= 1;
     }
     // ---- write this workgroup's partial (m x n) ----
-    float* P = p.partials + (size_t)blockIdx.x * p.m * p.n;
+    float* P = p.partials + (size_t)wg_id * p.m * p.n;
 #pragma unroll
     for (int q = 0; q < NBW; ++q) {
         if (blk_mb[q] >= 0) {
@@ -2889,6 +2892,31 @@ __global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgr
             }
         }
     }
+}
+
+template <int NBW, bool SILU, int NS, int R>
+__global__ __launch_bounds__(kWgradThreads) void wgrad_dma_kernel(const nlam_wgrad_t p) {
+    wgrad_dma_body<NBW, SILU, NS, R>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Grouped launch (nlam_wgrad_dma_group): the dW1 (or the dW2) launches of several small MLPs of one shape in ONE grid.  At 6 561
+// rows a member is 206 chunks on 128 workgroups -- one or two chunks each, 12-15 us of which nearly all is the launch's fixed cost
+// (wave start, index -> row -> barrier round trip, partial store); five members are 640 workgroups of 48 KB of LDS, all resident
+// at once.  Member k owns workgroups first[k] .. first[k + 1): inside that range the body runs exactly as in a launch of its
+// own (same nparts, same chunk sequence per workgroup, same order of sums): the partials are bit-identical.
+struct wgrad_dma_group_t {
+    nlam_wgrad_t g[NLAM_MAX_GROUP];
+    int n;
+    int first[NLAM_MAX_GROUP + 1];   // first workgroup (blockIdx.x) of each member; first[n] = gridDim.x
+};
+static_assert(sizeof(wgrad_dma_group_t) <= 4096, "wgrad_dma_group_t is passed by value: it must fit the kernel-argument segment");
+template <int NBW, bool SILU, int NS, int R>
+__global__ __launch_bounds__(kWgradThreads) void wgrad_dma_group_kernel(const wgrad_dma_group_t G) {
+    int gi = 0;   // wave-uniform (blockIdx.x and kernel arguments only), before any load of the member's operands
+#pragma unroll
+    for (int k = 1; k < NLAM_MAX_GROUP; ++k)
+        if (k < G.n && (int)blockIdx.x >= G.first[k]) gi = k;
+    wgrad_dma_body<NBW, SILU, NS, R>(G.g[gi], (int)blockIdx.x - G.first[gi], G.first[gi + 1] - G.first[gi]);
 }
 
 // Generic widths: element-wise staging (small / odd shapes only).
@@ -5405,6 +5433,23 @@ int wgrad_plan_of(const nlam_wgrad_t* p, int ldma) {
     return big ? NLAM_WGP_WBF_BIG : NLAM_WGP_WBF;
 }
 
+// The shapes nlam_wgrad_dma_group has a kernel for: the (blocks per wave, sources) pairs of the models, which wgrad_narrow runs
+// with the source count as a constant -- dW2 (1, 1) with or without SiLU, the two- and three-source dW1 at full width (2, 2) /
+// (3, 3).  Shape only: no pointer is looked at.  -> the source count, 0 = no such kernel.
+int wgrad_dma_group_ns(const nlam_wgrad_t* p) {
+    if (p == nullptr || p->nsrc < 1 || p->nsrc > NLAM_MAX_SRC || p->m < 1) return 0;
+    if ((p->flags & (NLAM_F_A_BF16 | NLAM_F_S_BF16)) != 0) return 0;   // bf16 operands are read by the split-bf16 wide family only
+    int n = 0, nb_total = 0;
+    for (int s = 0; s < p->nsrc; ++s) {
+        n += p->src[s].width;
+        nb_total += (p->src[s].width + 31) / 32;
+    }
+    if (n != p->n || wgrad_is_smalln(p) || wgrad_is_wide(p) || !wgrad_is_narrow_dma(p)) return 0;
+    const int nbw = (((p->m + 31) / 32) * nb_total + 3) / 4;
+    const bool silu = (p->flags & NLAM_F_SILU_B) != 0;
+    return nbw == p->nsrc && (!silu || p->nsrc == 1) ? p->nsrc : 0;
+}
+
 // workgroups of a grouped launch: kMaxGridBlocks dealt in proportion to the members' tiles, at least one each and never
 // more than a member has tiles
 void group_blocks(const long* tiles, int n, int* blocks) {
@@ -6576,6 +6621,30 @@ int32_t nlam_wgrad_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream) {
     return nlam_detail::wgrad_wbf_group(ps, n, (hipStream_t)hip_stream);
 }
 
+int32_t nlam_wgrad_dma_group_supported(const nlam_wgrad_t* p) { return wgrad_dma_group_ns(p) > 0 ? 1 : 0; }
+
+// The same for the narrow fp32 family (wgrad_dma_kernel): n <= NLAM_MAX_GROUP members of ONE of its model shapes, each computed
+// exactly as by its own nlam_wgrad launch.  Every member is checked before anything is launched.
+int32_t nlam_wgrad_dma_group(const nlam_wgrad_t* ps, int32_t n, void* hip_stream) {
+    NLAM_RANGE("nlam_wgrad_dma_group");
+    if (ps == nullptr || n < 1 || n > NLAM_MAX_GROUP) return NLAM_EINVAL;
+    for (int k = 0; k < n; ++k) {   // bad arguments first: an unsupported member elsewhere in the list does not hide them
+        const nlam_wgrad_t* p = &ps[k];
+        if (wgrad_plan_of(p, nlam_detail::wgrad_ldma) == NLAM_EINVAL || p->batch < 1 || p->rows < 1) return NLAM_EINVAL;
+        if (p->nparts != nlam_wgrad_nparts(p)) return NLAM_EINVAL;
+        for (int s = 0; s < p->nsrc; ++s)
+            if (p->src[s].ptr == nullptr) return NLAM_EINVAL;
+    }
+    for (int k = 0; k < n; ++k) {
+        const nlam_wgrad_t* p = &ps[k];
+        if (wgrad_plan_of(p, nlam_detail::wgrad_ldma) != NLAM_WGP_DMA || wgrad_dma_group_ns(p) == 0) return NLAM_EUNSUP;
+        if (p->m != ps[0].m || p->n != ps[0].n || p->nsrc != ps[0].nsrc || p->flags != ps[0].flags) return NLAM_EUNSUP;
+        for (int s = 0; s < p->nsrc; ++s)
+            if (p->src[s].width != ps[0].src[s].width) return NLAM_EUNSUP;
+    }
+    return nlam_detail::wgrad_dma_group(ps, n, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"
 #endif
 
@@ -6731,6 +6800,28 @@ int32_t nlam_detail::wgrad_narrow(const nlam_wgrad_t* p, int plan, hipStream_t s
     return pick<1, 2, 3>(nbw < 1 ? 1 : (nbw > 3 ? 3 : nbw), [&](auto nb) {
         return launch<wgrad_kernel<nb>>(grid, dim3(kWgradThreads), lds, stream, *p);
     });
+}
+
+// members checked by nlam_wgrad_dma_group: plan NLAM_WGP_DMA, one of the (1, 1) / (2, 2) / (3, 3) shapes, the same for all.
+// One chunk per barrier interval (R = 1) whatever NLAM_TUNE_WGRAD_DMA_R says: a member has one or two chunks per workgroup, and
+// the partials do not depend on R.
+int32_t nlam_detail::wgrad_dma_group(const nlam_wgrad_t* ps, int n, hipStream_t stream) {
+    wgrad_dma_group_t G;
+    int parts[NLAM_MAX_GROUP];
+    for (int k = 0; k < n; ++k) {
+        G.g[k] = ps[k];
+        parts[k] = ps[k].nparts;
+    }
+    for (int k = n; k < NLAM_MAX_GROUP; ++k) G.g[k] = ps[0];   // never selected (first[k] = grid size): defined bytes for the argument copy
+    group_prefix(G, n, parts);
+    const int ns = ps[0].nsrc;
+    const dim3 grid(G.first[n]), block(kWgradThreads);
+    const size_t lds = (size_t)2 * (1 + ns) * kWgTile * sizeof(float);   // two stages of (1 + sources) tiles
+    if (ns == 1)
+        return pick_bool((ps[0].flags & NLAM_F_SILU_B) != 0,
+                         [&](auto sl) { return launch<wgrad_dma_group_kernel<1, sl, 1, 1>>(grid, block, lds, stream, G); });
+    if (ns == 2) return launch<wgrad_dma_group_kernel<2, false, 2, 1>>(grid, block, lds, stream, G);
+    return launch<wgrad_dma_group_kernel<3, false, 3, 1>>(grid, block, lds, stream, G);
 }
 #endif
 

@@ -400,6 +400,7 @@ class _WgradOverlap:
         self.keep = []
         self.deferred = deferred
         self.capturing = torch.cuda.is_current_stream_capturing()
+        WGRAD_BATCH.reset()
 
     deferred = None
 
@@ -450,6 +451,15 @@ class _WgradOverlap:
             fn()
 
     def end(self):
+        # the small weight gradients still waiting for company (WGRAD_BATCH) leave now: behind this point every gradient is
+        # enqueued -- or, for a backward that failed (no longer active), dropped with the rest of its side work
+        if self.active:
+            try:
+                WGRAD_BATCH.flush()
+            except BaseException:
+                self.deferred, self.keep, self.active = None, [], False
+                raise
+        WGRAD_BATCH.reset()
         if self.deferred is not None:
             d, self.deferred = self.deferred, None
             try:
@@ -861,14 +871,168 @@ def _mlp_reduce_jobs(batch, part1, part2, vecp, nblk, vs, vec_rows, dims, params
 def _wgrad_request(A, m, n, B, rows, src_list, flags, dev):
     """-> (nlam_wgrad_t, partials) of dW (m, n) = A^T [sources]: ``A`` the (B * rows, m) row gradients, ``src_list`` entries
     (tensor | address, bstride, width, index tensor | address | None); ``partials`` (nparts, m, n) is what the launch writes."""
+    q, nparts = _wgrad_describe(A, m, n, B, rows, src_list, flags)
+    partials = torch.empty((nparts, m, n), device=dev, dtype=torch.float32)
+    q.partials, q.nparts = _ptr(partials), nparts
+    return q, partials
+
+
+def _wgrad_describe(A, m, n, B, rows, src_list, flags):
+    """-> (nlam_wgrad_t without its partials, nparts): what _wgrad_request launches, for questions about the launch's shape."""
     q = L.Wgrad()
     q.A, q.m, q.batch, q.rows, q.nsrc, q.flags, q.n = _ptr(A), m, B, rows, len(src_list), flags, n
     for k, (t, bstride, w, idx) in enumerate(src_list):
         _fill_src(q.src[k], t, bstride, w, idx)
-    nparts = L.load().nlam_wgrad_nparts(C.byref(q))
-    partials = torch.empty((nparts, m, n), device=dev, dtype=torch.float32)
-    q.partials, q.nparts = _ptr(partials), nparts
-    return q, partials
+    return q, L.load().nlam_wgrad_nparts(C.byref(q))
+
+
+# ---- small narrow weight gradients, collected and launched together (DESIGN.md 4.3) ----
+# The node MLPs on the mesh (6 561 rows at cfg2) fork three launches each -- dW1, dW2, the reduction -- of which nearly all is
+# fixed cost: one or two 32-row chunks per workgroup.  _WgradBatch collects such MLPs as backward meets them and launches K of
+# them as ONE dW1 grid, ONE dW2 grid (nlam_wgrad_dma_group: members of one kernel shape, each computed as by its own launch) and
+# ONE reduction.  Per member nothing changes -- nparts, chunks per workgroup, order of sums, order of the accumulations into one
+# .grad -- so the gradients are the same bits.
+
+WGRAD_BATCH_K = int(os.environ.get("NLAM_WGRAD_BATCH", "5"))   # members per flush; 0 = off (every MLP launches its own three)
+# "small" = at most this many 32-row chunks per workgroup of the launch: where the fixed cost dominates (for measuring: 0 defers nothing)
+WGRAD_BATCH_CHUNKS = int(os.environ.get("NLAM_WGRAD_BATCH_CHUNKS", "2"))
+
+
+def wgrad_is_small(rows: int, batch: int, nparts: int, chunks_per_wg: int | None = None) -> bool:
+    """A weight gradient over (batch, rows) rows on ``nparts`` workgroups is small when no workgroup sums more than
+    ``chunks_per_wg`` (default WGRAD_BATCH_CHUNKS = 2) chunks of 32 rows: 6 561 rows are 206 chunks on 128 workgroups (yes), 57 616
+    rows 1 801 on 226 (no)."""
+    per = WGRAD_BATCH_CHUNKS if chunks_per_wg is None else chunks_per_wg
+    return batch * ((rows + 31) // 32) <= per * nparts
+
+
+def wgrad_batch_policy(pending_owners, pending_jobs: int, owner, njobs: int, k: int, cap: int | None = None, max_jobs: int | None = None):
+    """When the collector flushes around the arrival of one MLP -> (flush before adding it, flush after adding it).
+    ``pending_owners``: the owners (ids of the first weight) waiting, ``pending_jobs`` their reduction jobs; the arrival brings
+    ``njobs``.  Before: its owner is already waiting (a rollout, gradient accumulation: two jobs adding into one .grad in one
+    reduction launch would race, and the order of the sums per parameter is the order of back-propagation), or the grouped entry
+    point's member cap / the reduction launch's job cap would be exceeded.  After: ``k`` members wait."""
+    cap = L.NLAM_MAX_GROUP if cap is None else cap
+    max_jobs = L.NLAM_MAX_REDUCE_JOBS if max_jobs is None else max_jobs
+    before = len(pending_owners) > 0 and (owner in pending_owners or len(pending_owners) + 1 > cap or pending_jobs + njobs > max_jobs)
+    waiting = (0 if before else len(pending_owners)) + 1
+    return before, waiting >= min(max(k, 1), cap)
+
+
+@dataclass
+class _WgradMember:
+    """One deferred MLP: what its three launches are made from (every tensor stays referenced here until the flush)."""
+
+    owner: object
+    B: int
+    rows: int
+    dims: tuple          # (hid, kin, dout)
+    req1: tuple          # _wgrad_request arguments (A, m, n, src_list, flags) of dW1
+    req2: tuple          # ... of dW2
+    vecp: torch.Tensor
+    nblk: int
+    vs: int
+    params: tuple
+    needs: list
+    has_ln: bool
+    ncols: int
+    njobs: int
+
+    def tensors(self):
+        out = [self.vecp]
+        for A, _m, _n, src_list, _f in (self.req1, self.req2):
+            out.append(A)
+            out.extend(t for (t, _b, _w, _i) in src_list if isinstance(t, torch.Tensor))
+        return out
+
+
+class _WgradBatch:
+    """The collector.  ``add`` is called from a fused MLP's backward in place of its fork; a flush is ONE OVERLAP.run closure.
+    Every flush runs on one side stream (the collector is the closures' owner), so the accumulations into a parameter that is
+    deferred more than once per step -- a rollout -- stay in the order of back-propagation."""
+
+    def __init__(self):
+        self.members = []
+        self.seen = set()   # owners deferred since OVERLAP.begin(): their later launches of this step stay on the collector's stream
+
+    def reset(self):
+        self.members, self.seen = [], set()
+
+    def enabled(self) -> bool:
+        return WGRAD_BATCH_K > 0 and WGRAD_BATCH_CHUNKS > 0
+
+    def wants(self, B, rows, req1, req2) -> bool:
+        """Both launches are shapes the grouped entry point has, and small."""
+        lib = L.load()
+        for A, m, n, src_list, flags in (req1, req2):
+            q, nparts = _wgrad_describe(A, m, n, B, rows, src_list, flags)
+            if not lib.nlam_wgrad_dma_group_supported(C.byref(q)) or not wgrad_is_small(rows, B, nparts):
+                return False
+        return True
+
+    def add(self, mem: _WgradMember):
+        before, after = wgrad_batch_policy({id(m.owner) for m in self.members}, sum(m.njobs for m in self.members), id(mem.owner), mem.njobs, WGRAD_BATCH_K)
+        if before:
+            self.flush()
+        self.members.append(mem)
+        self.seen.add(id(mem.owner))
+        if after:
+            self.flush()
+
+    def flush(self):
+        members, self.members = self.members, []
+        if members:
+            OVERLAP.run(self, tuple(t for m in members for t in m.tensors()), lambda: _wgrad_batch_launch(members))
+
+
+WGRAD_BATCH = _WgradBatch()
+
+
+def _wgrad_batch_launch(members):
+    """The launches of one flush, on the current (side) stream: per kernel shape one grouped launch (a shape with one member: its
+    own nlam_wgrad), then the members' reductions in arrival order in one nlam_reduce_jobs launch, then the completion reports."""
+    lib = L.load()
+    dev = members[0].vecp.device
+    parts, classes = [], {}
+    for mem in members:
+        got = []
+        for A, m, n, src_list, flags in (mem.req1, mem.req2):
+            q, partials = _wgrad_request(A, m, n, mem.B, mem.rows, src_list, flags, dev)
+            key = (m, n, flags, tuple(w for (_t, _b, w, _i) in src_list))
+            classes.setdefault(key, []).append((q, A, src_list, partials))
+            got.append(partials)
+        parts.append(got)
+    for (m, n, _flags, _widths), reqs in classes.items():
+        for g0 in range(0, len(reqs), L.NLAM_MAX_GROUP):
+            grp = reqs[g0 : g0 + L.NLAM_MAX_GROUP]
+            rc = -2
+            if len(grp) > 1:
+                arr = (L.Wgrad * len(grp))(*[r[0] for r in grp])
+                rows_all = sum(int(r[0].rows) * int(r[0].batch) for r in grp)
+
+                def meta(grp=grp, rows_all=rows_all, m=m, n=n):
+                    nbytes = sum(A.numel() * 4 + p_.numel() * 4 + sum(t.shape[-2] * w * 4 for (t, _b, w, _i) in sl if isinstance(t, torch.Tensor))
+                                 for (_q, A, sl, p_) in grp)
+                    return {"flops": 2.0 * rows_all * m * n, "bytes": float(nbytes), "bytes_min": float(nbytes - sum(r[3].numel() * 4 for r in grp) + len(grp) * m * n * 4),
+                            "mm": "f32", "mfmas_per_block": 0, "what": "weight gradients dW = A^T [gathered B] of several small MLPs in one grid"}
+
+                rc = PROFILE.launch(("wgrad_dma_group", rows_all, len(grp), m, n), lambda: lib.nlam_wgrad_dma_group(arr, len(grp), _stream()), meta)
+            if rc == -2:   # one member, or operands the DMA kernel cannot fetch (alignment): each on its own
+                for r in grp:
+                    L.check(PROFILE.launch(("wgrad", int(r[0].rows) * int(r[0].batch), m, n), lambda r=r: lib.nlam_wgrad(C.byref(r[0]), _stream())), "nlam_wgrad")
+            else:
+                L.check(rc, "nlam_wgrad_dma_group")
+    batch = _ReduceBatch(dev)
+    done = []
+    for mem, (part1, part2) in zip(members, parts):
+        batch.reserve(mem.njobs)
+        _mlp_reduce_jobs(batch, part1, part2, mem.vecp, mem.nblk, mem.vs, 4, mem.dims, mem.params, mem.needs, mem.has_ln, ncols=mem.ncols)
+        done.append([q for q, nd in zip(mem.params, mem.needs) if nd and q is not None and _direct_grad(q, q.shape)])
+    batch.flush()
+    OVERLAP.hold(torch.cuda.current_stream(), *[p_ for got in parts for p_ in got])
+    if GRAD_LISTENER is not None:   # inside the side-stream context, as for an MLP that launches its own
+        for d in done:
+            GRAD_LISTENER.note_done(d)
 
 
 @dataclass
@@ -1324,10 +1488,28 @@ def _fused_mlp_backward(ctx, g_out, g_aggr, needs):
     # Where the launches go: weight gradients (needed only by the optimizer) on a side stream when the trainer owns the
     # parameter gradients (see _WgradOverlap); an MLP none of whose inputs needs a gradient is a dead end of backward, so
     # its data-gradient kernel goes there as well.
-    if whole_side:
-        OVERLAP.run(prm[0], (g_out, g_aggr, xhat, rstd, wpack, dz1, dz2, vecp, z1, *bases), lambda: (launch_data(), launch_weights()), dead_end=True)
+    # Small weight gradients of the narrow family wait in WGRAD_BATCH for their like and leave together (grouped launches).  An
+    # MLP that was deferred earlier in this step keeps the collector's stream for whatever else it launches: the accumulations
+    # into its .grad stay ordered.
+    side_owner, handed_over = prm[0], False
+    if on_side and WGRAD_BATCH.enabled():
+        req1 = (dz1, hid, kin1, src_list, ctx.mm_flags | _wgrad_solo())
+        req2 = (dz2, dpad, hid, [(z1, rows * hid, hid, None)], L.F_SILU_B | ctx.mm_flags | _wgrad_solo())
+        if (not whole_side and not sbf and needs[1] and needs[3] and id(prm[0]) not in OVERLAP.assigned
+                and WGRAD_BATCH.wants(B, rows, req1, req2)):
+            njobs = 2 + sum(1 for x in (pneeds[1], pneeds[3], ctx.has_ln and pneeds[4], ctx.has_ln and pneeds[5]) if x)
+            WGRAD_BATCH.add(_WgradMember(prm[0], B, rows, (hid, kin, dout), req1, req2, vecp, nblk, vs, prm, pneeds, ctx.has_ln,
+                                         kin1 if pre else 0, njobs))
+            handed_over = True   # nothing is launched here
+        elif id(prm[0]) in WGRAD_BATCH.seen:
+            WGRAD_BATCH.flush()
+            side_owner = WGRAD_BATCH
+    if handed_over:
+        pass
+    elif whole_side:
+        OVERLAP.run(side_owner, (g_out, g_aggr, xhat, rstd, wpack, dz1, dz2, vecp, z1, *bases), lambda: (launch_data(), launch_weights()), dead_end=True)
     elif on_side:
-        OVERLAP.run(prm[0], (dz1, dz2, vecp, z1, *bases), launch_weights)
+        OVERLAP.run(side_owner, (dz1, dz2, vecp, z1, *bases), launch_weights)
     else:
         launch_weights()
     dW1, db1, dW2, db2, dg, dbt = results
