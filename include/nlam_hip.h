@@ -62,6 +62,10 @@
  *   nlam_latent_kl_fwd, nlam_latent_kl_bwd, nlam_latent_kl_workspace_floats
  *       the variational training objective of Graph-EFM: the reparameterised posterior draw from that generator and the KL
  *       divergence from the prior as one pass with a fixed-order reduction, and its elementwise backward.
+ *   nlam_latent_draw_fwd, nlam_latent_draw_bwd, nlam_crps_ens_fwd, nlam_crps_ens_bwd, nlam_crps_ens_workspace_floats
+ *       the ensemble CRPS fine-tuning term of Graph-EFM: the reparameterised draw from the prior with its gradient, and the
+ *       unbiased ensemble CRPS of the members rolled out from it as one pass with a fixed-order reduction; both backwards
+ *       elementwise.
  *   nlam_window_moments, nlam_moments_workspace_doubles
  *       the per-sample means and second moments of npyfilesmeps/compute_standardization_stats.py (values and
  *       standardized one-step differences), read in place from the resident series of the data path.
@@ -1150,6 +1154,79 @@ int32_t nlam_latent_kl_fwd(const nlam_latent_kl_t* p, void* hip_stream);
 int32_t nlam_latent_kl_bwd(const nlam_latent_kl_t* p, void* hip_stream);
 /* floats of nlam_latent_kl_t.workspace: one per workgroup; NLAM_EINVAL for sizes < 1 */
 int64_t nlam_latent_kl_workspace_floats(int32_t batch, int32_t rows, int32_t latent_dim);
+
+/* The ensemble CRPS fine-tuning term of the Graph-EFM training schedule (Oskarsson et al. 2024, section 3: L_Var + lambda_CRPS
+ * L_CRPS; models.EFMForecasterStep(crps_members = M)) inside the recorded training step.
+ *
+ * The prior draw with a gradient.  params (batch, rows, P): P = D = latent_dim with diagonal = 0 (std 1), P = 2 D with
+ * diagonal = 1 (std = 1e-4 + softplus(params[.., D:])), as nlam_latent_sample reads them; per element e < rows * D of item b:
+ *   nlam_latent_draw_fwd      latent[b][e] = mean + std eps,   eps[b][e] = eps
+ *                             noise_in == NULL: eps is element e % 4 of the Philox counter (e / 4, t, b, low word of *draw)
+ *                             under *seed (the generator, the Box-Muller pairs and the quad layout of nlam_latent_kl_fwd; the
+ *                             caller keeps the keys of the two apart); *draw is only read.  noise_in given: eps = noise_in[b][e].
+ *   nlam_latent_draw_bwd      elementwise, from params and the eps the forward wrote, g = g_latent[b][e]:
+ *                               g_params[.., :D] = g
+ *                               g_params[.., D:] = g eps softplus'(params[.., D:])          diagonal = 1
+ *                             g_params == NULL (a constant prior): nothing is launched.  softplus and its derivative are those
+ *                             of the step tails (beta 1, threshold 20, derivative 1 above).
+ * Both: 16-byte accesses where the buffers involved are 16-byte aligned (the parameter matrices also need D % 4 == 0), single
+ * elements otherwise.  NLAM_EINVAL for null required pointers (fwd: params, eps, latent, and seed and draw when noise_in == NULL;
+ * bwd: params, eps, g_latent), sizes < 1, diagonal outside {0, 1}, t < 0; NLAM_EUNSUP for batch > 65535 or rows * latent_dim >= 2^31.
+ *
+ * The term.  pred (batch * members, nodes, nvars): item b * M + m is member m of batch item b (the member-minor layout of
+ * nlam_ens_scores); target (batch, nodes, nvars).  With M = members, x_m the members and y the target of one element, w_n =
+ * row_weight[n], c_f = var_weight[f] (1 for var_weight == NULL):
+ *   nlam_crps_ens_fwd         crps[b] = sum_n,f (w_n c_f) [ 1/M sum_m |x_m - y|  -  1/(M (M - 1)) sum_{i<j} |x_i - x_j| ]
+ *                             term    = *weight * sum_b crps[b]
+ *                             (the bracket is ens_abs - ens_pair of nlam_ens_scores per element: the fair / unbiased ensemble
+ *                             CRPS; M = 2 is the paper's estimator).  One thread per quad of four consecutive elements of an
+ *                             item, the members in registers; per-workgroup partial sums in the workspace and one finishing
+ *                             workgroup that adds them in a fixed order (an item's partials in block order, then the items):
+ *                             no floating-point atomics, bit-identical from run to run.  A zero row weight is a weight like any
+ *                             other.
+ *   nlam_crps_ens_bwd         elementwise, recomputed from pred and target; g = (*g_term * *weight) (w_n c_f):
+ *                               g_pred[b M + m][n][f] = g ( sgn(x_m - y) / M  -  1/(M (M - 1)) sum_{j != m} sgn(x_m - x_j) )
+ *                             sgn(a - b) = (a > b) - (a < b), by comparison: a tie gives exactly 0 (the subgradient torch.abs
+ *                             takes) and the sign sums are exact integers.
+ * Both: 16-byte accesses where pred, target (and g_pred) are 16-byte aligned and nodes * nvars % 4 == 0, single elements
+ * otherwise; var_weight is staged in LDS.  NLAM_EINVAL for null required pointers (fwd: pred, target, row_weight, weight, crps,
+ * term, workspace; bwd: pred, target, row_weight, weight, g_term, g_pred), sizes < 1, members < 2, a short workspace; NLAM_EUNSUP
+ * for members > NLAM_CRPS_MAX_MEMBERS, batch > 65535, nvars > NLAM_LOSS_MAX_VARS, nodes * nvars >= 2^31.
+ * All four: every check before any launch; no allocation, no host synchronisation. */
+#define NLAM_CRPS_MAX_MEMBERS 16
+typedef struct {
+    const float* params;       /* (batch, rows, P) */
+    const float* noise_in;     /* (batch, rows, latent_dim) or NULL: draw */
+    const uint64_t* seed;      /* device (1): required when noise_in == NULL; the 64 bits of the key */
+    const int64_t* draw;       /* device (1): required when noise_in == NULL; only read */
+    float* eps;                /* (batch, rows, latent_dim): written by fwd, read by bwd */
+    float* latent;             /* fwd: (batch, rows, latent_dim) */
+    const float* g_latent;     /* bwd: (batch, rows, latent_dim) */
+    float* g_params;           /* bwd: (batch, rows, P) or NULL */
+    int32_t batch, rows, latent_dim, diagonal;
+    int32_t t, _pad;           /* t: the AR step, word 1 of the counter */
+} nlam_latent_draw_t;
+int32_t nlam_latent_draw_fwd(const nlam_latent_draw_t* p, void* hip_stream);
+int32_t nlam_latent_draw_bwd(const nlam_latent_draw_t* p, void* hip_stream);
+typedef struct {
+    const float* pred;         /* (batch * members, nodes, nvars) */
+    const float* target;       /* (batch, nodes, nvars) */
+    const float* row_weight;   /* (nodes) */
+    const float* var_weight;   /* (nvars) or NULL: ones */
+    const float* weight;       /* device (1) */
+    float* crps;               /* fwd: (batch), unweighted */
+    float* term;               /* fwd: device (1) */
+    float* workspace;          /* fwd: nlam_crps_ens_workspace_floats(batch, members, nodes, nvars) floats */
+    int64_t workspace_floats;
+    const float* g_term;       /* bwd: device (1) */
+    float* g_pred;             /* bwd: (batch * members, nodes, nvars) */
+    int32_t batch, members, nodes, nvars;
+} nlam_crps_ens_t;
+int32_t nlam_crps_ens_fwd(const nlam_crps_ens_t* p, void* hip_stream);
+int32_t nlam_crps_ens_bwd(const nlam_crps_ens_t* p, void* hip_stream);
+/* floats of nlam_crps_ens_t.workspace: one per workgroup; NLAM_EINVAL for sizes < 1 or members < 2, NLAM_EUNSUP for members >
+ * NLAM_CRPS_MAX_MEMBERS, nvars > NLAM_LOSS_MAX_VARS or nodes * nvars >= 2^31 */
+int64_t nlam_crps_ens_workspace_floats(int32_t batch, int32_t members, int32_t nodes, int32_t nvars);
 
 /* The same batch launch over STRIDED series: forecast-type and ensemble datastores (weather_dataset.py:135-200, :235-254,
  * :303-342, :399-418).  Element (sample s, member m, step j) of a series -- one contiguous (nodes x d) block -- sits at

@@ -204,6 +204,11 @@ EXPORTS = [
     "nlam_latent_kl_fwd",
     "nlam_latent_kl_bwd",
     "nlam_latent_kl_workspace_floats",
+    "nlam_latent_draw_fwd",
+    "nlam_latent_draw_bwd",
+    "nlam_crps_ens_fwd",
+    "nlam_crps_ens_bwd",
+    "nlam_crps_ens_workspace_floats",
 ]
 
 
@@ -507,6 +512,52 @@ class LatentKl(C.Structure):
         ("t", C.c_int32),
         ("_pad", C.c_int32),
     ]
+
+
+class LatentDraw(C.Structure):
+    """nlam_latent_draw_t: the prior draw of one AR step of the member rollout, with its gradient."""
+
+    _fields_ = [
+        ("params", C.c_void_p),
+        ("noise_in", C.c_void_p),
+        ("seed", C.c_void_p),
+        ("draw", C.c_void_p),
+        ("eps", C.c_void_p),
+        ("latent", C.c_void_p),
+        ("g_latent", C.c_void_p),
+        ("g_params", C.c_void_p),
+        ("batch", C.c_int32),
+        ("rows", C.c_int32),
+        ("latent_dim", C.c_int32),
+        ("diagonal", C.c_int32),
+        ("t", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class CrpsEns(C.Structure):
+    """nlam_crps_ens_t: the unbiased ensemble CRPS of one AR step of the member rollout."""
+
+    _fields_ = [
+        ("pred", C.c_void_p),
+        ("target", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("var_weight", C.c_void_p),
+        ("weight", C.c_void_p),
+        ("crps", C.c_void_p),
+        ("term", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("g_term", C.c_void_p),
+        ("g_pred", C.c_void_p),
+        ("batch", C.c_int32),
+        ("members", C.c_int32),
+        ("nodes", C.c_int32),
+        ("nvars", C.c_int32),
+    ]
+
+
+CRPS_MAX_MEMBERS = 16   # NLAM_CRPS_MAX_MEMBERS
 
 
 class WindowEns(C.Structure):
@@ -879,6 +930,12 @@ def load():
     lib.nlam_latent_kl_bwd.restype = i32
     lib.nlam_latent_kl_workspace_floats.argtypes = [i32, i32, i32]
     lib.nlam_latent_kl_workspace_floats.restype = i64
+    for name, struct in (("nlam_latent_draw_fwd", LatentDraw), ("nlam_latent_draw_bwd", LatentDraw), ("nlam_crps_ens_fwd", CrpsEns),
+                         ("nlam_crps_ens_bwd", CrpsEns)):
+        getattr(lib, name).argtypes = [C.POINTER(struct), vp]
+        getattr(lib, name).restype = i32
+    lib.nlam_crps_ens_workspace_floats.argtypes = [i32, i32, i32, i32]
+    lib.nlam_crps_ens_workspace_floats.restype = i64
     lib.nlam_window_moments.argtypes = [C.POINTER(Moments), vp]
     lib.nlam_window_moments.restype = i32
     lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]

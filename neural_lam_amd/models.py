@@ -55,6 +55,9 @@ FUSED_STATE_UPDATE = True
 import os as _os
 
 FOLD_INPUT_CAT = _os.environ.get("NLAM_FOLD_CAT", "1") == "1"
+# the ensemble CRPS term of EFMForecasterStep(crps_members=M) on ops.CrpsEnsFunction; NLAM_FUSED_CRPS=0 computes the term from torch
+# ops on the same member states (ops.crps_ens_torch: the rollout's launches stay, only the term is swapped) for A/B runs and tests
+FUSED_CRPS = _os.environ.get("NLAM_FUSED_CRPS", "1") == "1"
 # output clamping and the predicted std inside the step-tail pass (ops.StepTailExtFunction); NLAM_FUSED_CLAMPED_TAIL=0 restores the
 # torch-op tail of such models (get_clamped_new_state, softplus, the loss pass over the rollout) for A/B runs.  On: at cfg2 size
 # 1.75 against 1.80 ms per step with a predicted std, 1.72 against 2.71 ms with three clamps (profiles/clamped_tail/README.md)
@@ -1069,18 +1072,65 @@ class EFMForecaster(ARForecaster):
 
     last_kl = None
 
+    def member_crps(self, init_states, forcing_features, boundary_states, target_states, members, crps_spec, seed, draw,
+                    member_noise=None):
+        """The ensemble CRPS term of the fine-tuning stage: a rollout of ``B * members`` items on samples of the PRIOR -- item
+        ``b * members + m`` is member m of batch item b, started from that item's ``init_states`` under its forcing and boundary,
+        each member fed its own new state -- and, per AR step, the unbiased ensemble CRPS of the members' new states against the
+        target.  ``crps_spec = (var_weight (F,) | None, row_weight (N,), weight)``, ``weight`` the device float ``crps_weight / (B
+        T)``; ``seed`` / ``draw``: the device words of the member draws; ``member_noise`` (B * members, T, R, D) replaces the
+        generator.  The step tails run without a loss term (``target=None`` of ops.StepTailExtFunction); a predicted std of the
+        members is not used.  Returns (term, crps_per_item (T, B) unweighted)."""
+        from .ops import CrpsEnsFunction, LatentDrawFunction, StepTailExtFunction, crps_ens_torch
+
+        pred = self.predictor
+        M = int(members)
+        var_weight, row_weight, weight = crps_spec
+        rep = lambda x: x.repeat_interleave(M, dim=0)   # noqa: E731  member-minor: b * M + m
+        init, forcing_m, boundary_m = rep(init_states), rep(forcing_features), rep(boundary_states)
+        prev_prev_state, prev_state = init[:, 0], init[:, 1]
+        raw = (FUSED_STATE_UPDATE and init.is_cuda and init.dtype == torch.float32 and boundary_m.dtype == torch.float32
+               and pred.can_return_raw_delta())
+        bmask = self.boundary_mask.reshape(-1)
+        D = int(pred.latent_dim)
+        terms, items = [], []
+        with pred.static_cache():
+            for i in range(forcing_m.shape[1]):
+                forcing = forcing_m[:, i]
+                grid_prev_emb, graph_emb = pred.embedd_grid_and_graph(prev_state, prev_prev_state, forcing)
+                pp = pred.prior_params(grid_prev_emb, graph_emb)
+                z = LatentDrawFunction.apply(pp.float(), D, seed, draw, i, None if member_noise is None else member_noise[:, i])
+                if raw:
+                    delta, _ = pred.decode(grid_prev_emb, graph_emb, z, prev_state, raw_delta=True)
+                    new_state, _, _ = StepTailExtFunction.apply(delta.float(), prev_state, boundary_m[:, i], None, pred.diff_std,
+                                                                pred.diff_mean, bmask, None, None, 1.0, None, pred.clamp_tables())
+                else:
+                    pred_state, _ = pred.decode(grid_prev_emb, graph_emb, z, prev_state)
+                    new_state = self.boundary_mask * boundary_m[:, i] + self.interior_mask * pred_state
+                if FUSED_CRPS:
+                    term, per_item = CrpsEnsFunction.apply(new_state.float(), target_states[:, i].float(), row_weight, var_weight, weight, M)
+                else:
+                    term, per_item = crps_ens_torch(new_state.float(), target_states[:, i].float(), row_weight, var_weight, weight, M)
+                terms.append(term)
+                items.append(per_item)
+                prev_prev_state, prev_state = prev_state, new_state
+        crps = terms[0] if len(terms) == 1 else torch.stack(terms).sum()
+        return crps, torch.stack(items).detach()
+
 
 class EFMEvalResult(EvalResult):
     """What ``EFMForecasterStep.evaluate`` returns: the ``EvalResult`` of the rollout on posterior samples (``prediction``,
     ``time_step_loss`` .. as ``ForecasterStep.evaluate`` gives them, so ``evaluation.MetricAggregator`` and
     ``trainer.graphed_eval_step`` take it), and the validation ELBO ``loss`` = ``likelihood`` + ``kl`` (both weighted as in
-    training), ``kl_per_item`` (T, B) unweighted, ``pred_std`` (B, T, N, F) or None."""
+    training), ``kl_per_item`` (T, B) unweighted, ``pred_std`` (B, T, N, F) or None.  A step with ``crps_members > 0`` adds its
+    weighted ensemble CRPS term ``crps`` (from a member rollout on prior samples) to ``loss``; otherwise ``crps`` is None."""
 
-    __slots__ = ("pred_std", "loss", "likelihood", "kl", "kl_per_item")
+    __slots__ = ("pred_std", "loss", "likelihood", "kl", "kl_per_item", "crps")
 
-    def __init__(self, fields, pred_std, loss, likelihood, kl, kl_per_item):
+    def __init__(self, fields, pred_std, loss, likelihood, kl, kl_per_item, crps=None):
         super().__init__(*fields)
         self.pred_std, self.loss, self.likelihood, self.kl, self.kl_per_item = pred_std, loss, likelihood, kl, kl_per_item
+        self.crps = crps
 
 
 class EFMForecasterStep(ForecasterStep):
@@ -1104,15 +1154,38 @@ class EFMForecasterStep(ForecasterStep):
     words in place.  Ranks must not share noise: the key is ``noise_key(seed, rank) = (seed + rank * 0x9E3779B97F4A7C15) mod 2^64``
     (an odd multiplier: distinct ranks give distinct keys), ``rank`` from ``torch.distributed`` unless given.
     ``draw_state()`` / ``load_draw_state()`` carry ``{seed, draw, kl_beta}`` through ``save_checkpoint(..., extra=...)``.
-    ``last_terms``: the device scalars (likelihood, kl) of the last forward that ran, eager or replayed."""
+    ``last_terms``: the device scalars (likelihood, kl) of the last forward that ran, eager or replayed.
+
+    The fine-tuning stage (the paper's ``L_Var + lambda_CRPS L_CRPS``).  ``crps_members = M`` (2 .. 16; 0, the default, leaves the
+    step as described above, launch for launch) makes every ``forward`` run, behind the ELBO rollout, ``EFMForecaster.member_crps``:
+    M members per batch item rolled out on samples of the prior, and
+
+        loss = lik + kl + crps_weight / (B T) sum_{b,t} sum_n w_n sum_f c_f [ 1/M sum_m |x_m - y| - 1/(M (M-1)) sum_{i<j} |x_i - x_j| ]
+
+    ``w_n`` the interior weight, ``c_f = 1 / per_var_std[f]`` as ``wmae`` weights (ones with a predicted std), x_m member m's new
+    state, y the target.  ``crps_weight / (B T)`` is a device float per batch shape like ``kl_weight`` (``crps_weight_word``,
+    ``set_crps_weight``: in place, nothing recorded again; a weight of 0 still runs the members).  The members draw on the same
+    ``draw`` word under a key of their own, ``member_key(seed, rank) = (noise_key + 0xD1B54A32D192ED03) mod 2^64``, with counter
+    (quad, t, b M + m, low word of draw): posterior and member draws never share a (key, counter) pair.  ``last_crps``: the
+    weighted term of the last forward.  ``draw_state()`` then carries ``crps_weight`` too.  The member rollout keeps M times the
+    activations of the ELBO rollout alive for the backward."""
+
+    MEMBER_KEY_OFFSET = 0xD1B54A32D192ED03
 
     def __init__(self, forecaster, datastore, standardize: bool = False, state_feature_weights=None, loss: str = "nll",
-                 kl_beta: float = 1.0, seed: int = 0, rank: int | None = None):
+                 kl_beta: float = 1.0, seed: int = 0, rank: int | None = None, crps_members: int = 0, crps_weight: float = 0.0):
         if not getattr(getattr(forecaster, "predictor", None), "draws_latent", False):
             raise ValueError(f"EFMForecasterStep trains a predictor that draws a latent variable (GraphEFM, GraphEFMMultiScale), not "
                              f"{type(getattr(forecaster, 'predictor', forecaster)).__name__}: use ForecasterStep")
         if not isinstance(forecaster, EFMForecaster):
             raise ValueError("EFMForecasterStep needs an EFMForecaster over the predictor")
+        from ._lib import CRPS_MAX_MEMBERS
+
+        crps_members = int(crps_members)
+        if crps_members != 0 and not 2 <= crps_members <= CRPS_MAX_MEMBERS:
+            raise ValueError(f"EFMForecasterStep: crps_members must be 0 (no CRPS term) or 2 .. {CRPS_MAX_MEMBERS}, got {crps_members}")
+        if crps_members == 0 and float(crps_weight) != 0.0:
+            raise ValueError("EFMForecasterStep: crps_weight without crps_members: the CRPS term needs at least 2 members")
         super().__init__(forecaster, datastore, standardize=standardize, state_feature_weights=state_feature_weights, loss=loss)
         if rank is None:
             import torch.distributed as dist
@@ -1127,6 +1200,49 @@ class EFMForecasterStep(ForecasterStep):
         self.register_buffer("_terms", torch.zeros((2,), dtype=torch.float32), persistent=False)   # (likelihood, kl) of the last forward
         self._kl_words = {}   # (B, T) -> the device float kl_beta / (N_interior B T) of the steps recorded or run at that shape
         self._seed_device = None
+        self.crps_members, self.crps_weight = crps_members, float(crps_weight)
+        self._crps_words = {}   # (B, T) -> the device float crps_weight / (B T), kept as _kl_words is
+        if crps_members:
+            self.register_buffer("member_seed", torch.zeros((1,), dtype=torch.int64), persistent=False)   # the members' key
+            self.register_buffer("_crps_term", torch.zeros((), dtype=torch.float32), persistent=False)
+            self.register_buffer("crps_var_weight", None if self.per_var_std is None else 1.0 / self.per_var_std, persistent=False)
+
+    @property
+    def last_crps(self):
+        """The weighted CRPS term of the last ``forward`` that ran, eager or replayed: a device scalar of its own (None without
+        members)."""
+        return self._crps_term if self.crps_members else None
+
+    @classmethod
+    def member_key(cls, seed: int, rank: int) -> int:
+        """The Philox key of the member draws of ``rank`` under ``seed``: the posterior's key plus an odd constant."""
+        return (cls.noise_key(seed, rank) + cls.MEMBER_KEY_OFFSET) & 0xFFFFFFFFFFFFFFFF
+
+    def crps_weight_value(self, B: int, T: int) -> float:
+        """``crps_weight / (B T)``: what the host writes into the device word of that batch shape."""
+        return self.crps_weight / (B * T)
+
+    def crps_weight_word(self, B: int, T: int):
+        """The device float ``crps_weight / (B T)`` of batch shape (B, T): ``kl_weight_word``'s rules -- one word per shape, made
+        on first use outside a capture, then only written in place (``set_crps_weight``)."""
+        self.kl_weight_word(B, T)   # the device check (drops the words of another device, writes the keys), and the same error
+        word = self._crps_words.get((B, T))
+        if word is None:
+            dev = self.draw.device
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("EFMForecasterStep: the first call for a batch shape must run outside a stream capture (Trainer's "
+                                   "warm-up does): it writes that shape's crps_weight")
+            word = self._crps_words[(B, T)] = torch.full((1,), self.crps_weight_value(B, T), dtype=torch.float32, device=dev)
+        return word
+
+    def set_crps_weight(self, crps_weight: float):
+        """A new ``crps_weight``, written in place into the device word of every batch shape seen so far: no captured step is
+        recorded again.  Not between a ``forward`` and its ``backward`` (as ``set_kl_beta``)."""
+        if not self.crps_members:
+            raise ValueError("EFMForecasterStep.set_crps_weight: the step was built without crps_members")
+        self.crps_weight = float(crps_weight)
+        for (B, T), word in self._crps_words.items():
+            word.fill_(self.crps_weight_value(B, T))
 
     @property
     def last_terms(self):
@@ -1150,7 +1266,7 @@ class EFMForecasterStep(ForecasterStep):
         (``set_kl_beta``); never made inside a capture: the recorded fill would undo ``set_kl_beta`` at every replay."""
         dev = self.draw.device
         if self._seed_device != dev:   # after construction / ``.to()``: the words of another device are dropped, the key is written
-            self._kl_words = {}
+            self._kl_words, self._crps_words = {}, {}
             self._write_seed()
         word = self._kl_words.get((B, T))
         if word is None:
@@ -1163,6 +1279,9 @@ class EFMForecasterStep(ForecasterStep):
     def _write_seed(self):
         key = self.noise_key(self.seed_value, self.rank)
         self.seed.fill_(key - (1 << 64) if key >= (1 << 63) else key)   # the 64 bits, in the int64 the device word is kept as
+        if self.crps_members:
+            key = self.member_key(self.seed_value, self.rank)
+            self.member_seed.fill_(key - (1 << 64) if key >= (1 << 63) else key)
         self._seed_device = self.seed.device
 
     def set_kl_beta(self, kl_beta: float):
@@ -1176,18 +1295,23 @@ class EFMForecasterStep(ForecasterStep):
         """A new seed and draw count, written in place (no new recording): the next call draws (seed, draw + 1)."""
         self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF
         if self._seed_device != self.draw.device:
-            self._kl_words = {}
+            self._kl_words, self._crps_words = {}, {}
         self._write_seed()
         self.draw.fill_(int(draw))
 
     def draw_state(self) -> dict:
         """``{seed, draw, kl_beta}`` for ``save_checkpoint(..., extra=step.draw_state())`` (reads ``draw`` back: synchronises)."""
-        return {"seed": self.seed_value, "draw": int(self.draw.item()), "kl_beta": self.kl_beta}
+        state = {"seed": self.seed_value, "draw": int(self.draw.item()), "kl_beta": self.kl_beta}
+        if self.crps_members:
+            state["crps_weight"] = self.crps_weight
+        return state
 
     def load_draw_state(self, state: dict):
         """Continue the noise sequence of a saved run (the rank's key is folded in again here)."""
         self.reseed(int(state["seed"]), int(state["draw"]))
         self.set_kl_beta(float(state["kl_beta"]))
+        if self.crps_members and "crps_weight" in state:
+            self.set_crps_weight(float(state["crps_weight"]))
 
     def replay_state(self):
         """The device counters ``forward`` advances: ``Trainer`` puts them back behind the warm-up passes of a recording."""
@@ -1202,21 +1326,39 @@ class EFMForecasterStep(ForecasterStep):
         return self.forecaster(init_states, forcing, target_states, loss_spec=spec, kl_words=(kl_weight, self.seed, draw),
                                latent_noise=latent_noise)
 
-    def forward(self, init_states, target_states, forcing, standardize: bool | None = None, latent_noise=None):
+    def _crps(self, init_states, target_states, forcing, draw, member_noise):
+        """The weighted CRPS term of a member rollout on prior samples under ``draw`` as ``_elbo`` left it (the members share the
+        posterior's draw count and differ in the key)."""
+        B, T = target_states.shape[0], target_states.shape[1]
+        spec = (self.crps_var_weight, self.interior_weight, self.crps_weight_word(B, T))
+        crps, _ = self.forecaster.member_crps(init_states, forcing, target_states, target_states, self.crps_members, spec,
+                                              self.member_seed, draw, member_noise)
+        return crps
+
+    def forward(self, init_states, target_states, forcing, standardize: bool | None = None, latent_noise=None, member_noise=None):
+        """``member_noise`` (B * crps_members, T, R, D): standard-normal noise of the member rollout in place of the generator's.
+        Without it the members draw under ``draw`` as it stands, which only a call without ``latent_noise`` advances."""
         if standardize is None:
             standardize = self.standardize_inputs
         if standardize:
             init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
         prediction, _, lik, kl = self._elbo(init_states, target_states, forcing, self.draw, latent_noise)
         torch.stack((lik.detach().reshape(()), kl.detach().reshape(())), out=self._terms)   # one launch, recorded with the step
-        return prediction, lik + kl
+        if not self.crps_members:
+            return prediction, lik + kl
+        crps = self._crps(init_states, target_states, forcing, self.draw, member_noise)
+        self._crps_term.copy_(crps.detach().reshape(()))
+        return prediction, lik + kl + crps
 
-    def evaluate(self, init_states, target_states, forcing, phase="val", steps_to_log=(1,), standardize=None, latent_noise=None):
+    def evaluate(self, init_states, target_states, forcing, phase="val", steps_to_log=(1,), standardize=None, latent_noise=None,
+                 member_noise=None):
         """``ForecasterStep.evaluate`` for this objective: the launches of ``forward`` under ``torch.no_grad()`` -- the rollout on
         posterior samples -- then the metric pass of ``validation_step`` / ``test_step`` on its predictions.  Returns an
         ``EFMEvalResult``: the ``EvalResult`` fields plus the validation ELBO and its two terms.  It draws on a counter of its own
         (``eval_draw``, started at 2^31), so validating does not move the training run's noise sequence, and reads the
-        ``kl_weight`` word of its own batch shape.  Capturable after one eager call at that shape (trainer.graphed_eval_step)."""
+        ``kl_weight`` word of its own batch shape.  Capturable after one eager call at that shape (trainer.graphed_eval_step).
+        With ``crps_members > 0`` the member rollout runs too, on ``eval_draw`` under the members' key: ``crps`` is its weighted term
+        and ``loss`` includes it (``member_noise`` as in ``forward``)."""
         if phase not in ("val", "test"):
             raise ValueError(f"evaluate: phase must be 'val' or 'test', got {phase!r}")
         with torch.no_grad():
@@ -1226,4 +1368,7 @@ class EFMForecasterStep(ForecasterStep):
                 init_states, target_states, forcing = self.standardize(init_states, target_states, forcing)
             prediction, pred_std, lik, kl = self._elbo(init_states, target_states, forcing, self.eval_draw, latent_noise)
             fields = self._eval_fields(prediction, pred_std, target_states, phase, steps_to_log)
-            return EFMEvalResult(fields, pred_std, lik + kl, lik, kl, self.forecaster.last_kl)
+            if not self.crps_members:
+                return EFMEvalResult(fields, pred_std, lik + kl, lik, kl, self.forecaster.last_kl)
+            crps = self._crps(init_states, target_states, forcing, self.eval_draw, member_noise)   # the members on eval_draw too
+            return EFMEvalResult(fields, pred_std, lik + kl + crps, lik, kl, self.forecaster.last_kl, crps)

@@ -2724,6 +2724,129 @@ class LatentKLFunction(torch.autograd.Function):
         return (g_pq if ctx.needs_input_grad[0] else None, g_pp) + none[2:]
 
 
+class LatentDrawFunction(torch.autograd.Function):
+    """The prior draw of one AR step of the member rollout of the Graph-EFM CRPS term, with its gradient (nlam_latent_draw_fwd /
+    _bwd; the formulas are in include/nlam_hip.h):
+
+    forward(params (B, R, D | 2 D), latent_dim D, seed (device word: the 64 bits of the key), draw (device int64), t,
+    noise_in (B, R, D) | None) -> z (B, R, D) = mean + std eps.
+    eps is drawn on the device under (seed, draw, t) unless ``noise_in`` is given, and saved for the backward with ``params``.
+    Gradient: ``params`` when it requires one (a constant prior gets none, and nothing is launched).  No host synchronisation, no
+    allocation outside torch's allocator: the call can be captured."""
+
+    @staticmethod
+    def _args(params, D, eps, t):
+        B, R, P = params.shape
+        if P not in (D, 2 * D) or D < 1:
+            raise ValueError(f"LatentDrawFunction: prior parameters {tuple(params.shape)} for a latent of width {D}")
+        p = L.LatentDraw()
+        p.params, p.eps = _ptr(params), _ptr(eps)
+        p.batch, p.rows, p.latent_dim, p.diagonal, p.t = B, R, D, int(P == 2 * D), int(t)
+        return p
+
+    @staticmethod
+    def forward(ctx, params, latent_dim: int, seed, draw, t: int, noise_in=None):
+        _require_gpu(params, noise_in)
+        if noise_in is None and not (seed.is_cuda and draw.is_cuda and seed.dtype in (torch.uint64, torch.int64) and draw.dtype == torch.int64):
+            raise RuntimeError("LatentDrawFunction: seed (the 64 bits of the key, uint64 or int64) and draw (int64) are words in device memory")
+        params, noise_in = map(_cont, (params, noise_in))
+        B, R, D = params.shape[0], params.shape[1], int(latent_dim)
+        eps = torch.empty((B, R, D), device=params.device, dtype=torch.float32)
+        p = LatentDrawFunction._args(params, D, eps, t)
+        if noise_in is not None and noise_in.shape != eps.shape:
+            raise ValueError(f"LatentDrawFunction: noise of shape {tuple(noise_in.shape)} for a latent of shape {tuple(eps.shape)}")
+        z = torch.empty_like(eps)
+        p.noise_in, p.latent = _ptr(noise_in), _ptr(z)
+        if noise_in is None:
+            p.seed, p.draw = _ptr(seed), _ptr(draw)
+        L.check(L.load().nlam_latent_draw_fwd(C.byref(p), _stream()), "nlam_latent_draw_fwd")
+        ctx.save_for_backward(params, eps)
+        ctx.t, ctx.latent_dim = int(t), D
+        ctx.set_materialize_grads(False)
+        return z
+
+    @staticmethod
+    def backward(ctx, g_z):
+        params, eps = ctx.saved_tensors
+        if g_z is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        g_z = g_z.contiguous()
+        g_params = torch.empty_like(params)
+        p = LatentDrawFunction._args(params, ctx.latent_dim, eps, ctx.t)
+        p.g_latent, p.g_params = _ptr(g_z), _ptr(g_params)
+        L.check(L.load().nlam_latent_draw_bwd(C.byref(p), _stream()), "nlam_latent_draw_bwd")
+        return (g_params,) + (None,) * 5
+
+
+class CrpsEnsFunction(torch.autograd.Function):
+    """The unbiased ensemble CRPS of one AR step of the member rollout (nlam_crps_ens_fwd / _bwd; the formulas are in
+    include/nlam_hip.h):
+
+    forward(pred (B M, N, F), target (B, N, F), row_weight (N,), var_weight (F,) | None, weight (device float), members M) ->
+    (term scalar = weight * sum_b crps_b, crps_per_item (B,)).  Item ``b * M + m`` of ``pred`` is member m of batch item b.
+    Gradient: ``pred``, recomputed from ``pred`` and ``target`` (nothing else is saved); ``crps_per_item`` is not differentiable.
+    ``weight`` is saved for the backward, which multiplies it in again, as ``LatentKLFunction`` treats ``kl_weight``.  No host
+    synchronisation, no allocation outside torch's allocator: the call can be captured."""
+
+    @staticmethod
+    def _args(pred, target, row_weight, var_weight, weight, members):
+        BM, N, F = pred.shape
+        B = BM // members
+        if members < 2 or B * members != BM or tuple(target.shape) != (B, N, F) or row_weight.numel() != N or (
+                var_weight is not None and var_weight.numel() != F):
+            raise ValueError(f"CrpsEnsFunction: {members} members, states {tuple(pred.shape)}, target {tuple(target.shape)}")
+        p = L.CrpsEns()
+        p.pred, p.target, p.row_weight, p.var_weight, p.weight = _ptr(pred), _ptr(target), _ptr(row_weight), _ptr(var_weight), _ptr(weight)
+        p.batch, p.members, p.nodes, p.nvars = B, int(members), N, F
+        return p
+
+    @staticmethod
+    def forward(ctx, pred, target, row_weight, var_weight, weight, members: int):
+        lib = L.load()
+        _require_gpu(pred, target, row_weight, var_weight, weight)
+        pred, target, row_weight, var_weight = map(_cont, (pred, target, row_weight, var_weight))
+        p = CrpsEnsFunction._args(pred, target, row_weight, var_weight, weight, members)
+        B, dev = p.batch, pred.device
+        crps = torch.empty((B,), device=dev, dtype=torch.float32)
+        term = torch.empty((), device=dev, dtype=torch.float32)
+        nws = lib.nlam_crps_ens_workspace_floats(B, int(members), p.nodes, p.nvars)
+        if nws < 0:
+            L.check(int(nws), "nlam_crps_ens_workspace_floats")
+        ws = torch.empty((nws,), device=dev, dtype=torch.float32)
+        p.crps, p.term, p.workspace, p.workspace_floats = _ptr(crps), _ptr(term), _ptr(ws), nws
+        L.check(lib.nlam_crps_ens_fwd(C.byref(p), _stream()), "nlam_crps_ens_fwd")
+        ctx.save_for_backward(pred, target, row_weight, var_weight, weight)
+        ctx.members = int(members)
+        ctx.mark_non_differentiable(crps)
+        ctx.set_materialize_grads(False)
+        return term, crps
+
+    @staticmethod
+    def backward(ctx, g_term, _g_crps):
+        pred, target, row_weight, var_weight, weight = ctx.saved_tensors
+        if g_term is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        gt = g_term.contiguous().to(torch.float32)
+        g_pred = torch.empty_like(pred)
+        p = CrpsEnsFunction._args(pred, target, row_weight, var_weight, weight, ctx.members)
+        p.g_term, p.g_pred = _ptr(gt), _ptr(g_pred)
+        L.check(L.load().nlam_crps_ens_bwd(C.byref(p), _stream()), "nlam_crps_ens_bwd")
+        return (g_pred,) + (None,) * 5
+
+
+def crps_ens_torch(pred, target, row_weight, var_weight, weight, members: int):
+    """``CrpsEnsFunction`` composed from torch ops on the same member states (models.FUSED_CRPS off: the comparison route of the
+    tests and of tools/efm_train_bench.py).  The (B, M, M, N, F) temporary of the pair term is what the kernel avoids."""
+    BM, N, F = pred.shape
+    B, M = BM // members, int(members)
+    x = pred.reshape(B, M, N, F)
+    wc = row_weight.reshape(N, 1) * (var_weight.reshape(1, F) if var_weight is not None else 1.0)
+    skill = (x - target.unsqueeze(1)).abs().sum(1) / M
+    pair = (x.unsqueeze(1) - x.unsqueeze(2)).abs().sum((1, 2)) / (2 * M * (M - 1))   # every pair twice
+    crps = ((skill - pair) * wc).sum((1, 2))
+    return weight.reshape(()) * crps.sum(), crps.detach()
+
+
 def eval_metrics(pred, target, pred_std, var_std, interior_weight, kind, map_steps=(), want_mae=False, want_std=False):
     """The evaluation tensors of ``validation_step`` / ``test_step`` (models/module.py:491-504, :546-576, :607-681) in one pass
     over the rollout and a fixed-order reduction (nlam_eval_metrics): no autograd, no host synchronisation (capturable).

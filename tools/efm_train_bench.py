@@ -14,6 +14,14 @@ step against.  Route "fused_eager": the fused step without the recording (use_gr
 "torch" route whose recording failed (``recorded`` false: Trainer then runs it with eager launches).  Per route and rollout
 length: ms per step (HIP events around ``--steps`` synchronised steps; median over the alternating rounds and their spread), and
 whether the step really ran as a recorded graph.
+
+    python tools/efm_train_bench.py --crps-members 2 [--out profiles/efm_crps/bench.json]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o t -- python tools/efm_train_bench.py --crps-members 2 --trace crps_fused --ar-steps 1 --steps 50
+    python tools/efm_train_bench.py --crps-members 2 --parse-stats DIR/t_kernel_stats.csv --steps 50
+
+With ``--crps-members M`` the routes are those of the fine-tuning stage instead, all three recorded: "elbo" (the step without members),
+"crps_fused" (``crps_members=M``, the term on nlam_crps_ens_fwd / _bwd) and "crps_torch" (the same member rollout with
+NLAM_FUSED_CRPS=0: the term from torch ops on the same member states).
 """
 import argparse
 import csv
@@ -26,17 +34,18 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 NEW_KERNELS = ("latent_kl_fwd_kernel", "latent_kl_finish_kernel", "latent_kl_bwd_kernel")
+CRPS_KERNELS = ("latent_draw_fwd_kernel", "latent_draw_bwd_kernel", "crps_ens_fwd_kernel", "crps_ens_finish_kernel", "crps_ens_bwd_kernel")
 SETUP_KERNELS = ("spin_kernel",)   # the one-off stream-layout probe of ops._streams_share_queue: no part of a step
 
 
-def parse_stats(path, steps):
+def parse_stats(path, steps, new_kernels=NEW_KERNELS):
     """Kernels per pass and the share of the new launches from a rocprofv3 kernel_stats.csv of a ``--trace`` run of ``steps``
     steps: the run makes steps + 2 passes (the two warm-up passes of the recording run eagerly, the recording itself runs nothing).
     SETUP_KERNELS are left out; the other one-off launches of the set-up (weight initialisation, graph layouts) are not."""
     rows = [r for r in csv.DictReader(open(path)) if not any(k in r["Name"] for k in SETUP_KERNELS)]
     calls = sum(int(r["Calls"]) for r in rows)
     total = sum(float(r["TotalDurationNs"]) for r in rows)
-    new = [r for r in rows if any(k in r["Name"] for k in NEW_KERNELS)]
+    new = [r for r in rows if any(k in r["Name"] for k in new_kernels)]
     passes = steps + 2
     return {"stats_file": str(path), "passes": passes, "kernels_per_step": calls / passes, "kernel_ms_per_step": total / passes / 1e6,
             "new_launches_per_step": sum(int(r["Calls"]) for r in new) / passes,
@@ -50,12 +59,15 @@ def main():
     ap.add_argument("--ar-steps", type=int, nargs="+", default=[1, 4])
     ap.add_argument("--steps", type=int, default=30, help="steps per timed window")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--trace", choices=("fused", "fused_eager", "torch"), default=None, help="run one route for --steps steps and exit (for a kernel trace)")
+    ap.add_argument("--trace", choices=("fused", "fused_eager", "torch", "elbo", "crps_fused", "crps_torch"), default=None,
+                    help="run one route for --steps steps and exit (for a kernel trace)")
+    ap.add_argument("--crps-members", type=int, default=0, help="M > 0: time the fine-tuning stage (routes elbo, crps_fused, crps_torch)")
+    ap.add_argument("--crps-weight", type=float, default=1.0)
     ap.add_argument("--parse-stats", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.parse_stats is not None:
-        print(json.dumps(parse_stats(args.parse_stats, args.steps), indent=1))
+        print(json.dumps(parse_stats(args.parse_stats, args.steps, CRPS_KERNELS if args.crps_members else NEW_KERNELS), indent=1))
         return
 
     import torch
@@ -109,7 +121,9 @@ def main():
     def make(route, T):
         torch.manual_seed(42)
         model = graph_efm.GraphEFM(ds, graph=graph, hidden_dim=D)
-        step = hm.EFMForecasterStep(hm.EFMForecaster(model, ds), ds, seed=1).to(dev)
+        members = args.crps_members if route in ("crps_fused", "crps_torch") else 0
+        step = hm.EFMForecasterStep(hm.EFMForecaster(model, ds), ds, seed=1, crps_members=members,
+                                    crps_weight=args.crps_weight if members else 0.0).to(dev)
         module = TorchElbo(step) if route == "torch" else step
         tr = Trainer(module, lr=1e-4, use_graph=route != "fused_eager")
         g = torch.Generator().manual_seed(123)
@@ -118,11 +132,12 @@ def main():
 
         def run(n):
             hm.FUSED_STATE_UPDATE = route != "torch"
+            hm.FUSED_CRPS = route != "crps_torch"
             try:
                 for _ in range(n):
                     loss = tr.step(*batch)
             finally:
-                hm.FUSED_STATE_UPDATE = True
+                hm.FUSED_STATE_UPDATE = hm.FUSED_CRPS = True
             return loss
 
         return tr, run
@@ -146,9 +161,11 @@ def main():
         return
 
     out = {"grid": [NX, NY], "nodes": N, "state_vars": NS, "hidden_dim": D, "batch": 1, "steps": args.steps, "rounds": args.rounds,
+           "crps_members": args.crps_members,
            "source_stamp": L.source_stamp(), "device": torch.cuda.get_device_name(0), "ar_steps": {}}
     for T in args.ar_steps:
-        routes = {name: make(name, T) for name in ("fused", "fused_eager", "torch")}
+        names = ("elbo", "crps_fused", "crps_torch") if args.crps_members else ("fused", "fused_eager", "torch")
+        routes = {name: make(name, T) for name in names}
         for _, run in routes.values():
             run(3)   # warm-up passes and the recording
         ms = {name: [] for name in routes}
@@ -157,8 +174,12 @@ def main():
                 ms[name].append(window_ms(run, args.steps))
         row = {name: {"ms_per_step": statistics.median(v), "ms_per_step_rounds": v, "spread_ms": max(v) - min(v),
                       "recorded": routes[name][0].use_graph and routes[name][0]._graph is not None} for name, v in ms.items()}
-        row["torch_over_fused"] = row["torch"]["ms_per_step"] / row["fused"]["ms_per_step"]
-        row["torch_over_fused_eager"] = row["torch"]["ms_per_step"] / row["fused_eager"]["ms_per_step"]
+        if args.crps_members:
+            row["crps_torch_over_crps_fused"] = row["crps_torch"]["ms_per_step"] / row["crps_fused"]["ms_per_step"]
+            row["crps_fused_over_elbo"] = row["crps_fused"]["ms_per_step"] / row["elbo"]["ms_per_step"]
+        else:
+            row["torch_over_fused"] = row["torch"]["ms_per_step"] / row["fused"]["ms_per_step"]
+            row["torch_over_fused_eager"] = row["torch"]["ms_per_step"] / row["fused_eager"]["ms_per_step"]
         out["ar_steps"][str(T)] = row
         del routes
         torch.cuda.empty_cache()
