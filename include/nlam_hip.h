@@ -55,6 +55,9 @@
  *       a forecast of any length as replays of ONE recorded AR step: a lead counter in device memory ties the data path
  *       (this lead's forcing window and boundary truth, cut from the resident series) to the inference step tail, which
  *       rotates the state in place and writes this lead's physical fields, valid time and verification sums.
+ *   nlam_forecast_init_strided, nlam_forecast_head_strided
+ *       that data path over forecast-type and ensemble series: nlam_window_batch_ens's (sample, member, lead-time row) addressing
+ *       from a flat sample index read on the device.
  *   nlam_philox_normal_fill, nlam_latent_sample, nlam_ens_scores, nlam_ens_scores_workspace_floats
  *       sampled ensembles inside that recorded step (Graph-EFM): the reparameterised draw of the latent variable from a
  *       counter-based generator keyed by the lead counter, and the ensemble verification of every lead (ensemble-mean error,
@@ -1028,6 +1031,39 @@ int32_t nlam_forecast_tail(const nlam_forecast_t* p, void* hip_stream);
 int32_t nlam_forecast_finish(const nlam_forecast_t* p, void* hip_stream);
 /* floats of nlam_forecast_t.workspace for these sizes; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP for nvars > NLAM_EVAL_MAX_VARS */
 int64_t nlam_forecast_workspace_floats(int32_t batch, int32_t nodes, int32_t nvars);
+
+/* nlam_forecast_init / _head over STRIDED series: forecast-type and ensemble datastores, addressed as nlam_window_ens_t addresses
+ * them.  Element (sample s, member m, row j) of a series -- one contiguous (nodes x d) block -- sits at
+ *   base + s * stride_sample + j * stride_step + m * stride_member      (floats, 64-bit)
+ *   analysis data (is_forecast = 0): stride_sample == stride_step, the time stride (NLAM_EINVAL otherwise); n_times = time steps
+ *   forecast data (is_forecast = 1): stride_sample = analysis stride, stride_step = lead-time stride; n_times = analysis times
+ *   forcing without a member axis: forcing_stride_member = 0
+ * sample_idx[b] is the flat sample index of forecast b, read on the device and clamped into [0, base_len * members) instead of
+ * faulting; (s, m) = divmod(idx, members), time-major.  base_len is that of nlam_window_batch_ens at ar_steps = max_lead:
+ * nlam_window_len over n_times for analysis data (at least 1), n_times for forecast data.  With off = max(2, past) and k = *lead:
+ *   nlam_forecast_init_strided   prev_prev = row off - 2, prev = row off - 1; *lead = 0
+ *   nlam_forecast_head_strided   truth = row off + k; slot w of the forcing window = row off + k - past + w
+ * Rows are clamped as well: forecast data into [0, state_steps) and [0, forcing_steps), analysis data the time index s + j into
+ * [0, n_times).  Output layout, standardisation and the guard on *lead are those of the plain pair; each block takes the 16-byte
+ * path when that block, its destination and its size allow it (strides may break the alignment from one member to the next).  The
+ * outputs have the bits of nlam_window_batch_ens at ar_steps = max_lead with statistics.
+ * Of nlam_forecast_t the destinations, statistics, counter and sizes are read; its state, forcing, times, start and n_times are
+ * ignored.  nlam_forecast_tail (valid_times = NULL: its time arithmetic is that of a plain series) and nlam_forecast_finish serve
+ * both kinds of source.  NLAM_EINVAL (before any launch) for null required pointers, sizes < 1, negative strides, members < 1,
+ * is_forecast not in {0, 1}, and on forecast data state_steps < off + max_lead or, with d_forcing > 0, forcing_steps <
+ * off + max_lead + future; NLAM_EUNSUP as the plain pair. */
+typedef struct {
+    const float* state;
+    const float* forcing;            /* NULL when d_forcing == 0 */
+    const int64_t* sample_idx;       /* device (batch): flat sample indices */
+    int64_t state_stride_sample, state_stride_step, state_stride_member;
+    int64_t forcing_stride_sample, forcing_stride_step, forcing_stride_member;
+    int64_t n_times;
+    int32_t state_steps, forcing_steps;   /* forecast data: lead times per analysis time (ignored for analysis data) */
+    int32_t is_forecast, members;
+} nlam_forecast_src_t;
+int32_t nlam_forecast_init_strided(const nlam_forecast_t* p, const nlam_forecast_src_t* src, void* hip_stream);
+int32_t nlam_forecast_head_strided(const nlam_forecast_t* p, const nlam_forecast_src_t* src, void* hip_stream);
 
 /* Sampled ensembles inside the recorded forecast step (neural_lam_amd/forecast.py, EnsembleForecast): batch = starts * members,
  * batch item b = s * members + m (member-minor), every start repeated `members` times in nlam_forecast_t.start.

@@ -197,6 +197,8 @@ EXPORTS = [
     "nlam_forecast_tail",
     "nlam_forecast_finish",
     "nlam_forecast_workspace_floats",
+    "nlam_forecast_init_strided",
+    "nlam_forecast_head_strided",
     "nlam_philox_normal_fill",
     "nlam_latent_sample",
     "nlam_ens_scores",
@@ -434,6 +436,26 @@ class Forecast(C.Structure):
         ("num_past_forcing_steps", C.c_int32),
         ("num_future_forcing_steps", C.c_int32),
         ("delta_ld", C.c_int32),
+    ]
+
+
+class ForecastSrc(C.Structure):
+    """nlam_forecast_src_t: the strided (forecast / ensemble) series nlam_forecast_init_strided / _head_strided read."""
+    _fields_ = [
+        ("state", C.c_void_p),
+        ("forcing", C.c_void_p),
+        ("sample_idx", C.c_void_p),
+        ("state_stride_sample", C.c_int64),
+        ("state_stride_step", C.c_int64),
+        ("state_stride_member", C.c_int64),
+        ("forcing_stride_sample", C.c_int64),
+        ("forcing_stride_step", C.c_int64),
+        ("forcing_stride_member", C.c_int64),
+        ("n_times", C.c_int64),
+        ("state_steps", C.c_int32),
+        ("forcing_steps", C.c_int32),
+        ("is_forecast", C.c_int32),
+        ("members", C.c_int32),
     ]
 
 
@@ -913,6 +935,9 @@ def load():
     lib.nlam_window_batch_ens.restype = i32
     for entry in (lib.nlam_forecast_init, lib.nlam_forecast_head, lib.nlam_forecast_tail, lib.nlam_forecast_finish):
         entry.argtypes = [C.POINTER(Forecast), vp]
+        entry.restype = i32
+    for entry in (lib.nlam_forecast_init_strided, lib.nlam_forecast_head_strided):
+        entry.argtypes = [C.POINTER(Forecast), C.POINTER(ForecastSrc), vp]
         entry.restype = i32
     lib.nlam_forecast_workspace_floats.argtypes = [i32, i32, i32]
     lib.nlam_forecast_workspace_floats.restype = i64

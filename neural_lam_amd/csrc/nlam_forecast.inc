@@ -11,6 +11,8 @@
 //   finish  one workgroup: the partial sums in a fixed order into sq / ab [b][k][f], then ++*lead.  ONE thread reads the counter
 //           and writes it; head and tail only read it, so no launch races with its own readers.
 // All three do nothing once *lead >= max_lead: a replay too many writes nothing.
+// nlam_forecast_init_strided / _head_strided are init and head over forecast-type and ensemble series: the same row loops, the
+// (sample, member, row) block found with nlam_window_ens_t's strides from a flat sample index read on the device.
 // HBM-bound: a workgroup of the tail owns (batch item, chunk of whole nodes), a multiple of 4 nodes, so a chunk starts on a
 // 16-byte boundary whenever its batch item does; 16-byte accesses where every operand of the chunk is aligned (DESIGN 4.17's
 // rule), single elements otherwise and on a chunk's last partial quad.  The per-variable tables -- StepTailTables plus (std, mean)
@@ -75,6 +77,72 @@ __device__ __forceinline__ void fc_state_row(const float* __restrict__ src, floa
     }
 }
 
+// one (nodes x d_forcing * window) row of windowed forcing, standardised: window_batch_kernel's (window x d_forcing) ->
+// (d_forcing x window) transpose per node.  slot(w) is the (nodes x d_forcing) block that window slot w reads.
+template <typename SLOT>
+__device__ __forceinline__ void fc_forcing_row(float* __restrict__ dst, const float2* stats, unsigned nodes, unsigned df, unsigned W,
+                                               unsigned tid, unsigned nthr, SLOT slot) {
+    const unsigned fw = df * W;
+    const unsigned per_out = nodes * fw;
+    const bool vec = (per_out & 3u) == 0 && (reinterpret_cast<size_t>(dst) & 15) == 0;
+    for (unsigned q = tid; q < (per_out + 3) / 4; q += nthr) {
+        const unsigned e0 = 4 * q;
+        unsigned n = e0 / fw;
+        unsigned jj = e0 - n * fw;
+        unsigned fi = jj / W, w = jj - fi * W;
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float x = 0.f;
+            if (e0 + c < per_out) {
+                const float2 ms = stats[fi];
+                x = __fdiv_rn(__fsub_rn(slot(w)[(long)n * df + fi], ms.x), ms.y);
+            }
+            v[c] = x;
+            if (++w == W) {
+                w = 0;
+                if (++fi == df) {
+                    fi = 0;
+                    ++n;
+                }
+            }
+        }
+        if (vec) {
+            *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (e0 + c < per_out) dst[e0 + c] = v[c];
+        }
+    }
+}
+
+// The strided source of nlam_forecast_init_strided / _head_strided: nlam_window_ens_t's addressing.  The flat sample index is
+// read on the device, clamped into [0, n_flat) and split into (sample, member) once per workgroup.
+struct ForecastSrcArgs {
+    nlam_forecast_t p;
+    nlam_forecast_src_t s;
+    long n_flat;   // base_len * members at ar_steps = max_lead (computed and checked by the entry point)
+};
+
+struct FcSample {
+    long s, m;
+};
+
+__device__ __forceinline__ FcSample fc_sample(const ForecastSrcArgs& a, int b) {
+    const long idx = min(max(a.s.sample_idx[b], 0L), a.n_flat - 1);
+    const long s = idx / a.s.members;
+    return FcSample{s, idx - s * a.s.members};
+}
+
+// the contiguous (nodes x d) block of row j of (sample, member): forecast data clamps the lead-time row into [0, steps), analysis
+// data the time index s + j into [0, n_times) (there stride_sample == stride_step)
+__device__ __forceinline__ const float* fc_src_block(const float* base, long stride_sample, long stride_step, long stride_member,
+                                                     const nlam_forecast_src_t& c, int steps, FcSample i, long j) {
+    if (c.is_forecast) return base + i.s * stride_sample + fc_clamp_time(j, steps - 1) * stride_step + i.m * stride_member;
+    return base + fc_clamp_time(i.s + j, c.n_times - 1) * stride_step + i.m * stride_member;
+}
+
 // blockIdx.z = forecast of the batch, blockIdx.y = 0: prev_prev (time t0 - 1), 1: prev (time t0); the counter starts at 0
 __global__ __launch_bounds__(256) void forecast_init_kernel(const nlam_forecast_t p) {
     const float2* const stats = fc_stage_stats(p.state_mean, p.state_std, p.d_state);
@@ -105,43 +173,52 @@ __global__ __launch_bounds__(256) void forecast_head_kernel(const nlam_forecast_
     }
     const int past = p.num_past_forcing_steps;
     const unsigned W = past + p.num_future_forcing_steps + 1, df = p.d_forcing;
-    const unsigned fw = df * W;
-    const unsigned per_out = (unsigned)p.nodes * fw;
     const long per_in = (long)p.nodes * df;
     const long t0 = tv - past;   // time of window slot 0
-    float* dst = p.forcing_windowed + (long)b * per_out;
-    const bool vec = (per_out & 3u) == 0 && (reinterpret_cast<size_t>(dst) & 15) == 0;
-    for (unsigned q = tid; q < (per_out + 3) / 4; q += nthr) {
-        const unsigned e0 = 4 * q;
-        unsigned n = e0 / fw;
-        unsigned jj = e0 - n * fw;
-        unsigned fi = jj / W, w = jj - fi * W;
-        float v[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float x = 0.f;
-            if (e0 + c < per_out) {
-                const long t = fc_clamp_time(t0 + (long)w, last);
-                const float2 ms = stats[fi];
-                x = __fdiv_rn(__fsub_rn(p.forcing[t * per_in + (long)n * df + fi], ms.x), ms.y);
-            }
-            v[c] = x;
-            if (++w == W) {
-                w = 0;
-                if (++fi == df) {
-                    fi = 0;
-                    ++n;
-                }
-            }
-        }
-        if (vec) {
-            *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (e0 + c < per_out) dst[e0 + c] = v[c];
-        }
+    fc_forcing_row(p.forcing_windowed + (long)b * p.nodes * (df * W), stats, p.nodes, df, W, tid, nthr,
+                   [&](unsigned w) { return p.forcing + fc_clamp_time(t0 + (long)w, last) * per_in; });
+}
+
+// forecast_init_kernel over a strided source: rows off - 2 and off - 1 of the sample
+__global__ __launch_bounds__(256) void forecast_init_strided_kernel(const ForecastSrcArgs a) {
+    const nlam_forecast_t& p = a.p;
+    const nlam_forecast_src_t& c = a.s;
+    const float2* const stats = fc_stage_stats(p.state_mean, p.state_std, p.d_state);
+    const int b = blockIdx.z, r = blockIdx.y;
+    const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
+    const long j = max(2, p.num_past_forcing_steps) - 2 + r;
+    const float* src = fc_src_block(c.state, c.state_stride_sample, c.state_stride_step, c.state_stride_member, c, c.state_steps,
+                                    fc_sample(a, b), j);
+    fc_state_row(src, (r == 0 ? p.prev_prev : p.prev) + (long)b * per, stats, per, p.d_state, blockIdx.x * blockDim.x + threadIdx.x,
+                 gridDim.x * blockDim.x);
+    if (blockIdx.x == 0 && r == 0 && b == 0 && threadIdx.x == 0) *p.lead = 0;
+}
+
+// forecast_head_kernel over a strided source: the truth is row off + k, window slot w of the forcing row off + k - past + w
+__global__ __launch_bounds__(256) void forecast_head_strided_kernel(const ForecastSrcArgs a) {
+    const nlam_forecast_t& p = a.p;
+    const nlam_forecast_src_t& c = a.s;
+    const int k = *p.lead;
+    if (k >= p.max_lead) return;   // the same in every thread of the grid, ahead of every barrier
+    const bool forc = blockIdx.y == 1;
+    const float2* const stats = forc ? fc_stage_stats(p.forcing_mean, p.forcing_std, p.d_forcing)
+                                     : fc_stage_stats(p.state_mean, p.state_std, p.d_state);
+    const int b = blockIdx.z;
+    const FcSample i = fc_sample(a, b);
+    const int past = p.num_past_forcing_steps;
+    const long jv = max(2, past) + k;   // the row of this lead
+    const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
+    if (!forc) {
+        const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
+        fc_state_row(fc_src_block(c.state, c.state_stride_sample, c.state_stride_step, c.state_stride_member, c, c.state_steps, i, jv),
+                     p.truth + (long)b * per, stats, per, p.d_state, tid, nthr);
+        return;
     }
+    const unsigned W = past + p.num_future_forcing_steps + 1, df = p.d_forcing;
+    fc_forcing_row(p.forcing_windowed + (long)b * p.nodes * (df * W), stats, p.nodes, df, W, tid, nthr, [&](unsigned w) {
+        return fc_src_block(c.forcing, c.forcing_stride_sample, c.forcing_stride_step, c.forcing_stride_member, c, c.forcing_steps, i,
+                            jv - past + (long)w);
+    });
 }
 
 // blockIdx.y = forecast of the batch, blockIdx.x = chunk of fc_chunk_nodes nodes.  LDS: StepTailTables, (std, mean) of the state,
@@ -338,6 +415,37 @@ int32_t forecast_check(const nlam_forecast_t* p, int which) {
     return 0;
 }
 
+// the checks of a strided source, and the launch arguments: the series, the sample indices and n_times of `p` are replaced by the
+// source's, so that forecast_check sees what the kernels read
+int32_t forecast_src_check(const nlam_forecast_t* p, const nlam_forecast_src_t* s, int which, ForecastSrcArgs* a) {
+    if (p == nullptr || s == nullptr) return NLAM_EINVAL;
+    a->p = *p;
+    a->s = *s;
+    a->p.state = s->state;
+    a->p.forcing = s->forcing;
+    a->p.start = s->sample_idx;
+    a->p.n_times = s->n_times;
+    if (const int32_t rc = forecast_check(&a->p, which)) return rc;
+    if (s->members < 1 || (s->is_forecast != 0 && s->is_forecast != 1)) return NLAM_EINVAL;
+    if (s->state_stride_sample < 0 || s->state_stride_step < 0 || s->state_stride_member < 0 || s->forcing_stride_sample < 0 ||
+        s->forcing_stride_step < 0 || s->forcing_stride_member < 0)
+        return NLAM_EINVAL;
+    const int64_t off = p->num_past_forcing_steps > 2 ? p->num_past_forcing_steps : 2;
+    int64_t base_len;
+    if (s->is_forecast) {
+        if (s->state_steps < off + p->max_lead) return NLAM_EINVAL;   // lead-time axis too short
+        if (p->d_forcing > 0 && s->forcing_steps < off + p->max_lead + p->num_future_forcing_steps) return NLAM_EINVAL;
+        base_len = s->n_times;
+    } else {
+        if (s->state_stride_sample != s->state_stride_step || (p->d_forcing > 0 && s->forcing_stride_sample != s->forcing_stride_step))
+            return NLAM_EINVAL;   // one time axis
+        base_len = nlam_window_len(s->n_times, -1, p->max_lead, p->num_past_forcing_steps, p->num_future_forcing_steps);
+        if (base_len < 1) base_len = 1;   // too short a series: the time clamp keeps every read inside it
+    }
+    a->n_flat = (long)(base_len * s->members);
+    return 0;
+}
+
 // workgroups of a (nodes x row) block of `elems` floats: four elements per thread, two rounds
 int fc_row_blocks(long elems) {
     const long blocks = (elems + 2047) / 2048;
@@ -363,6 +471,25 @@ int32_t nlam_forecast_head(const nlam_forecast_t* p, void* hip_stream) {
     const int wide = p->d_state > p->d_forcing ? p->d_state : p->d_forcing;
     return launch<forecast_head_kernel>(dim3(fc_row_blocks(e_state > e_forc ? e_state : e_forc), p->d_forcing > 0 ? 2 : 1, p->batch),
                                         dim3(256), (size_t)wide * sizeof(float2), (hipStream_t)hip_stream, *p);
+}
+
+int32_t nlam_forecast_init_strided(const nlam_forecast_t* p, const nlam_forecast_src_t* src, void* hip_stream) {
+    NLAM_RANGE("nlam_forecast_init_strided");
+    ForecastSrcArgs a;
+    if (const int32_t rc = forecast_src_check(p, src, kFcInit, &a)) return rc;
+    return launch<forecast_init_strided_kernel>(dim3(fc_row_blocks((long)p->nodes * p->d_state), 2, p->batch), dim3(256),
+                                                (size_t)p->d_state * sizeof(float2), (hipStream_t)hip_stream, a);
+}
+
+int32_t nlam_forecast_head_strided(const nlam_forecast_t* p, const nlam_forecast_src_t* src, void* hip_stream) {
+    NLAM_RANGE("nlam_forecast_head_strided");
+    ForecastSrcArgs a;
+    if (const int32_t rc = forecast_src_check(p, src, kFcHead, &a)) return rc;
+    const long window = (long)p->num_past_forcing_steps + p->num_future_forcing_steps + 1;
+    const long e_state = (long)p->nodes * p->d_state, e_forc = (long)p->nodes * p->d_forcing * window;
+    const int wide = p->d_state > p->d_forcing ? p->d_state : p->d_forcing;
+    return launch<forecast_head_strided_kernel>(dim3(fc_row_blocks(e_state > e_forc ? e_state : e_forc), p->d_forcing > 0 ? 2 : 1, p->batch),
+                                                dim3(256), (size_t)wide * sizeof(float2), (hipStream_t)hip_stream, a);
 }
 
 int32_t nlam_forecast_tail(const nlam_forecast_t* p, void* hip_stream) {

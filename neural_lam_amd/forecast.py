@@ -2,7 +2,8 @@
 
 ``ARForecaster.forward`` under ``torch.no_grad()`` wants the forcing windows and boundary states of the whole horizon
 materialised, records every AR step again when it is captured, and returns standardised, stacked predictions.  ``Forecast``
-is the product form: the series stay where ``DeviceWeatherDataset`` keeps them, a lead counter in device memory ties the data
+is the product form: the series stay where ``DeviceWeatherDataset`` keeps them (plain analysis series, or forecast-type and
+ensemble layouts read through their strides), a lead counter in device memory ties the data
 path to the inference step tail (``nlam_forecast_head`` / ``_tail`` / ``_finish``, include/nlam_hip.h), and one recorded step
 
     head -> predictor(prev, prev_prev, forcing, raw_delta=True) -> tail -> finish
@@ -49,6 +50,46 @@ def plan_forecast(n_times, num_past_forcing_steps, num_future_forcing_steps, max
         raise ValueError(f"plan_forecast: n_times {n_times} and max_lead {max_lead} must be >= 1, the forcing steps ({past}, {fut}) >= 0")
     off = max(2, past)
     return off, max(0, n_times - (off + max_lead + fut) + 1)
+
+
+def plan_forecast_dataset(layout, num_past_forcing_steps, num_future_forcing_steps, max_lead, ar_steps):
+    """``(off, n_starts, members)`` for a dataset of any layout (``layout``: the ``data.Layout`` of ``plan_layout``).  A start is a
+    flat sample index, ``i -> (i // members, i % members)`` as ``DeviceWeatherDataset.batch`` decodes it.  Forecast data (the
+    layout keeps lead times): every analysis time of every member is a start, and the horizon is what the dataset keeps resident,
+    so ``max_lead > ar_steps`` is a ValueError.  Analysis data: ``plan_forecast`` over the common time axis per member; ``ar_steps``
+    is not read.  No GPU."""
+    past, fut, max_lead = int(num_past_forcing_steps), int(num_future_forcing_steps), int(max_lead)
+    members = int(layout.members)
+    if layout.state_steps is None:
+        off, per_member = plan_forecast(layout.n_times, past, fut, max_lead)
+        return off, per_member * members, members
+    off = plan_forecast(layout.n_times, past, fut, max_lead)[0]
+    if max_lead > int(ar_steps):
+        raise ValueError(f"forecast data keeps the lead times of ar_steps = {int(ar_steps)} resident: max_lead {max_lead} needs a "
+                         f"dataset built with ar_steps >= {max_lead}")
+    return off, int(layout.n_times) * members, members
+
+
+def dataset_source(dataset, sample_idx):
+    """The ``nlam_forecast_src_t`` of a ``DeviceWeatherDataset``'s resident series: the strides in floats from the tensors' own
+    layout, as its ``nlam_window_batch_ens`` launch takes them.  ``sample_idx``: the device int64 tensor of flat sample indices
+    the launches read (kept alive by the caller)."""
+    s = L.ForecastSrc()
+    s.state, s.forcing, s.sample_idx = _ptr(dataset.state), _ptr(dataset.forcing), _ptr(sample_idx)
+    lead_ax = 1 if dataset.is_forecast else 0
+
+    def strides(x):   # (sample, step, member); member stride 0 without a member axis
+        if x is None:
+            return 0, 0, 0
+        return x.stride(0), x.stride(lead_ax), (x.stride(lead_ax + 1) if x.dim() == 4 + lead_ax else 0)
+
+    s.state_stride_sample, s.state_stride_step, s.state_stride_member = strides(dataset.state)
+    s.forcing_stride_sample, s.forcing_stride_step, s.forcing_stride_member = strides(dataset.forcing)
+    s.n_times, s.is_forecast, s.members = int(dataset._n_times), int(dataset.is_forecast), int(dataset.members)
+    if dataset.is_forecast:
+        s.state_steps = dataset.state.shape[1]
+        s.forcing_steps = 0 if dataset.forcing is None else dataset.forcing.shape[1]
+    return s
 
 
 def check_starts(starts, n_starts):
@@ -107,13 +148,20 @@ def _kernel_nodes(graph: "torch.cuda.CUDAGraph") -> int:
 
 
 class Forecast:
-    """A forecast engine over a trained ``ForecasterStep`` and a ``DeviceWeatherDataset`` of plain analysis series.
+    """A forecast engine over a trained ``ForecasterStep`` and a ``DeviceWeatherDataset`` of any layout.
 
     ``step``: its predictor, boundary mask, interior weights and statistics are used; the predictor must satisfy
     ``can_return_raw_delta()`` or ``can_fuse_ext_tail()`` (GraphLAM, Hi-LAM, Hi-LAM-Parallel, with or without output clamps and a
-    predicted std; ValueError otherwise, Graph-EFM included).  ``dataset``: ``dataset.kernel == "nlam_window_batch"`` (forecast-type
-    and ensemble layouts: ValueError); its ``ar_steps`` is ignored, the horizon is ``max_lead``.  ``verify=True`` also scores
-    every lead against the analysis (``ForecastResult.sq`` / ``ab``).  ``use_graph=False`` issues the same launches eagerly.
+    predicted std; ValueError otherwise, Graph-EFM included).  ``dataset``: a plain analysis series (``dataset.kernel ==
+    "nlam_window_batch"``) is read by ``nlam_forecast_init`` / ``_head``, its ``ar_steps`` is ignored and the horizon is
+    ``max_lead``.  A forecast-type or ensemble ``DeviceWeatherDataset`` is read by ``nlam_forecast_init_strided`` / ``_head_strided``
+    through the dataset's own strides: a start is a flat sample index, ``i -> (i // members, i % members)`` as ``dataset.batch``
+    decodes it; analysis data with members has ``plan_forecast(...)[1] * members`` starts; forecast data has ``len(dataset)`` starts
+    and only the lead times of its ``ar_steps`` resident, so ``max_lead > dataset.ar_steps`` is a ValueError (build the dataset with
+    ``ar_steps`` = the longest horizon wanted).  Every lead is verified against the dataset's own rows: the state of the start's
+    member, the forcing shared or per member as the dataset has it.  Anything else that claims another kernel: ValueError.
+    ``verify=True`` also scores every lead against the analysis (``ForecastResult.sq`` / ``ab``).  ``use_graph=False`` issues the
+    same launches eagerly.
     ``autocast_dtype``: the predictor call alone runs under ``torch.autocast`` with it.  Weights changed in place between two
     ``run`` calls (a training step, ``load_state_dict``, ``with tr.ema_weights():``) are honoured by the second call: the recorded
     step reads the parameters where they live and the static embeddings are recomputed by every ``run``."""
@@ -135,9 +183,12 @@ class Forecast:
             raise ValueError(f"Forecast: {type(predictor).__name__} cannot hand its raw network output to the forecast tail (it needs "
                              "can_return_raw_delta() or can_fuse_ext_tail(): a graph model with a per-variable diff_std, and "
                              "NLAM_FUSED_CLAMPED_TAIL on for output clamps or a predicted std; Graph-EFM is not served)")
-        if getattr(dataset, "kernel", None) != "nlam_window_batch":
-            raise ValueError("Forecast reads plain analysis series (dataset.kernel == 'nlam_window_batch'): forecast-type and ensemble "
-                             "datasets are not served")
+        from .data import DeviceWeatherDataset
+
+        strided = isinstance(dataset, DeviceWeatherDataset) and dataset.kernel == "nlam_window_batch_ens"
+        if not strided and getattr(dataset, "kernel", None) != "nlam_window_batch":
+            raise ValueError("Forecast reads a DeviceWeatherDataset (any layout) or plain analysis series (dataset.kernel == "
+                             "'nlam_window_batch'): other forecast-type and ensemble datasets are not served")
         self.max_lead, self.batch_size = int(max_lead), int(batch_size)
         if self.max_lead < 1 or self.batch_size < 1:
             raise ValueError(f"Forecast: max_lead {max_lead} and batch_size {batch_size} must be >= 1")
@@ -148,10 +199,16 @@ class Forecast:
         self.verify, self.use_graph, self.autocast_dtype = bool(verify), bool(use_graph), autocast_dtype
         self.past, self.future = dataset.num_past_forcing_steps, dataset.num_future_forcing_steps
         self.n_times = int(dataset._n_times)
-        self.off, self.n_starts = plan_forecast(self.n_times, self.past, self.future, self.max_lead)
+        self.strided = strided
+        if strided:
+            self.off, self.n_starts, self.data_members = plan_forecast_dataset(dataset.layout, self.past, self.future, self.max_lead,
+                                                                               dataset.ar_steps)
+        else:
+            self.off, self.n_starts = plan_forecast(self.n_times, self.past, self.future, self.max_lead)
+            self.data_members = 1
         B, Lm = self.batch_size, self.max_lead
-        N, F = int(dataset.state.shape[1]), int(dataset.state.shape[2])
-        dfo = 0 if dataset.forcing is None else int(dataset.forcing.shape[2])
+        N, F = int(dataset.state.shape[-2]), int(dataset.state.shape[-1])
+        dfo = 0 if dataset.forcing is None else int(dataset.forcing.shape[-1])
         if N != predictor.num_grid_nodes or F != step.state_mean.numel() or (dfo > 0 and step.forcing_mean is None):
             raise ValueError(f"Forecast: the dataset's series ({N} nodes, {F} state and {dfo} forcing variables) do not fit the step")
         self.has_std = bool(predictor.output_std)
@@ -192,6 +249,12 @@ class Forecast:
         p.max_lead, p.num_past_forcing_steps, p.num_future_forcing_steps = Lm, self.past, self.future
         p.delta_ld = 2 * F if self.has_std else F
         self._p = p
+        self._src = None
+        if strided:
+            # the head and init read the series through the dataset's own strides (they ignore p.state / p.forcing / p.start, which
+            # the tail's argument check still wants); the tail's valid-time arithmetic is a plain series': computed per run (_replay)
+            p.times = p.valid_times = None
+            self._src = dataset_source(dataset, self.start)
         self._static = None     # persistent copies of the predictor's static embeddings: the recorded step reads these
         self._graph = None
         self._delta = None      # the recorded step's network output (kept alive with the graph)
@@ -201,6 +264,10 @@ class Forecast:
     def _entry(self, name):
         from .ops import _stream
 
+        if self._src is not None and name in ("nlam_forecast_init", "nlam_forecast_head"):
+            name += "_strided"
+            L.check(getattr(self._lib, name)(C.byref(self._p), C.byref(self._src), _stream()), name)
+            return
         L.check(getattr(self._lib, name)(C.byref(self._p), _stream()), name)
 
     def _autocast(self):
@@ -296,6 +363,21 @@ class Forecast:
         self._replay(starts, leads)
         return ForecastResult(self.out_state, self.out_std, self.valid_times, self.sq, self.ab)
 
+    def _dataset_times(self, starts):
+        """``valid_times`` of a strided dataset, the ``target_times`` of ``dataset.batch``: ``times[s + off + k]`` (analysis data),
+        ``times[s] + elapsed[off + k]`` (forecast data), the time / lead-time index without stamps.  On the device, once per run,
+        with the kernels' clamp of the flat index."""
+        ds, M = self.dataset, self.data_members
+        s = torch.clamp(starts, 0, max(self.n_starts, M) - 1) // M
+        rows = torch.arange(self.off, self.off + self.max_lead, device=starts.device)
+        if ds.is_forecast:
+            vt = rows.expand(s.numel(), -1) if ds.times is None else ds.times[s][:, None] + ds.elapsed[rows][None]
+        else:
+            vt = torch.clamp(s[:, None] + rows, max=self.n_times - 1)
+            if ds.times is not None:
+                vt = ds.times[vt]
+        self.valid_times.copy_(vt)
+
     def _replay(self, starts, leads):
         """``leads`` leads from the device sample indices ``starts`` (one per batch item) into the engine's buffers."""
         with torch.no_grad():
@@ -303,7 +385,11 @@ class Forecast:
             with self._static_installed():
                 if self.use_graph and self._graph is None:
                     self._record()
-                torch.add(starts, self.off - 1, out=self.start)   # t0 of every forecast
+                if self.strided:
+                    self.start.copy_(starts)   # the flat sample index: the kernels split it into (sample, member)
+                    self._dataset_times(starts)
+                else:
+                    torch.add(starts, self.off - 1, out=self.start)   # t0 of every forecast
                 self._entry("nlam_forecast_init")
                 for _ in range(leads):
                     if self.use_graph:
@@ -389,6 +475,9 @@ class EnsembleForecast(Forecast):
     so the forecast of ``(seed, start, member)`` has the same bits with and without the graph, from run to run and whatever
     other starts share the batch.  A deterministic predictor (whatever ``Forecast`` takes) is accepted too, without the sampling
     launch: its members are identical by construction (the baseline of the ensemble launch's cost).
+    On a forecast-type or ensemble dataset (``Forecast``'s rules) all ``members`` model members of a start begin from the same
+    dataset sample ``(s, m_data)``, and the "start" word of the Philox counter is the flat sample index, not the time index ``t0``
+    of a plain series: the guarantee above holds per dataset, but the same weather read from a plain series draws other noise.
     ``verify``: the per-member sums of ``Forecast`` and the ensemble scores; the mean and spread fields are always written.
     ``record_noise``: keep every lead's draws (``EnsembleResult.noise``).  Members are always kept: the member fields take
     ``4 S M L N F`` bytes (twice that with a std head), mean and spread ``8 S L N F``."""

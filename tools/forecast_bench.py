@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Forecast engine (neural_lam_amd/forecast.py) against the existing route, one process, alternating with warm-up.
 
-    python tools/forecast_bench.py [--config cfg2] [--leads 40 240] [--rounds 3] [--out profiles/forecast/bench.json]
+    python tools/forecast_bench.py [--config cfg2] [--leads 40 240] [--rounds 3] [--layout plain|forecast|members]
+                                   [--out profiles/forecast/bench.json]
 
 Route "engine": ``Forecast(step, dataset, max_lead=L).run(starts)`` -- init + L replays of one recorded step, the series resident.
 Route "existing": what bench.py's forecast leg does, at T = L: ``ARForecaster.forward`` under no_grad captured as ONE graph of T
@@ -9,6 +10,8 @@ steps, replayed; its pre-built inputs (forcing windows and boundary states of th
 Per route and horizon: ms per lead time (HIP events around a synchronised window of ``--repeats`` forecasts; median over the rounds
 and the rounds' spread max - min), kernel launches per lead (kernel nodes of the recorded graph / leads in it), and the peak memory
 above what both routes share (the model and the resident series): for the existing route with and without its inputs.
+``--layout forecast`` / ``members`` keep the engine's series as forecast-type data or with a member axis (the strided head and
+init); the existing route's inputs are synthetic either way, so its numbers do not depend on the layout.
 For the engine also the head and tail kernels alone: 50 launches replayed from one graph between two events, and their minimum
 bytes (every float they must read or write, once) over that time.
 """
@@ -59,6 +62,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3, help="forecasts per timed window")
     ap.add_argument("--verify", action="store_true", help="the engine also scores every lead (sq / ab)")
+    ap.add_argument("--layout", choices=["plain", "forecast", "members"], default="plain",
+                    help="the resident series: a plain analysis series, forecast-type data (analysis time, lead time, member), or an "
+                         "analysis series with a member axis; the last two go through nlam_forecast_init_strided / _head_strided")
+    ap.add_argument("--members", type=int, default=2, help="size of the member axis of the forecast and members layouts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -75,16 +82,26 @@ def main():
     N, F, DF, B = ds.num_grid_points, cfg["ns"], cfg["nf"], cfg["B"]
     past = fut = 1
     window = past + fut + 1
-    n_times = max(args.leads) + 2 + fut + 4
     g = torch.Generator().manual_seed(123)
-    state = torch.randn(n_times, N, F, generator=g).to(dev)
-    forcing = torch.randn(n_times, N, DF, generator=g).to(dev)
-    data = DeviceWeatherDataset(state, forcing, None, ar_steps=1, num_past_forcing_steps=past, num_future_forcing_steps=fut,
-                                standardization=step.standardization_stats())
-    starts = torch.arange(B, dtype=torch.int64, device=dev)
+    M = args.members
+    kw = dict(num_past_forcing_steps=past, num_future_forcing_steps=fut, standardization=step.standardization_stats())
+    if args.layout == "forecast":   # B analysis times x the lead times of the longest horizon x M members, the forcing shared
+        steps = 2 + max(args.leads) + fut
+        state = torch.randn(B, steps, M, N, F, generator=g).to(dev)
+        forcing = torch.randn(B, steps, N, DF, generator=g).to(dev)
+        data = DeviceWeatherDataset(state, forcing, None, ar_steps=max(args.leads), is_forecast=True, **kw)
+    else:                           # an analysis series, with a member axis of M ("members") or without one ("plain")
+        n_times = max(args.leads) + 2 + fut + 4
+        member_axis = (M,) if args.layout == "members" else ()
+        state = torch.randn(n_times, *member_axis, N, F, generator=g).to(dev)
+        forcing = torch.randn(n_times, N, DF, generator=g).to(dev)
+        data = DeviceWeatherDataset(state, forcing, None, ar_steps=1, **kw)
+    strided = data.kernel != "nlam_window_batch"
+    starts = torch.arange(B, dtype=torch.int64, device=dev) * data.members + (data.members - 1)   # sample b, its last member
     torch.cuda.synchronize()
     shared = torch.cuda.memory_allocated()
-    out = {"config": args.config, "nodes": N, "state_vars": F, "forcing_vars": DF, "batch": B, "rounds": args.rounds,
+    out = {"config": args.config, "layout": args.layout, "members": M if strided else 1,
+           "nodes": N, "state_vars": F, "forcing_vars": DF, "batch": B, "rounds": args.rounds,
            "repeats": args.repeats, "verify": args.verify, "source_stamp": L.source_stamp(), "device": torch.cuda.get_device_name(0),
            "shared_bytes": shared, "horizons": {}}
 
@@ -136,7 +153,11 @@ def main():
         stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)   # noqa: E731
         delta = torch.randn(B * N, fc._p.delta_ld, generator=g).to(dev) * 0.01
         fc._p.delta = C.c_void_p(delta.data_ptr())
-        head_ms = kernel_ms(lambda: L.check(fc._lib.nlam_forecast_head(C.byref(fc._p), stream()), "nlam_forecast_head"))
+        if strided:
+            head_ms = kernel_ms(lambda: L.check(fc._lib.nlam_forecast_head_strided(C.byref(fc._p), C.byref(fc._src), stream()),
+                                                "nlam_forecast_head_strided"))
+        else:
+            head_ms = kernel_ms(lambda: L.check(fc._lib.nlam_forecast_head(C.byref(fc._p), stream()), "nlam_forecast_head"))
         tail_ms = kernel_ms(lambda: L.check(fc._lib.nlam_forecast_tail(C.byref(fc._p), stream()), "nlam_forecast_tail"))
         head_bytes = 2 * 4 * B * N * (F + DF * window)
         tail_bytes = 4 * B * N * (fc._p.delta_ld + 5 * F + (F if fc.has_std else 0))
