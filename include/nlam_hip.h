@@ -828,6 +828,8 @@ int32_t nlam_step_tail_loss_bwd(int32_t kind, const float* g_pred, const float* 
  *   pred = bmask[n] * truth + (1 - bmask[n]) * new
  *   std  = softplus(delta[row * ld + F + f])        -> pred_std (rows, F), with a std head
  *   loss += scale * row_weight[n] * entry(pred - target; consts[f], or this element's std)
+ * The clamp of u is at the fp32 values float32(1e-6) and float32(1 - 1e-6) = 1 - 17 * 2^-24, as torch clamps an fp32 tensor: beyond
+ * the upper one 1 - u is 1.3 % above 1e-6, so a float64 evaluation with the decimal constants differs there by that much.
  * softplus (beta 1, threshold 20) and inv_softplus (utils/tensor.py, lower clamp log(float32(1 + 1e-6))) are torch's, and the
  * backward gives the derivatives autograd gives that formulation (0 through a clamp outside its bounds).  lo / hi are the
  * standardised limits, lo < hi is the caller's contract; entries of variables without that limit are not read.
