@@ -72,6 +72,11 @@
  *   nlam_window_moments, nlam_moments_workspace_doubles
  *       the per-sample means and second moments of npyfilesmeps/compute_standardization_stats.py (values and
  *       standardized one-step differences), read in place from the resident series of the data path.
+ *   nlam_series_range, nlam_series_range_workspace_words, nlam_series_pack_q16, nlam_window_batch_q16,
+ *   nlam_window_moments_q16, nlam_forecast_init_q16, nlam_forecast_head_q16
+ *       the resident series kept as packed int16 (per-feature scale and offset, as GRIB and packed netCDF ship them): the
+ *       exact range and the encoding of an fp32 chunk on upload, and the batch, moments and forecast data kernels with the
+ *       decode in flight; a packed series gives the bits of an fp32 series that holds its decoded values.
  *   nlam_reduce_partials
  *       deterministic second stage of the per-workgroup partial sums.
  *   nlam_adamw_step
@@ -1348,6 +1353,72 @@ typedef struct {
 int32_t nlam_window_moments(const nlam_moments_t* p, void* hip_stream);
 /* doubles of nlam_moments_t.workspace for these sizes; -1 (NLAM_EINVAL) for sizes out of range */
 int64_t nlam_moments_workspace_doubles(int32_t nodes, int32_t nvars, int64_t count, int32_t step);
+
+/* Resident series as PACKED int16.  Every series has per-feature fp32 tables scale[f] > 0 and offset[f]:
+ *   decode  x = fadd_rn(fmul_rn((float)q, scale[f]), offset[f])       two separately rounded fp32 operations, never one fma
+ *           (contraction is switched off around them; numpy on float32 arrays: q.astype(float32) * scale + offset)
+ *   encode  q = clamp(rintf(fdiv_rn(fsub_rn(x, offset[f]), scale[f])), -32767, 32767)   round to nearest even; -32768 is never
+ *           produced and has no special meaning on decode
+ * Standardisation, where an entry applies it, follows on the decoded value exactly as in the fp32 entries (IEEE sub, then div);
+ * the two affine maps are not folded.  Every _q16 entry therefore gives the bits of its fp32 entry on a series of the decoded
+ * values.  Strides of a packed series are counted in int16 ELEMENTS; a (nodes x d) block may start at any 2-byte-aligned
+ * address and is read four codes (8 bytes) per lane when it starts on an 8-byte boundary, its destination on a 16-byte
+ * boundary and its length is a multiple of 4, code by code otherwise (the fp32 entries' 16-byte test).
+ *
+ * nlam_series_range: per-feature minimum, maximum and count of non-finite values of a contiguous fp32 chunk (rows, nvars),
+ *   MERGED into the running device tables run_min / run_max (nvars floats, initialised by the caller to +inf / -inf) and
+ *   run_bad (nvars int64, initialised to 0): a series uploaded in chunks is reduced chunk by chunk.  Non-finite values are
+ *   counted and take no part in the extrema.  min and max are exact and order-independent; no atomics: per-workgroup
+ *   partial tables in `workspace` (nlam_series_range_workspace_words(rows, nvars) 32-bit words, monotone in rows), folded by
+ *   a second launch.  NLAM_EINVAL for null pointers, rows or nvars < 1, a short workspace; NLAM_EUNSUP for nvars >
+ *   NLAM_MOMENTS_MAX_VARS.
+ * nlam_series_pack_q16: encodes the contiguous fp32 chunk (rows, nvars) into dst[dst_offset ... dst_offset + rows * nvars)
+ *   (elements).  16-byte loads and 8-byte stores where the chunk is 16-byte and the destination 8-byte aligned, single
+ *   elements otherwise and on the last partial quad.  NLAM_EINVAL for null pointers, rows or nvars < 1, dst_offset < 0;
+ *   NLAM_EUNSUP for chunks of 2^31 elements or more.
+ * Both: no allocation, no host synchronisation. */
+int64_t nlam_series_range_workspace_words(int64_t rows, int32_t nvars);
+int32_t nlam_series_range(const float* x, int64_t rows, int32_t nvars, float* run_min, float* run_max, int64_t* run_bad,
+                          uint32_t* workspace, int64_t workspace_words, void* hip_stream);
+int32_t nlam_series_pack_q16(const float* x, int64_t rows, int32_t nvars, const float* scale, const float* offset, int16_t* dst,
+                             int64_t dst_offset, void* hip_stream);
+
+/* The packed source of a _q16 entry, passed beside the entry's parameter struct.  A series whose pointer is set here is read
+ * from it, with the strides of the parameter struct counted in int16 elements, and the float pointer of that series in the
+ * parameter struct is ignored.  A series whose pointer is NULL here is not packed: it is read as fp32 through the float
+ * pointer and float strides of the parameter struct (state packed and forcing fp32, or the reverse).  NLAM_EINVAL when the
+ * state is in neither place, when d_forcing > 0 and the forcing is in neither place, or when a packed series comes without
+ * one of its two tables. */
+typedef struct {
+    const int16_t* state;           /* packed state series or NULL */
+    const int16_t* forcing;         /* packed forcing series or NULL */
+    const float* state_scale;       /* (d_state) */
+    const float* state_offset;      /* (d_state) */
+    const float* forcing_scale;     /* (d_forcing) */
+    const float* forcing_offset;    /* (d_forcing) */
+} nlam_q16_src_t;
+
+/* nlam_window_batch_ens over packed series: the same launch shape, clamp of the flat index, (s, m) = divmod(idx, members), rows,
+ * forcing-window transpose, target_times and optional standardisation.  A plain analysis series is the case
+ * state_stride_sample == state_stride_step with members = 1.  Checks and return codes as nlam_window_batch_ens, with the
+ * series pointers checked as nlam_q16_src_t describes. */
+int32_t nlam_window_batch_q16(const nlam_window_ens_t* p, const nlam_q16_src_t* src, void* hip_stream);
+
+/* nlam_window_moments over a packed series (`series`, strides of nlam_moments_t in int16 elements; nlam_moments_t.series is
+ * ignored), both modes: the same node split, the same fp64 sums from the first decoded element in the same order, the same
+ * second launch; out_mean / out_sq are bit-identical to nlam_window_moments on the decoded series.  Checks and return codes
+ * as nlam_window_moments; NLAM_EINVAL also for a null series, scale or offset. */
+int32_t nlam_window_moments_q16(const nlam_moments_t* p, const int16_t* series, const float* scale, const float* offset,
+                                void* hip_stream);
+
+/* nlam_forecast_init_strided / _head_strided over packed series: the same launch shapes, sample arithmetic, row clamps, guard on
+ * *lead and standardisation; nlam_forecast_tail / _finish read what the head wrote and serve this source as well.  Of
+ * nlam_forecast_src_t the strides of a packed series are counted in int16 elements.  Checks and return codes as the strided
+ * pair, with the series pointers checked as nlam_q16_src_t describes. */
+int32_t nlam_forecast_init_q16(const nlam_forecast_t* p, const nlam_forecast_src_t* src, const nlam_q16_src_t* packed,
+                               void* hip_stream);
+int32_t nlam_forecast_head_q16(const nlam_forecast_t* p, const nlam_forecast_src_t* src, const nlam_q16_src_t* packed,
+                               void* hip_stream);
 
 /* decoupled-weight-decay Adam on flat buffers; step_count is the 1-based step */
 int32_t nlam_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,

@@ -211,6 +211,13 @@ EXPORTS = [
     "nlam_crps_ens_fwd",
     "nlam_crps_ens_bwd",
     "nlam_crps_ens_workspace_floats",
+    "nlam_series_range_workspace_words",
+    "nlam_series_range",
+    "nlam_series_pack_q16",
+    "nlam_window_batch_q16",
+    "nlam_window_moments_q16",
+    "nlam_forecast_init_q16",
+    "nlam_forecast_head_q16",
 ]
 
 
@@ -647,6 +654,18 @@ class Moments(C.Structure):
     ]
 
 
+class Q16Src(C.Structure):
+    """nlam_q16_src_t: the packed int16 series of a _q16 entry and their decode tables (a NULL series is read as fp32)."""
+    _fields_ = [
+        ("state", C.c_void_p),
+        ("forcing", C.c_void_p),
+        ("state_scale", C.c_void_p),
+        ("state_offset", C.c_void_p),
+        ("forcing_scale", C.c_void_p),
+        ("forcing_offset", C.c_void_p),
+    ]
+
+
 class Loss(C.Structure):
     _fields_ = [
         ("pred", C.c_void_p),
@@ -965,6 +984,19 @@ def load():
     lib.nlam_window_moments.restype = i32
     lib.nlam_moments_workspace_doubles.argtypes = [i32, i32, i64, i32]
     lib.nlam_moments_workspace_doubles.restype = i64
+    lib.nlam_series_range_workspace_words.argtypes = [i64, i32]
+    lib.nlam_series_range_workspace_words.restype = i64
+    lib.nlam_series_range.argtypes = [vp, i64, i32, vp, vp, vp, vp, i64, vp]
+    lib.nlam_series_range.restype = i32
+    lib.nlam_series_pack_q16.argtypes = [vp, i64, i32, vp, vp, vp, i64, vp]
+    lib.nlam_series_pack_q16.restype = i32
+    lib.nlam_window_batch_q16.argtypes = [C.POINTER(WindowEns), C.POINTER(Q16Src), vp]
+    lib.nlam_window_batch_q16.restype = i32
+    lib.nlam_window_moments_q16.argtypes = [C.POINTER(Moments), vp, vp, vp, vp]
+    lib.nlam_window_moments_q16.restype = i32
+    for entry in (lib.nlam_forecast_init_q16, lib.nlam_forecast_head_q16):
+        entry.argtypes = [C.POINTER(Forecast), C.POINTER(ForecastSrc), C.POINTER(Q16Src), vp]
+        entry.restype = i32
     lib.nlam_grad_sumsq_workspace_doubles.argtypes = [i64]
     lib.nlam_grad_sumsq_workspace_doubles.restype = i64
     lib.nlam_grad_sumsq.argtypes = [vp, i64, vp, i64, f32, vp, vp]

@@ -7604,3 +7604,6 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 #if NLAM_IN_TU(6)
 #include "nlam_gemm.inc"
 #endif
+
+// packed int16 series: its sections pick their own slices (5 beside the window and moments kernels, 1 beside the forecast pair)
+#include "nlam_packed.inc"

@@ -16,6 +16,11 @@ with or without an ensemble-member axis.  Plain analysis series (no member axis 
 lead times a sample can read stay resident -- ``max(2, past) + ar_steps`` for the state, ``+ future`` for the forcing --
 and host arrays (numpy memmaps included) are uploaded in chunks of analysis times, so the host never holds more than one
 chunk and HBM never holds the unread tail of the forecasts.
+
+``storage="int16"`` keeps the series as packed 16-bit codes with a per-feature ``scale`` / ``offset`` (the packing of GRIB
+and packed netCDF), half the bytes of fp32: float series are packed on upload (exact range first, then the encoding, chunk
+by chunk), ``PackedSeries`` hands over codes that are packed already.  ``nlam_window_batch_q16`` decodes them in the batch
+launch, so the batches are fp32 as ever and carry the bits of an fp32 dataset holding the decoded series.
 """
 from __future__ import annotations
 
@@ -149,6 +154,138 @@ def _resident(x, dev, steps, member_axis, keep_members):
     return out
 
 
+class PackedSeries:
+    """A series that is already packed, as GRIB and packed netCDF archives ship it: ``values`` int16 of the usual shape
+    (``(time, [member], N, F)`` or ``(analysis_time, elapsed, [member], N, F)``; numpy, memmap, torch CPU or device tensor)
+    with the per-feature fp32 tables of the archive, ``x = float32(q) * scale[f] + offset[f]`` (two fp32 roundings).  It is
+    uploaded as it is, with no float pass.  TypeError unless ``values`` is int16; ValueError unless both tables hold ``F``
+    finite entries and every ``scale > 0``.  The code -32768 has no special meaning (fill gaps before packing)."""
+
+    def __init__(self, values, scale, offset):
+        if not hasattr(values, "shape"):
+            values = np.asarray(values)
+        if str(values.dtype).replace("torch.", "") != "int16":
+            raise TypeError(f"PackedSeries: values must be int16, got {values.dtype}")
+        if len(values.shape) < 1:
+            raise ValueError("PackedSeries: values must have a feature axis")
+        F = int(values.shape[-1])
+        tabs = []
+        for name, t in (("scale", scale), ("offset", offset)):
+            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            if a.shape != (F,):
+                raise ValueError(f"PackedSeries: {name} must have one entry per feature ({F}), got {a.size}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"PackedSeries: {name} must be finite")
+            tabs.append(a)
+        if not (tabs[0] > 0).all():
+            raise ValueError("PackedSeries: scale must be > 0 for every feature")
+        self.values, self.scale, self.offset = values, tabs[0], tabs[1]
+
+    @property
+    def shape(self):
+        return tuple(self.values.shape)
+
+
+def default_tables(lo, hi):
+    """The decode tables of features with the exact ranges ``[lo, hi]`` (float64 on the host): ``offset = fp32((hi + lo) / 2)``,
+    ``scale = fp32((hi - lo) / 65534)``, so the extrema land on the codes -+32767.  A constant feature gets ``scale = 1`` and
+    its value as the offset (it round-trips exactly); so does a range so small that its scale underflows fp32."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        offset = ((hi + lo) / 2).astype(np.float32)
+        scale = ((hi - lo) / 65534).astype(np.float32)
+    flat = ~(scale > 0)
+    scale[flat] = 1.0
+    offset[flat & (hi == lo)] = lo[flat & (hi == lo)].astype(np.float32)
+    return scale, offset
+
+
+def _cut(x, steps, member_axis, keep_members):
+    """(index of the axes behind the leading one, resident shape) of the part of ``x`` a sample can read: ``_resident``'s cut."""
+    sl = [slice(None)] * len(x.shape)
+    if steps is not None:
+        sl[1] = slice(0, steps)
+    if member_axis is not None and not keep_members:
+        sl[member_axis] = 0
+    rest = tuple(sl[1:])
+    n0 = int(x.shape[0])
+    shape = (n0,) + tuple(len(range(*r.indices(int(d)))) for d, r in zip(x.shape[1:], rest) if isinstance(r, slice))
+    return rest, shape
+
+
+def _pieces(x, dev, rest, shape, dtype):
+    """``(a0, a1, chunk)``: the resident part of ``x`` in contiguous device chunks of its leading axis, each of at most
+    UPLOAD_CHUNK_BYTES in ``dtype`` (``_resident``'s chunks); a host array is converted and copied chunk by chunk."""
+    np_dtype = {torch.float32: np.float32, torch.int16: np.int16}[dtype]
+    row_bytes = np.dtype(np_dtype).itemsize * max(1, int(np.prod(shape[1:], dtype=np.int64)))
+    step = max(1, int(UPLOAD_CHUNK_BYTES) // row_bytes)
+    for a0 in range(0, shape[0], step):
+        a1 = min(shape[0], a0 + step)
+        piece = x[(slice(a0, a1),) + rest]
+        if isinstance(piece, torch.Tensor):
+            piece = piece.to(dtype).contiguous().to(dev)
+        else:
+            piece = np.ascontiguousarray(piece, dtype=np_dtype)
+            if not piece.flags.writeable:   # a read-only memmap chunk: torch.from_numpy wants writable memory
+                piece = piece.copy()
+            piece = torch.from_numpy(piece).to(dev)
+        yield a0, a1, piece
+
+
+def _resident_q16(name, x, dev, steps, member_axis, keep_members, lib):
+    """``_resident`` for packed storage: ``(values int16, scale, offset)`` on ``dev``.  A ``PackedSeries`` is cut and uploaded
+    as it is.  A float series takes two passes over the chunks of its leading axis -- ``nlam_series_range`` merges the exact
+    per-feature range, then ``nlam_series_pack_q16`` encodes with the tables of that range -- so the host never holds more than
+    one chunk and the device never an fp32 copy of more than one.  ValueError (before anything is stored) for a non-finite value."""
+    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
+    if isinstance(x, PackedSeries):
+        rest, shape = _cut(x.values, steps, member_axis, keep_members)
+        out = torch.empty(shape, dtype=torch.int16, device=dev)
+        for a0, a1, piece in _pieces(x.values, dev, rest, shape, torch.int16):
+            out[a0:a1].copy_(piece)
+        return out, torch.from_numpy(x.scale.copy()).to(dev), torch.from_numpy(x.offset.copy()).to(dev)
+    if not hasattr(x, "shape"):
+        x = np.asarray(x, dtype=np.float32)
+    rest, shape = _cut(x, steps, member_axis, keep_members)
+    F = int(shape[-1])
+    if F > L.MOMENTS_MAX_VARS:
+        raise ValueError(f"{name}: {F} features; the range kernel of storage='int16' takes at most {L.MOMENTS_MAX_VARS}")
+    with torch.cuda.device(dev):
+        lo = torch.full((F,), float("inf"), device=dev, dtype=torch.float32)
+        hi = torch.full((F,), float("-inf"), device=dev, dtype=torch.float32)
+        bad = torch.zeros((F,), device=dev, dtype=torch.int64)
+        ws = None
+        for _, _, piece in _pieces(x, dev, rest, shape, torch.float32):
+            rows = piece.numel() // F
+            if rows == 0:
+                continue
+            words = int(lib.nlam_series_range_workspace_words(rows, F))
+            if ws is None or ws.numel() < words:
+                ws = torch.empty((words,), device=dev, dtype=torch.int32)
+            L.check(lib.nlam_series_range(_ptr(piece), rows, F, _ptr(lo), _ptr(hi), _ptr(bad), _ptr(ws), ws.numel(), stream()),
+                    "nlam_series_range")
+        bad_host = bad.cpu().numpy()
+        if bad_host.any():
+            f = int(np.flatnonzero(bad_host)[0])
+            raise ValueError(f"storage='int16': the {name} series holds non-finite values ({int(bad_host[f])} in feature {f}, the "
+                             "first of them); fill gaps before packing -- the format has no missing-value code")
+        if ws is None:   # no element at all
+            scale, offset = np.ones(F, np.float32), np.zeros(F, np.float32)
+        else:
+            scale, offset = default_tables(lo.cpu().numpy(), hi.cpu().numpy())
+        scale, offset = torch.from_numpy(scale).to(dev), torch.from_numpy(offset).to(dev)
+        out = torch.empty(shape, dtype=torch.int16, device=dev)
+        per = int(np.prod(shape[1:], dtype=np.int64))
+        for a0, _, piece in _pieces(x, dev, rest, shape, torch.float32):
+            rows = piece.numel() // F
+            if rows:
+                L.check(lib.nlam_series_pack_q16(_ptr(piece), rows, F, _ptr(scale), _ptr(offset), _ptr(out), a0 * per, stream()),
+                        "nlam_series_pack_q16")
+            del piece
+    return out, scale, offset
+
+
 def _ns(x, dev):
     """int64 nanoseconds on ``dev`` from int64 / numpy datetime64 / timedelta64 stamps."""
     if not isinstance(x, torch.Tensor):
@@ -180,11 +317,20 @@ class DeviceWeatherDataset:
     ForecasterModule registers, module.py:159-215, std already clamped) for ``batch(..., standardize=True)``.
     ``kernel`` names the C entry that cuts the batches: ``"nlam_window_batch"`` for plain analysis series,
     ``"nlam_window_batch_ens"`` otherwise (the strided entry may be selected for any layout; it gives the same samples).
+    storage: ``"float32"`` (default) keeps float series as fp32; ``"int16"`` packs them on upload with the tables of each
+    feature's exact range (``default_tables``; ValueError for a non-finite value, before anything is stored).  A
+    ``PackedSeries`` for ``state`` and / or ``forcing`` is kept packed under either setting, so one series may be packed and
+    the other fp32.  With a packed series ``kernel`` is ``"nlam_window_batch_q16"`` (every layout), ``state`` / ``forcing`` are
+    the int16 tensors, ``state_scale`` / ``state_offset`` / ``forcing_scale`` / ``forcing_offset`` the fp32 decode tables on the
+    device (None for an fp32 series), ``resident_bytes`` the HBM the series take and ``decoded()`` the fp32 series they stand for.
     """
 
     def __init__(self, state, forcing=None, times=None, ar_steps=3, num_past_forcing_steps=1, num_future_forcing_steps=1,
-                 standardization=None, device="cuda", is_forecast=False, elapsed=None, load_single_member=False):
+                 standardization=None, device="cuda", is_forecast=False, elapsed=None, load_single_member=False,
+                 storage="float32"):
         dev = torch.device(device)
+        if storage not in ("float32", "int16"):
+            raise ValueError(f"storage must be 'float32' or 'int16', got {storage!r}")
         if dev.type != "cuda":
             raise RuntimeError("DeviceWeatherDataset keeps its series in HBM and cuts samples with a HIP kernel: it needs a GPU "
                                "(there is no CPU fallback; the CPU restatement lives in oracle/data.py for the tests)")
@@ -203,12 +349,21 @@ class DeviceWeatherDataset:
             raise ValueError("elapsed is the lead-time axis of forecast data (is_forecast=True)")
         s_shape = _shape(state)
         m_ax = len(s_shape) - 3
-        self.state = _resident(state, dev, lay.state_steps, m_ax if lay.state_members is not None else None, lay.keep_state_members)
+        self._lib = L.load()
+        self.state_scale = self.state_offset = self.forcing_scale = self.forcing_offset = None
+
+        def resident(name, x, steps, member_axis, keep):   # (series, scale, offset): fp32 as ever, or packed int16 with its tables
+            if storage == "int16" or isinstance(x, PackedSeries):
+                return _resident_q16(name, x, dev, steps, member_axis, keep, self._lib)
+            return _resident(x, dev, steps, member_axis, keep), None, None
+
+        self.state, self.state_scale, self.state_offset = resident(
+            "state", state, lay.state_steps, m_ax if lay.state_members is not None else None, lay.keep_state_members)
         self.forcing = None
         if forcing is not None and _shape(forcing)[-1] > 0:
             f_ax = len(_shape(forcing)) - 3
-            self.forcing = _resident(forcing, dev, lay.forcing_steps, f_ax if lay.forcing_members is not None else None,
-                                     lay.keep_forcing_members)
+            self.forcing, self.forcing_scale, self.forcing_offset = resident(
+                "forcing", forcing, lay.forcing_steps, f_ax if lay.forcing_members is not None else None, lay.keep_forcing_members)
         self.times = None if times is None else _ns(times, dev)
         if self.times is not None and self.times.shape != (s_shape[0],):
             raise ValueError("times must have one entry per state time step" if not self.is_forecast else
@@ -222,9 +377,10 @@ class DeviceWeatherDataset:
         self.members = lay.members
         self._nodes, self._d_state = int(s_shape[-2]), int(s_shape[-1])
         self.device = dev
-        self._lib = L.load()
         plain = not self.is_forecast and self.state.dim() == 3 and (self.forcing is None or self.forcing.dim() == 3)
         self.kernel = "nlam_window_batch" if plain else "nlam_window_batch_ens"
+        if self.state_scale is not None or self.forcing_scale is not None:
+            self.kernel = "nlam_window_batch_q16"   # any layout: the strided entry with the decode in flight
         if plain:
             n_forc = -1 if self.forcing is None else self.forcing.shape[0]
             self._len = int(self._lib.nlam_window_len(self.state.shape[0], n_forc, self.ar_steps, self.num_past_forcing_steps,
@@ -251,6 +407,30 @@ class DeviceWeatherDataset:
 
     def __len__(self):
         return self._len
+
+    # ---- packed storage ----
+    @property
+    def storage(self):
+        """``"float32"``, ``"int16"`` (every resident series packed) or ``"mixed"`` (one of state and forcing packed)."""
+        packed = [sc is not None for x, sc in ((self.state, self.state_scale), (self.forcing, self.forcing_scale)) if x is not None]
+        return "int16" if all(packed) else "mixed" if any(packed) else "float32"
+
+    @property
+    def resident_bytes(self):
+        """Bytes of HBM the resident series take (the decode tables, time stamps and statistics are not counted)."""
+        return sum(x.numel() * x.element_size() for x in (self.state, self.forcing) if x is not None)
+
+    def decoded(self, series="state"):
+        """The fp32 series the resident ``series`` (``"state"`` or ``"forcing"``) stands for: ``float32(q) * scale + offset``
+        with two fp32 roundings, the kernels' decode; an fp32 series is returned as it is, a missing forcing as None.  A
+        FULL-SIZE fp32 allocation (plus a temporary of the same size): for tests and debugging on small datasets only."""
+        if series not in ("state", "forcing"):
+            raise ValueError(f"series must be 'state' or 'forcing', got {series!r}")
+        x, scale, offset = ((self.state, self.state_scale, self.state_offset) if series == "state" else
+                            (self.forcing, self.forcing_scale, self.forcing_offset))
+        if x is None or scale is None:
+            return x
+        return torch.add(torch.mul(x.to(torch.float32), scale), offset)   # two launches: the product is rounded before the sum
 
     def __getitem__(self, idx):
         """One UNSTANDARDISED sample, as the reference's dataset returns it (:479-480)."""
@@ -311,9 +491,12 @@ class DeviceWeatherDataset:
         if standardize and self.stats is None:
             raise ValueError("standardize=True needs the standardization statistics (constructor argument)")
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if self.kernel == "nlam_window_batch_ens":
+        if self.kernel in ("nlam_window_batch_ens", "nlam_window_batch_q16"):
             self._launch_ens(indices, init, target, forcing if fw else None, times, standardize, stream)
             return init, target, forcing, times
+        if self.state_scale is not None or self.forcing_scale is not None:
+            raise TypeError(f"kernel {self.kernel!r} reads fp32 series: this dataset has storage={self.storage!r} and is cut by "
+                            "'nlam_window_batch_q16'")
         if self.kernel != "nlam_window_batch" or self.state.dim() != 3 or self.is_forecast:
             raise ValueError(f"kernel {self.kernel!r}: nlam_window_batch cuts plain analysis series only")
         p = L.Window()
@@ -332,9 +515,18 @@ class DeviceWeatherDataset:
         return init, target, forcing, times
 
     def _launch_ens(self, indices, init, target, forcing, times, standardize, stream):
-        """nlam_window_batch_ens over the resident series: strides in floats from the tensors' own layout."""
+        """nlam_window_batch_ens over the resident series: strides in elements (floats, or int16 of a packed series) from the
+        tensors' own layout.  With a packed series the launch is nlam_window_batch_q16 and that series rides in its own struct."""
         p = L.WindowEns()
-        p.state, p.forcing, p.sample_idx = _ptr(self.state), _ptr(self.forcing), _ptr(indices)
+        q = None
+        if self.state_scale is not None or self.forcing_scale is not None:
+            if self.kernel != "nlam_window_batch_q16":
+                raise TypeError(f"kernel {self.kernel!r} reads fp32 series: this dataset has storage={self.storage!r} and is cut by "
+                                "'nlam_window_batch_q16'")
+            q = self.packed_source()
+        p.state = None if self.state_scale is not None else _ptr(self.state)
+        p.forcing = None if self.forcing_scale is not None else _ptr(self.forcing)
+        p.sample_idx = _ptr(indices)
         p.init_states, p.target_states, p.forcing_windowed = _ptr(init), _ptr(target), _ptr(forcing)
         # no time stamps: the kernel reports the time index (analysis) or the lead-time index (forecast) of every target step
         p.times, p.elapsed, p.target_times = _ptr(self.times), _ptr(self.elapsed), _ptr(times)
@@ -359,7 +551,19 @@ class DeviceWeatherDataset:
         p.nodes, p.d_state, p.batch = self._nodes, self._d_state, indices.numel()
         p.d_forcing = 0 if self.forcing is None else self.forcing.shape[-1]
         p.ar_steps, p.num_past_forcing_steps, p.num_future_forcing_steps = self.ar_steps, self.num_past_forcing_steps, self.num_future_forcing_steps
+        if q is not None:
+            L.check(self._lib.nlam_window_batch_q16(C.byref(p), C.byref(q), stream), "nlam_window_batch_q16")
+            return
         L.check(self._lib.nlam_window_batch_ens(C.byref(p), stream), "nlam_window_batch_ens")
+
+    def packed_source(self):
+        """The ``nlam_q16_src_t`` of the resident series: the packed ones with their tables, NULL for an fp32 series."""
+        q = L.Q16Src()
+        if self.state_scale is not None:
+            q.state, q.state_scale, q.state_offset = _ptr(self.state), _ptr(self.state_scale), _ptr(self.state_offset)
+        if self.forcing is not None and self.forcing_scale is not None:
+            q.forcing, q.forcing_scale, q.forcing_offset = _ptr(self.forcing), _ptr(self.forcing_scale), _ptr(self.forcing_offset)
+        return q
 
     def epoch_permutation(self, seed=0):
         """A resident random permutation of the sample indices: ``perm[k * B : (k + 1) * B]`` feeds ``batch`` with no host copy."""

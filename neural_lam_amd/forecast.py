@@ -73,9 +73,12 @@ def plan_forecast_dataset(layout, num_past_forcing_steps, num_future_forcing_ste
 def dataset_source(dataset, sample_idx):
     """The ``nlam_forecast_src_t`` of a ``DeviceWeatherDataset``'s resident series: the strides in floats from the tensors' own
     layout, as its ``nlam_window_batch_ens`` launch takes them.  ``sample_idx``: the device int64 tensor of flat sample indices
-    the launches read (kept alive by the caller)."""
+    the launches read (kept alive by the caller).  A packed series (``storage="int16"``) leaves its float pointer NULL and its
+    strides count int16 elements: it rides in ``dataset.packed_source()`` beside this struct, for the ``_q16`` pair."""
     s = L.ForecastSrc()
-    s.state, s.forcing, s.sample_idx = _ptr(dataset.state), _ptr(dataset.forcing), _ptr(sample_idx)
+    s.state = None if getattr(dataset, "state_scale", None) is not None else _ptr(dataset.state)
+    s.forcing = None if getattr(dataset, "forcing_scale", None) is not None else _ptr(dataset.forcing)
+    s.sample_idx = _ptr(sample_idx)
     lead_ax = 1 if dataset.is_forecast else 0
 
     def strides(x):   # (sample, step, member); member stride 0 without a member axis
@@ -185,7 +188,11 @@ class Forecast:
                              "NLAM_FUSED_CLAMPED_TAIL on for output clamps or a predicted std; Graph-EFM is not served)")
         from .data import DeviceWeatherDataset
 
-        strided = isinstance(dataset, DeviceWeatherDataset) and dataset.kernel == "nlam_window_batch_ens"
+        packed = isinstance(dataset, DeviceWeatherDataset) and dataset.storage != "float32"
+        strided = isinstance(dataset, DeviceWeatherDataset) and (packed or dataset.kernel == "nlam_window_batch_ens")
+        if packed and dataset.kernel != "nlam_window_batch_q16":
+            raise TypeError(f"Forecast: dataset.kernel {dataset.kernel!r} reads fp32 series, but the dataset has storage="
+                            f"{dataset.storage!r} (its kernel is 'nlam_window_batch_q16')")
         if not strided and getattr(dataset, "kernel", None) != "nlam_window_batch":
             raise ValueError("Forecast reads a DeviceWeatherDataset (any layout) or plain analysis series (dataset.kernel == "
                              "'nlam_window_batch'): other forecast-type and ensemble datasets are not served")
@@ -195,6 +202,10 @@ class Forecast:
         dev = getattr(getattr(dataset, "state", None), "device", dataset.device)   # with its index: "cuda" names the current device
         if dev.type != "cuda" or any(p.device != dev for p in predictor.parameters()) or step.state_mean.device != dev:
             raise RuntimeError(f"Forecast runs on the GPU that holds the dataset ({dev}): move the step there (there is no CPU fallback)")
+        if not packed and any(x is not None and x.dtype != torch.float32 for x in (getattr(dataset, "state", None),
+                                                                                   getattr(dataset, "forcing", None))):
+            raise TypeError("Forecast: the plain and strided entries read fp32 series; packed int16 series come from a "
+                            "DeviceWeatherDataset built with storage='int16' or from data.PackedSeries")
         self.step, self.dataset, self.predictor = step, dataset, predictor
         self.verify, self.use_graph, self.autocast_dtype = bool(verify), bool(use_graph), autocast_dtype
         self.past, self.future = dataset.num_past_forcing_steps, dataset.num_future_forcing_steps
@@ -249,7 +260,11 @@ class Forecast:
         p.max_lead, p.num_past_forcing_steps, p.num_future_forcing_steps = Lm, self.past, self.future
         p.delta_ld = 2 * F if self.has_std else F
         self._p = p
-        self._src = None
+        self._src = self._packed = None
+        if packed:
+            # every layout of a packed dataset, the plain one included, goes through the strided pair with the decode in flight;
+            # p.state / p.forcing only satisfy the tail's argument check (no launch reads a series through them)
+            self._packed = dataset.packed_source()
         if strided:
             # the head and init read the series through the dataset's own strides (they ignore p.state / p.forcing / p.start, which
             # the tail's argument check still wants); the tail's valid-time arithmetic is a plain series': computed per run (_replay)
@@ -265,6 +280,10 @@ class Forecast:
         from .ops import _stream
 
         if self._src is not None and name in ("nlam_forecast_init", "nlam_forecast_head"):
+            if self._packed is not None:
+                name += "_q16"
+                L.check(getattr(self._lib, name)(C.byref(self._p), C.byref(self._src), C.byref(self._packed), _stream()), name)
+                return
             name += "_strided"
             L.check(getattr(self._lib, name)(C.byref(self._p), C.byref(self._src), _stream()), name)
             return

@@ -95,9 +95,25 @@ def plan_statistics(layout: StatsLayout, *, step_length=3, flux_index=0, batch_s
                      flux_batches=tuple((b, min(n, b + bs)) for b in range(0, n, bs)))
 
 
+def _decode_tables(ds, x):
+    """(scale, offset) of resident series ``x`` of ``ds`` when it is packed int16, None for an fp32 series; TypeError for
+    anything else (the moments kernels read fp32, or int16 with the dataset's own tables)."""
+    if x.dtype == torch.float32:
+        return None
+    for series, scale, offset in ((getattr(ds, "state", None), getattr(ds, "state_scale", None), getattr(ds, "state_offset", None)),
+                                  (getattr(ds, "forcing", None), getattr(ds, "forcing_scale", None),
+                                   getattr(ds, "forcing_offset", None))):
+        if x is series and x.dtype == torch.int16 and scale is not None:
+            return scale, offset
+    raise TypeError(f"the moments kernels read an fp32 series, or a packed int16 series of the dataset itself (storage="
+                    f"{getattr(ds, 'storage', 'float32')!r}); got a {x.dtype} tensor")
+
+
 def _moments(ds, x, first, count, row_begin, nrows, step=0, mean=None, std=None):
     """nlam_window_moments over samples [first, first + count) of resident series ``x`` of dataset ``ds``: two fresh
-    float64 device tensors (count * max(step, 1), F), per-row means and second moments."""
+    float64 device tensors (count * max(step, 1), F), per-row means and second moments.  A packed series (``ds.state`` /
+    ``ds.forcing`` of a ``storage="int16"`` dataset) goes through nlam_window_moments_q16 with the dataset's decode tables."""
+    tables = _decode_tables(ds, x)
     S, F = max(step, 1), int(x.shape[-1])
     o = dict(device=ds.device, dtype=torch.float64)
     out_mean, out_sq = torch.empty((count * S, F), **o), torch.empty((count * S, F), **o)
@@ -111,20 +127,25 @@ def _moments(ds, x, first, count, row_begin, nrows, step=0, mean=None, std=None)
     ws = torch.empty(n_ws, **o)
     lead = 1 if ds.is_forecast else 0
     p = L.Moments()
-    p.series, p.workspace = C.c_void_p(x.data_ptr()), C.c_void_p(ws.data_ptr())
+    p.series = C.c_void_p(x.data_ptr()) if tables is None else None
+    p.workspace = C.c_void_p(ws.data_ptr())
     p.out_mean, p.out_sq = C.c_void_p(out_mean.data_ptr()), C.c_void_p(out_sq.data_ptr())
     if step:
         p.mean, p.std = C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr())
     p.workspace_doubles = n_ws
-    # (sample, step, member) strides in floats, as DeviceWeatherDataset._launch_ens; member stride 0 without a member axis
+    # (sample, step, member) strides in elements, as DeviceWeatherDataset._launch_ens; member stride 0 without a member axis
     p.stride_sample, p.stride_step = x.stride(0), x.stride(lead)
     p.stride_member = x.stride(lead + 1) if x.dim() == 4 + lead else 0
     p.n_times, p.first, p.count = ds.layout.n_times, first, count
     p.is_forecast, p.members = int(ds.is_forecast), ds.members
     p.steps = x.shape[1] if ds.is_forecast else 0
     p.nodes, p.nvars, p.row_begin, p.nrows, p.step = nodes, F, row_begin, nrows, step
-    L.check(lib.nlam_window_moments(C.byref(p), C.c_void_p(torch.cuda.current_stream(ds.device).cuda_stream)),
-            "nlam_window_moments")
+    stream = C.c_void_p(torch.cuda.current_stream(ds.device).cuda_stream)
+    if tables is not None:
+        L.check(lib.nlam_window_moments_q16(C.byref(p), C.c_void_p(x.data_ptr()), C.c_void_p(tables[0].data_ptr()),
+                                            C.c_void_p(tables[1].data_ptr()), stream), "nlam_window_moments_q16")
+        return out_mean, out_sq
+    L.check(lib.nlam_window_moments(C.byref(p), stream), "nlam_window_moments")
     return out_mean, out_sq
 
 

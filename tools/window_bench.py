@@ -6,10 +6,14 @@ Cases:
   analysis_m2   analysis series, 2 members: nlam_window_batch_ens
   forecast_m2   forecast series, 2 members, 65 lead times given (3 / 4 kept resident): nlam_window_batch_ens
 
-Each launch is timed as 50 launches replayed from one HIP graph between two HIP events (the Python call is longer than
-the kernel).  Bytes come from shapes: every output float is read once and written once, 2 * 4 * output floats.
+Every case runs on fp32 series and on the same series packed as int16 (storage="int16": nlam_window_batch_q16), back to back
+in one process; --storage picks one of the two.
 
-  python tools/window_bench.py [--case all|analysis_m1|analysis_m2|forecast_m2] [--reps 50] [--out F.json]
+Each launch is timed as 50 launches replayed from one HIP graph between two HIP events (the Python call is longer than
+the kernel).  Bytes come from shapes: every output float is read once (4 bytes from an fp32 series, 2 from a packed one) and
+written once.  ``resident_bytes`` is what the case's series take in HBM in that storage.
+
+  python tools/window_bench.py [--case all|analysis_m1|analysis_m2|forecast_m2] [--storage both|float32|int16] [--reps 50] [--out F.json]
 Under ``rocprofv3 --kernel-trace --stats -- python tools/window_bench.py --case analysis_m1`` the two kernels of the
 single-member case are listed side by side.
 """
@@ -50,13 +54,14 @@ def time_launch(ds, idx, reps):
         e1.record()
         torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1) / reps * 1e3)
-    nbytes = 2 * 4 * sum(t.numel() for t in outs[:3])
-    return {"kernel": ds.kernel, "us": best, "bytes": nbytes, "GBps": nbytes / best * 1e-3}
+    per_float = 4 + (2 if ds.storage == "int16" else 4)
+    nbytes = per_float * sum(t.numel() for t in outs[:3])
+    return {"kernel": ds.kernel, "storage": ds.storage, "us": best, "bytes": nbytes, "GBps": nbytes / best * 1e-3}
 
 
-def make(case, dev):
+def make(case, dev, storage="float32"):
     gen = torch.Generator(device=dev).manual_seed(7)
-    kw = dict(ar_steps=T, num_past_forcing_steps=PAST, num_future_forcing_steps=FUT, standardization=stats())
+    kw = dict(ar_steps=T, num_past_forcing_steps=PAST, num_future_forcing_steps=FUT, standardization=stats(), storage=storage)
     if case == "analysis_m1":
         return DeviceWeatherDataset(torch.randn(24, N, NS, device=dev, generator=gen), torch.randn(24, N, NF, device=dev, generator=gen),
                                     None, **kw)
@@ -75,6 +80,7 @@ def make(case, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="all", choices=["all", "analysis_m1", "analysis_m2", "forecast_m2"])
+    ap.add_argument("--storage", default="both", choices=["both", "float32", "int16"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -82,20 +88,24 @@ def main():
     cases = ["analysis_m1", "analysis_m2", "forecast_m2"] if args.case == "all" else [args.case]
     res = {"shape": {"nodes": N, "d_state": NS, "d_forcing": NF, "batch": B, "ar_steps": T, "window": PAST + FUT + 1},
            "device": torch.cuda.get_device_name(0), "cases": {}}
+    storages = ["float32", "int16"] if args.storage == "both" else [args.storage]
     for case in cases:
-        ds = make(case, dev)
-        idx = ds.epoch_permutation(seed=0)[:B]
-        rows = []
-        if case == "analysis_m1":
+        rows, resident = [], {}
+        for storage in storages:
+            ds = make(case, dev, storage)
+            idx = ds.epoch_permutation(seed=0)[:B]
+            if case == "analysis_m1" and storage == "float32":
+                rows.append(time_launch(ds, idx, args.reps))
+                ds.kernel = "nlam_window_batch_ens"
             rows.append(time_launch(ds, idx, args.reps))
-            ds.kernel = "nlam_window_batch_ens"
-        rows.append(time_launch(ds, idx, args.reps))
-        res["cases"][case] = {"resident_state": list(ds.state.shape), "resident_forcing": list(ds.forcing.shape),
-                              "len": len(ds), "launches": rows}
+            resident[storage] = ds.resident_bytes
+            res["cases"][case] = {"resident_state": list(ds.state.shape), "resident_forcing": list(ds.forcing.shape),
+                                  "len": len(ds), "launches": rows, "resident_bytes": resident}
+            del ds
+            torch.cuda.empty_cache()
         for r in rows:
-            print(f"{case:12s} {r['kernel']:22s} {r['us']:8.2f} us  {r['GBps']:7.1f} GB/s  ({r['bytes'] / 1e6:.1f} MB)")
-        del ds
-        torch.cuda.empty_cache()
+            print(f"{case:12s} {r['storage']:8s} {r['kernel']:22s} {r['us']:8.2f} us  {r['GBps']:7.1f} GB/s  ({r['bytes'] / 1e6:.1f} MB)")
+        print(f"{case:12s} resident bytes: " + ", ".join(f"{k} {v}" for k, v in resident.items()))
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
