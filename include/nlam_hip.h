@@ -62,6 +62,9 @@
  *       sampled ensembles inside that recorded step (Graph-EFM): the reparameterised draw of the latent variable from a
  *       counter-based generator keyed by the lead counter, and the ensemble verification of every lead (ensemble-mean error,
  *       spread, the two terms of fair CRPS, rank histogram, mean and spread fields) as one reduction over the member axis.
+ *   nlam_ens_products, nlam_ens_products_workspace_floats
+ *       what the ensemble is made for, per lead of that step: exceedance probabilities of threshold events and quantile fields
+ *       from the sorted members, with Brier score, reliability table, pinball loss and coverage counts.
  *   nlam_latent_kl_fwd, nlam_latent_kl_bwd, nlam_latent_kl_workspace_floats
  *       the variational training objective of Graph-EFM: the reparameterised posterior draw from that generator and the KL
  *       divergence from the prior as one pass with a fixed-order reduction, and its elementwise backward.
@@ -1145,6 +1148,68 @@ int32_t nlam_ens_scores(const nlam_ens_scores_t* p, void* hip_stream);
 /* floats of nlam_ens_scores_t.workspace; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP for members > NLAM_ENS_MAX_MEMBERS or
  * nvars > NLAM_EVAL_MAX_VARS */
 int64_t nlam_ens_scores_workspace_floats(int32_t starts, int32_t members, int32_t nodes, int32_t nvars);
+
+/* Exceedance probabilities and quantile fields of the same ensemble, and their scores, for lead slot k = *lead (only read; nothing
+ * is written once k >= max_lead): after nlam_ens_scores, before nlam_forecast_finish.  prev / truth / row_weight / state_mean /
+ * state_std as in nlam_ens_scores_t; truth may be NULL.  E = events, Q = quantiles, M = members, x_(0) <= ... <= x_(M-1) the
+ * sorted members of one element, y its truth, w_n = row_weight[n], "live" = w_n != 0.  Every table is device memory, read by the
+ * launch: a replay sees new values.
+ *   event e     variable event_var[e]; x is in the event when x > event_thr[e] (event_sense[e] = 0) or x < event_thr[e]
+ *               (event_sense[e] = 1); equality never counts.  Thresholds are in standardised units.
+ *   quantile j  level q = q_level[j] with i = q_index[j] = floor(q (M - 1)) and g = q_frac[j] = q (M - 1) - i, both computed by
+ *               the caller in float64: the launch does no arithmetic on q but the 1 - q of the pinball loss.
+ *                 Q_j = x_(i) + g (x_(min(i + 1, M - 1)) - x_(i))                 numpy's default (linear) quantile
+ *               The members are ordered as sign-magnitude bit patterns: -0 below +0, a NaN member at the end its sign puts it,
+ *               so the quantiles that reach it are NaN.
+ *   prob[s][k][e][n]      = (float)c / (float)M, c = the members of variable event_var[e] at node n in the event
+ *   quant[s][k][j][n][f]  = Q_j * state_std[f] + state_mean[f]
+ * and with truth given, o = 1 when the truth is in the event, else 0:
+ *   brier[s][k][e]        = sum_n w_n (c / M - o)^2
+ *   rel_count[s][k][e][c] = the live nodes with exactly c members in the event, c = 0 .. M;  rel_obs: those of them with o = 1
+ *   pinball[s][k][j][f]   = sum_n w_n rho,  rho = q (y - Q_j) for y >= Q_j, else (1 - q) (Q_j - y)        standardised units
+ *   below[s][k][j][f]     = the live nodes with y < Q_j
+ * With truth == NULL the five score pointers must be NULL and only prob and quant are written.  Per-(start, chunk) partial sums
+ * in the workspace, one finishing launch (with truth only) that adds them in a fixed order: no floating-point atomics,
+ * bit-identical from run to run.  The ranges of event_var ([0, d_state)), event_sense ({0, 1}) and q_index ([0, members)) are the
+ * caller's to check: the launch clamps the two indices into range and treats any non-zero sense as 1.
+ * NLAM_EINVAL for null required pointers (prev, row_weight, state_mean, state_std, lead, workspace), sizes < 1, events or
+ * quantiles < 0 or both 0, events > 0 without its three tables and prob, quantiles > 0 without its three tables and quant, a short
+ * workspace, a score pointer without truth, truth without brier / rel_count / rel_obs (events > 0) or pinball / below
+ * (quantiles > 0); NLAM_EUNSUP for members > NLAM_ENS_MAX_MEMBERS, d_state > NLAM_EVAL_MAX_VARS, events > NLAM_ENS_MAX_EVENTS,
+ * quantiles > NLAM_ENS_MAX_QUANTILES, starts > 65535, nodes * d_state >= 2^31.  Every check comes before any launch; no
+ * allocation, no host synchronisation. */
+#define NLAM_ENS_MAX_EVENTS 32
+#define NLAM_ENS_MAX_QUANTILES 16
+typedef struct {
+    const float* prev;            /* (starts * members, nodes, d_state) standardised states of this lead */
+    const float* truth;           /* (starts * members, nodes, d_state) standardised analysis, or NULL: no scores */
+    const float* row_weight;      /* (nodes) */
+    const float* state_mean;      /* (d_state) */
+    const float* state_std;       /* (d_state) */
+    const int32_t* lead;          /* device (1): k, only read */
+    const int32_t* event_var;     /* device (events) */
+    const int32_t* event_sense;   /* device (events): 0 above, 1 below */
+    const float* event_thr;       /* device (events): standardised units */
+    const int32_t* q_index;       /* device (quantiles) */
+    const float* q_frac;          /* device (quantiles) */
+    const float* q_level;         /* device (quantiles) */
+    float* prob;                  /* (starts, max_lead, events, nodes) */
+    float* quant;                 /* (starts, max_lead, quantiles, nodes, d_state) physical units */
+    float* brier;                 /* (starts, max_lead, events) */
+    int32_t* rel_count;           /* (starts, max_lead, events, members + 1) */
+    int32_t* rel_obs;             /* (starts, max_lead, events, members + 1) */
+    float* pinball;               /* (starts, max_lead, quantiles, d_state) */
+    int32_t* below;               /* (starts, max_lead, quantiles, d_state) */
+    float* workspace;             /* nlam_ens_products_workspace_floats(starts, members, nodes, d_state, events, quantiles) floats */
+    int64_t workspace_floats;
+    int32_t starts, members, nodes, d_state;
+    int32_t max_lead, events, quantiles, _pad;
+} nlam_ens_products_t;
+int32_t nlam_ens_products(const nlam_ens_products_t* p, void* hip_stream);
+/* floats of nlam_ens_products_t.workspace; NLAM_EINVAL for sizes < 1, events or quantiles < 0 or both 0, NLAM_EUNSUP for members >
+ * NLAM_ENS_MAX_MEMBERS, nvars > NLAM_EVAL_MAX_VARS, events > NLAM_ENS_MAX_EVENTS or quantiles > NLAM_ENS_MAX_QUANTILES */
+int64_t nlam_ens_products_workspace_floats(int32_t starts, int32_t members, int32_t nodes, int32_t nvars, int32_t events,
+                                           int32_t quantiles);
 
 /* The posterior draw and the KL term of the Graph-EFM training objective (Oskarsson et al. 2024, section 3; models.EFMForecaster)
  * inside the recorded training step.  With D = latent_dim, u = 1e-4, pq (batch, rows, 2 D) the encoder's parameters (always

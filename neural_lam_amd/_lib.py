@@ -101,6 +101,8 @@ CLAMP_NONE, CLAMP_BOTH, CLAMP_LOWER, CLAMP_UPPER = 0, 1, 2, 3
 EVAL_MAX_MAPS = 32    # NLAM_EVAL_MAX_MAPS: lead times of one nlam_eval_metrics call's loss maps
 EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
 ENS_MAX_MEMBERS = 64  # NLAM_ENS_MAX_MEMBERS: members of one nlam_ens_scores call
+ENS_MAX_EVENTS = 32   # NLAM_ENS_MAX_EVENTS: threshold events of one nlam_ens_products call
+ENS_MAX_QUANTILES = 16   # NLAM_ENS_MAX_QUANTILES: quantile levels of one nlam_ens_products call
 MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
 # learning-rate schedules of nlam_adamw_step_controlled (NLAM_SCHED_*) and the words of its control block
 SCHED_KINDS = {"constant": 1, "warmup_cosine": 2, "warmup_linear": 3}
@@ -203,6 +205,8 @@ EXPORTS = [
     "nlam_latent_sample",
     "nlam_ens_scores",
     "nlam_ens_scores_workspace_floats",
+    "nlam_ens_products",
+    "nlam_ens_products_workspace_floats",
     "nlam_latent_kl_fwd",
     "nlam_latent_kl_bwd",
     "nlam_latent_kl_workspace_floats",
@@ -510,6 +514,42 @@ class EnsScores(C.Structure):
         ("nodes", C.c_int32),
         ("d_state", C.c_int32),
         ("max_lead", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class EnsProducts(C.Structure):
+    """nlam_ens_products_t: exceedance probabilities, quantile fields and their scores of one lead."""
+
+    _fields_ = [
+        ("prev", C.c_void_p),
+        ("truth", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("state_mean", C.c_void_p),
+        ("state_std", C.c_void_p),
+        ("lead", C.c_void_p),
+        ("event_var", C.c_void_p),
+        ("event_sense", C.c_void_p),
+        ("event_thr", C.c_void_p),
+        ("q_index", C.c_void_p),
+        ("q_frac", C.c_void_p),
+        ("q_level", C.c_void_p),
+        ("prob", C.c_void_p),
+        ("quant", C.c_void_p),
+        ("brier", C.c_void_p),
+        ("rel_count", C.c_void_p),
+        ("rel_obs", C.c_void_p),
+        ("pinball", C.c_void_p),
+        ("below", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("starts", C.c_int32),
+        ("members", C.c_int32),
+        ("nodes", C.c_int32),
+        ("d_state", C.c_int32),
+        ("max_lead", C.c_int32),
+        ("events", C.c_int32),
+        ("quantiles", C.c_int32),
         ("_pad", C.c_int32),
     ]
 
@@ -968,6 +1008,10 @@ def load():
     lib.nlam_ens_scores.restype = i32
     lib.nlam_ens_scores_workspace_floats.argtypes = [i32, i32, i32, i32]
     lib.nlam_ens_scores_workspace_floats.restype = i64
+    lib.nlam_ens_products.argtypes = [C.POINTER(EnsProducts), vp]
+    lib.nlam_ens_products.restype = i32
+    lib.nlam_ens_products_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.nlam_ens_products_workspace_floats.restype = i64
     lib.nlam_latent_kl_fwd.argtypes = [C.POINTER(LatentKl), vp]
     lib.nlam_latent_kl_fwd.restype = i32
     lib.nlam_latent_kl_bwd.argtypes = [C.POINTER(LatentKl), vp]

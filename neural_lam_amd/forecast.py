@@ -25,6 +25,13 @@ histogram, mean and spread fields).
     res = ens.run([0])              # EnsembleResult
     res.members                     # (S, M, L, N, F) physical units;  res.mean, res.spread (S, L, N, F)
     res.crps(step.state_std)        # (L, F) fair CRPS;  res.rmse(...), res.spread_skill(), res.rank_hist
+
+``events`` / ``quantiles`` add one more launch per lead (``nlam_ens_products``): the probability that a variable crosses a
+threshold and quantile fields, from the members sorted in registers, with their scores under ``verify``.
+
+    ens = EnsembleForecast(step, dataset, 40, members=16, events=[("t2m", "<", 273.15)], quantiles=[0.1, 0.5, 0.9])
+    pr = ens.run([0]).products      # EnsembleProducts: pr.prob (S, L, E, N), pr.quantile (S, L, Q, N, F)
+    pr.brier_score(), pr.reliability(), pr.pinball_loss(step.state_std), pr.coverage()
 """
 from __future__ import annotations
 
@@ -417,6 +424,97 @@ class Forecast:
                         self._one_lead()
 
 
+class EnsembleProducts(NamedTuple):
+    """Device tensors of ``nlam_ens_products`` for one ``EnsembleForecast.run``, cut to the ``leads`` that ran.  ``prob`` /
+    the event scores are None without ``events``, ``quantile`` / the quantile scores without ``quantiles``, all scores without
+    ``verify``.  Sums are in standardised units, the quantile fields in physical units."""
+    prob: Optional[torch.Tensor]        # (S, leads, E, N) fraction of the members in the event
+    quantile: Optional[torch.Tensor]    # (S, leads, Q, N, F) linear-interpolation quantiles of the members
+    brier: Optional[torch.Tensor]       # (S, leads, E) sum_n w_n (prob - o)^2
+    rel_count: Optional[torch.Tensor]   # (S, leads, E, M + 1) int32: live nodes with c members in the event
+    rel_obs: Optional[torch.Tensor]     # (S, leads, E, M + 1) int32: those of them where the truth is in it
+    pinball: Optional[torch.Tensor]     # (S, leads, Q, F) sum_n w_n rho_q(y - Q_q)
+    below: Optional[torch.Tensor]       # (S, leads, Q, F) int32: live nodes with the truth below the quantile
+    events: tuple                       # ((variable index, ">" or "<", threshold in physical units), ...)
+    levels: tuple                       # the quantile levels
+    n_members: int
+    n_live: int                         # nodes with a non-zero weight
+
+    def _scores(self, t, what):
+        if t is None:
+            raise ValueError(f"EnsembleProducts: {what} needs EnsembleForecast(..., verify=True) and the products it scores")
+        return t
+
+    def brier_score(self):
+        """(leads, E) Brier score of every event: the mean over the starts of ``brier``."""
+        return torch.mean(self._scores(self.brier, "brier_score"), dim=0)
+
+    def reliability(self):
+        """``(forecast probability (M + 1), observed frequency (leads, E, M + 1), counts (leads, E, M + 1))`` summed over the
+        starts: of the live nodes forecast ``c / M``, the fraction where the event happened (NaN for an empty bin)."""
+        count = self._scores(self.rel_count, "reliability").sum(0)
+        obs = self.rel_obs.sum(0)
+        fc = torch.arange(self.n_members + 1, device=count.device, dtype=torch.float32) / self.n_members
+        return fc, obs.to(torch.float32) / count.to(torch.float32), count
+
+    def pinball_loss(self, state_std):
+        """(leads, Q, F) pinball (quantile) loss in physical units: ``mean_s pinball * state_std``."""
+        return torch.mean(self._scores(self.pinball, "pinball_loss"), dim=0) * state_std
+
+    def coverage(self):
+        """(leads, Q, F) fraction of the live nodes, over all starts, whose truth lies below the quantile: ``q`` when calibrated."""
+        below = self._scores(self.below, "coverage")
+        return below.sum(0).to(torch.float32) / float(below.shape[0] * self.n_live)
+
+
+def quantile_tables(levels, members):
+    """``(index, frac)`` of ``nlam_ens_products_t.q_index`` / ``q_frac``: ``i = floor(q (M - 1))``, ``g = q (M - 1) - i`` in float64."""
+    import math
+
+    pos = [float(q) * (int(members) - 1) for q in levels]
+    idx = [min(int(math.floor(v)), int(members) - 1) for v in pos]
+    return idx, [v - i for v, i in zip(pos, idx)]
+
+
+def parse_products(events, quantiles, var_names, n_vars):
+    """The host checks of ``EnsembleForecast(events=..., quantiles=...)``: ``(events, levels)`` with every event as ``(variable
+    index, 0 for ">" or 1 for "<", threshold)``.  ValueError for an unknown variable, a bad sense, a level outside [0, 1] and
+    more than ``NLAM_ENS_MAX_EVENTS`` / ``NLAM_ENS_MAX_QUANTILES`` of them.  No GPU."""
+    ev, levels = [], []
+    for item in (events or ()):
+        try:
+            var, sense, thr = item
+        except (TypeError, ValueError):
+            raise ValueError(f"EnsembleForecast: an event is (variable, '>' or '<', threshold), got {item!r}") from None
+        if isinstance(var, str):
+            if var_names is None or var not in var_names:
+                raise ValueError(f"EnsembleForecast: unknown state variable {var!r} in an event (known: {var_names})")
+            idx = list(var_names).index(var)
+        else:
+            try:
+                idx = int(var)
+            except (TypeError, ValueError):
+                idx = -1
+            if isinstance(var, bool) or idx != var or not 0 <= idx < n_vars:
+                raise ValueError(f"EnsembleForecast: event variable index {var!r} outside [0, {n_vars})")
+        if sense not in (">", "<"):
+            raise ValueError(f"EnsembleForecast: an event's sense is '>' or '<', got {sense!r}")
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("EnsembleForecast: an event's threshold is NaN")
+        ev.append((idx, 0 if sense == ">" else 1, thr))
+    for q in (quantiles or ()):
+        q = float(q)
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"EnsembleForecast: quantile level {q} outside [0, 1]")
+        levels.append(q)
+    if len(ev) > L.ENS_MAX_EVENTS:
+        raise ValueError(f"EnsembleForecast: at most {L.ENS_MAX_EVENTS} events, got {len(ev)}")
+    if len(levels) > L.ENS_MAX_QUANTILES:
+        raise ValueError(f"EnsembleForecast: at most {L.ENS_MAX_QUANTILES} quantile levels, got {len(levels)}")
+    return ev, levels
+
+
 class EnsembleResult(NamedTuple):
     """Device tensors of one ``EnsembleForecast.run`` (the engine's buffers, cut to the ``leads`` that ran; batch item
     ``b = s * M + m``).  The raw fields are those of ``ForecastResult`` over the ``S * M`` batch plus the ensemble launch's; the
@@ -435,6 +533,7 @@ class EnsembleResult(NamedTuple):
     rank_hist: Optional[torch.Tensor]  # (S, leads, F, M + 1) int32
     noise: Optional[torch.Tensor]      # (leads, S * M, R, latent_dim) the standard-normal draws (record_noise / latent_noise)
     n_members: int
+    products: Optional[EnsembleProducts] = None   # EnsembleForecast(events=..., quantiles=...)
 
     def _per_member(self, t):
         return None if t is None else t.view(t.shape[0] // self.n_members, self.n_members, *t.shape[1:])
@@ -487,7 +586,7 @@ class EnsembleResult(NamedTuple):
 class EnsembleForecast(Forecast):
     """``members`` forecasts from each of ``n_starts`` initial times, as ONE recorded step over the batch ``n_starts * members``:
 
-        head -> embed + prior parameters -> nlam_latent_sample -> decoder -> tail -> nlam_ens_scores -> finish
+        head -> embed + prior parameters -> nlam_latent_sample -> decoder -> tail -> nlam_ens_scores [-> nlam_ens_products] -> finish
 
     replayed per lead.  The predictor is a Graph-EFM (``GraphEFM``, ``GraphEFMMultiScale``; ``can_return_raw_delta()``): every
     lead draws a new latent sample per member from Philox4x32-10 keyed by ``seed`` and counted by (lead, member, start time),
@@ -499,17 +598,24 @@ class EnsembleForecast(Forecast):
     of a plain series: the guarantee above holds per dataset, but the same weather read from a plain series draws other noise.
     ``verify``: the per-member sums of ``Forecast`` and the ensemble scores; the mean and spread fields are always written.
     ``record_noise``: keep every lead's draws (``EnsembleResult.noise``).  Members are always kept: the member fields take
-    ``4 S M L N F`` bytes (twice that with a std head), mean and spread ``8 S L N F``."""
+    ``4 S M L N F`` bytes (twice that with a std head), mean and spread ``8 S L N F``.
+    ``events``: ``(variable, sense, threshold)`` triples -- a state variable name of the datastore (``step.state_var_names``) or its
+    index, ``">"`` or ``"<"`` (equality never counts), a threshold in physical units -- and ``quantiles``: levels in [0, 1].  Either
+    adds ``nlam_ens_products`` after ``nlam_ens_scores`` in the recorded step (``EnsembleResult.products``: ``4 S L N (E + Q F)``
+    bytes of fields; their scores with ``verify``).  Thresholds live in a device table in standardised units, ``(thr - mean) / std``
+    computed in float64: ``set_thresholds`` rewrites it without a new recording.  With neither, nothing is allocated or launched."""
 
     _serves_latent = True
 
     def __init__(self, step, dataset, max_lead, members, n_starts=1, seed=0, verify=True, use_graph=True, autocast_dtype=None,
-                 record_noise=False):
+                 record_noise=False, events=None, quantiles=None):
         members, n_starts = int(members), int(n_starts)
         if not 1 <= members <= L.ENS_MAX_MEMBERS:
             raise ValueError(f"EnsembleForecast: members {members} outside [1, {L.ENS_MAX_MEMBERS}]")
         if n_starts < 1:
             raise ValueError(f"EnsembleForecast: n_starts {n_starts} must be >= 1")
+        self._events, self._levels = parse_products(events, quantiles, getattr(step, "state_var_names", None),
+                                                    int(getattr(step, "state_mean", torch.empty(0)).numel()))
         super().__init__(step, dataset, max_lead, batch_size=n_starts * members, verify=verify, use_graph=use_graph,
                          autocast_dtype=autocast_dtype)
         S, M, B, Lm = n_starts, members, n_starts * members, self.max_lead
@@ -549,6 +655,62 @@ class EnsembleForecast(Forecast):
             s.diagonal = int(self.predictor.prior_model.output_dist == "diagonal")
             self._s = s
         self._kept = None   # the recorded step's prior parameters (kept alive with the graph, like its network output)
+        self._pr = None
+        if self._events or self._levels:
+            self._init_products()
+
+    def _init_products(self):
+        """The tables, outputs and argument struct of ``nlam_ens_products`` (only with ``events`` or ``quantiles``)."""
+        e, step = self._e, self.step
+        S, M, N, F, Lm = e.starts, e.members, e.nodes, e.d_state, e.max_lead
+        E, Q = len(self._events), len(self._levels)
+        dev = self.start.device
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        self._mean64, self._std64 = step.state_mean.detach().cpu().double(), step.state_std.detach().cpu().double()
+        self.n_live = int((step.interior_weight != 0).sum())
+        p = L.EnsProducts()
+        p.prev, p.row_weight, p.state_mean, p.state_std, p.lead = e.prev, e.row_weight, e.state_mean, e.state_std, e.lead
+        p.truth = e.truth if self.verify else None
+        self.prob = self.quantile = self.brier = self.rel_count = self.rel_obs = self.pinball = self.below = None
+        if E:
+            self.event_var = torch.tensor([v for v, _, _ in self._events], **i32)
+            self.event_sense = torch.tensor([sn for _, sn, _ in self._events], **i32)
+            self.event_thr = torch.zeros((E,), **f32)
+            self.set_thresholds([t for _, _, t in self._events])
+            self.prob = torch.empty((S, Lm, E, N), **f32)
+            p.event_var, p.event_sense, p.event_thr, p.prob = (_ptr(t) for t in (self.event_var, self.event_sense, self.event_thr, self.prob))
+            if self.verify:
+                self.brier = torch.zeros((S, Lm, E), **f32)
+                self.rel_count, self.rel_obs = torch.zeros((S, Lm, E, M + 1), **i32), torch.zeros((S, Lm, E, M + 1), **i32)
+                p.brier, p.rel_count, p.rel_obs = _ptr(self.brier), _ptr(self.rel_count), _ptr(self.rel_obs)
+        if Q:
+            idx, frac = quantile_tables(self._levels, M)
+            self.q_index = torch.tensor(idx, **i32)
+            self.q_frac = torch.tensor(frac, dtype=torch.float64).to(**f32)
+            self.q_level = torch.tensor(self._levels, dtype=torch.float64).to(**f32)
+            self.quantile = torch.empty((S, Lm, Q, N, F), **f32)
+            p.q_index, p.q_frac, p.q_level, p.quant = (_ptr(t) for t in (self.q_index, self.q_frac, self.q_level, self.quantile))
+            if self.verify:
+                self.pinball = torch.zeros((S, Lm, Q, F), **f32)
+                self.below = torch.zeros((S, Lm, Q, F), **i32)
+                p.pinball, p.below = _ptr(self.pinball), _ptr(self.below)
+        self.products_workspace = torch.empty((int(self._lib.nlam_ens_products_workspace_floats(S, M, N, F, E, Q)),), **f32)
+        p.workspace, p.workspace_floats = _ptr(self.products_workspace), self.products_workspace.numel()
+        p.starts, p.members, p.nodes, p.d_state, p.max_lead, p.events, p.quantiles = S, M, N, F, Lm, E, Q
+        self._pr = p
+
+    def set_thresholds(self, values):
+        """New thresholds (physical units, one per event, in the order of ``events``) for the following runs: the device table
+        is rewritten in place, ``(thr - state_mean) / state_std`` in float64 rounded to fp32.  No new recording, like ``run(seed=...)``."""
+        values = [float(v) for v in values]
+        if len(values) != len(self._events) or not values:
+            raise ValueError(f"EnsembleForecast.set_thresholds: {len(values)} thresholds for {len(self._events)} events")
+        if any(v != v for v in values):
+            raise ValueError("EnsembleForecast.set_thresholds: a threshold is NaN")
+        var = torch.tensor([v for v, _, _ in self._events], dtype=torch.int64)
+        std = (torch.tensor(values, dtype=torch.float64) - self._mean64[var]) / self._std64[var]
+        self.event_thr.copy_(std.to(torch.float32))
+        self._events = [(v, sn, t) for (v, sn, _), t in zip(self._events, values)]
 
     def _set_seed(self, seed):
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -576,6 +738,8 @@ class EnsembleForecast(Forecast):
         from .ops import _stream
 
         L.check(self._lib.nlam_ens_scores(C.byref(self._e), _stream()), "nlam_ens_scores")
+        if self._pr is not None:
+            L.check(self._lib.nlam_ens_products(C.byref(self._pr), _stream()), "nlam_ens_products")
 
     def _install(self, given):
         """Install the recording that draws the noise (``given`` False) or reads it from ``self.noise`` (True)."""
@@ -619,5 +783,10 @@ class EnsembleForecast(Forecast):
         cut = lambda t, dim=1: None if t is None else t.narrow(dim, 0, leads)   # noqa: E731
         scores = (self.ens_sq, self.ens_var, self.ens_abs, self.ens_pair, self.rank_hist) if self.verify else (None,) * 5
         noise = self.noise if self.samples and (self.record_noise or latent_noise is not None) else None
+        products = None
+        if self._pr is not None:
+            fields = (self.prob, self.quantile, self.brier, self.rel_count, self.rel_obs, self.pinball, self.below)
+            products = EnsembleProducts(*(cut(t) for t in fields), tuple((v, "<" if sn else ">", t) for v, sn, t in self._events),
+                                        tuple(self._levels), self.members, self.n_live)
         return EnsembleResult(cut(self.out_state), cut(self.out_std), cut(self.valid_times), cut(self.sq), cut(self.ab),
-                              cut(self.mean), cut(self.spread), *(cut(t) for t in scores), cut(noise, 0), self.members)
+                              cut(self.mean), cut(self.spread), *(cut(t) for t in scores), cut(noise, 0), self.members, products)

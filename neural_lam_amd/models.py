@@ -840,6 +840,7 @@ class ForecasterStep(nn.Module):
         self.default_loss = self.loss_kind == LOSS_WMSE
         self.forecaster = forecaster
         self.standardize_inputs = bool(standardize)
+        self.state_var_names = [str(n) for n in datastore.get_vars_names("state")]   # what EnsembleForecast(events=...) names
         bm = torch.tensor(datastore.boundary_mask.values, dtype=torch.float32)
         self.register_buffer("interior_mask_bool", (1.0 - bm).to(torch.bool), persistent=False)
         self.register_buffer("interior_index", torch.nonzero(1.0 - bm > 0.5).reshape(-1), persistent=False)

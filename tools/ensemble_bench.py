@@ -3,6 +3,7 @@
 
     python tools/ensemble_bench.py [--config cfg2] [--members 4 16] [--leads 40] [--rounds 3] [--out profiles/ensemble/bench.json]
     python tools/ensemble_bench.py --kernels-only      # under rocprofv3 --kernel-trace --stats: the two launches alone
+    python tools/ensemble_bench.py --products [--kernels-only] [--out profiles/ensemble_products/bench.json]
 
 Route "forecast": ``Forecast(step, data, L, batch_size=M, verify=True).run([start] * M)`` with the configuration's GraphLAM.
 Route "ensemble": ``EnsembleForecast(step, data, L, members=M).run([start])`` with the same predictor: the same batch, the same
@@ -12,6 +13,9 @@ Per route: ms per lead (HIP events around a synchronised window of ``--repeats``
 the rounds' spread max - min), kernel launches per lead and peak memory above what the routes share (model and resident series).
 The two new launches alone: 50 of them recorded into one graph and replayed between two events, with their minimum bytes
 (nlam_ens_scores: 4 S N F (M + 3) + 8 S N F; nlam_latent_sample: parameters in, latent out) over that time.
+``--products`` adds the route "ensemble_products": the "ensemble" engine with 4 events and 3 quantile levels (nlam_ens_products and
+its finishing pass per lead), alternating with the others, and times that launch pair alone against its minimum bytes
+(4 S N F (M + 1) + 4 S N (E + Q F)).  Without the option the run is what it was.
 """
 import argparse
 import ctypes as C
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=2, help="forecasts per timed window")
     ap.add_argument("--kernels-only", action="store_true", help="launch nlam_ens_scores and nlam_latent_sample alone (for a kernel trace)")
+    ap.add_argument("--products", action="store_true", help="add the route with 4 events and 3 quantiles, and time nlam_ens_products alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -68,9 +73,14 @@ def main():
     for M in args.members:
         row = {}
         engines = {}
-        for name, make in (("forecast", lambda: Forecast(step, data, args.leads, batch_size=M, verify=True)),
-                           ("ensemble", lambda: EnsembleForecast(step, data, args.leads, members=M)),
-                           ("efm", lambda: EnsembleForecast(efm_step, data, args.leads, members=M))):
+        routes = [("forecast", lambda: Forecast(step, data, args.leads, batch_size=M, verify=True)),
+                  ("ensemble", lambda: EnsembleForecast(step, data, args.leads, members=M)),
+                  ("efm", lambda: EnsembleForecast(efm_step, data, args.leads, members=M))]
+        if args.products:   # standardised data: thresholds around the bulk and in the tails, the median and the 10 % / 90 % envelope
+            events = [(0, ">", 0.0), (0, "<", -1.0), (F // 2, ">", 1.5), (F - 1, "<", 0.5)]
+            routes.append(("ensemble_products", lambda: EnsembleForecast(step, data, args.leads, members=M, events=events,
+                                                                         quantiles=[0.1, 0.5, 0.9])))
+        for name, make in routes:
             torch.cuda.synchronize()
             before = torch.cuda.memory_allocated()
             torch.cuda.reset_peak_memory_stats()
@@ -106,6 +116,17 @@ def main():
         row["kernels"] = {"ens_scores_and_finish": {"ms": scores_ms, "min_bytes": scores_bytes, "gb_per_s": scores_bytes / scores_ms / 1e6},
                           "latent_sample": {"ms": sample_ms, "min_bytes": sample_bytes, "gb_per_s": sample_bytes / sample_ms / 1e6,
                                             "rows": efm_eng._s.rows, "latent_dim": efm_eng._s.latent_dim}}
+        if args.products:
+            pe = engines["ensemble_products"][0]
+            pe.run([0], leads=1)
+            pe.lead.zero_()
+            prod_ms = kernel_ms(lambda: L.check(pe._lib.nlam_ens_products(C.byref(pe._pr), stream()), "nlam_ens_products"))
+            prod_bytes = 4 * N * F * (M + 1) + 4 * N * (pe._pr.events + pe._pr.quantiles * F)
+            row["kernels"]["ens_products_and_finish"] = {"ms": prod_ms, "min_bytes": prod_bytes, "gb_per_s": prod_bytes / prod_ms / 1e6,
+                                                         "events": pe._pr.events, "quantiles": pe._pr.quantiles}
+            if not args.kernels_only:
+                row["products_minus_ensemble_ms"] = row["ensemble_products"]["ms_per_lead"] - row["ensemble"]["ms_per_lead"]
+            del pe
         out["members"][str(M)] = row
         del engines, ens, efm_eng
         torch.cuda.empty_cache()
