@@ -1426,7 +1426,8 @@ int64_t nlam_moments_workspace_doubles(int32_t nodes, int32_t nvars, int64_t cou
  *           produced and has no special meaning on decode
  * Standardisation, where an entry applies it, follows on the decoded value exactly as in the fp32 entries (IEEE sub, then div);
  * the two affine maps are not folded.  Every _q16 entry therefore gives the bits of its fp32 entry on a series of the decoded
- * values.  Strides of a packed series are counted in int16 ELEMENTS; a (nodes x d) block may start at any 2-byte-aligned
+ * values: it launches the kernel of that fp32 entry, instantiated for int16 elements where a series is packed (the fp32 entries
+ * launch the float instantiations).  Strides of a packed series are counted in int16 ELEMENTS; a (nodes x d) block may start at any 2-byte-aligned
  * address and is read four codes (8 bytes) per lane when it starts on an 8-byte boundary, its destination on a 16-byte
  * boundary and its length is a multiple of 4, code by code otherwise (the fp32 entries' 16-byte test).
  *

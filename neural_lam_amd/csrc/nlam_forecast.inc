@@ -2,8 +2,8 @@
 //
 // A captured launch keeps its pointers, so what depends on the lead time is addressed on the device: `start` holds each
 // forecast's time index t0, `lead` the number k of lead times already produced.  Per replay
-//   head    this lead's standardised forcing window and boundary truth, cut from the resident series (the loops and the
-//           IEEE sub + div of window_batch_kernel: the same bits)
+//   head    this lead's standardised forcing window and boundary truth, cut from the resident series (the row loops of
+//           nlam_series.inc, which window_batch_kernel runs too: the same bits)
 //   (the network, recorded between the two)
 //   tail    one pass per element: step_tail_pred -- the function of step_tail_ext_fwd_kernel, so the new state has the bits of
 //           nlam_step_tail_ext_fwd(target = NULL) --, the in-place rotation prev_prev <- prev <- new, slot k of the physical
@@ -13,6 +13,8 @@
 // All three do nothing once *lead >= max_lead: a replay too many writes nothing.
 // nlam_forecast_init_strided / _head_strided are init and head over forecast-type and ensemble series: the same row loops, the
 // (sample, member, row) block found with nlam_window_ens_t's strides from a flat sample index read on the device.
+// nlam_forecast_init_q16 / _head_q16 launch the same two kernel templates with int16_t for every packed series (the strided
+// entries launch the float instantiations); all of them stage (mean, std) in LDS.
 // HBM-bound: a workgroup of the tail owns (batch item, chunk of whole nodes), a multiple of 4 nodes, so a chunk starts on a
 // 16-byte boundary whenever its batch item does; 16-byte accesses where every operand of the chunk is aligned (DESIGN 4.17's
 // rule), single elements otherwise and on a chunk's last partial quad.  The per-variable tables -- StepTailTables plus (std, mean)
@@ -46,77 +48,6 @@ __device__ __forceinline__ const float2* fc_stage_stats(const float* mean, const
     return tab;
 }
 
-// one (nodes x d) block of the state series, standardised: window_batch_kernel's state rows
-__device__ __forceinline__ void fc_state_row(const float* __restrict__ src, float* __restrict__ dst, const float2* stats, unsigned per,
-                                             unsigned d, unsigned tid, unsigned nthr) {
-    const bool vec = (per & 3u) == 0 && ((reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst)) & 15) == 0;
-    for (unsigned q = tid; q < (per + 3) / 4; q += nthr) {
-        const unsigned e0 = 4 * q;
-        float v[4];
-        if (vec) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(src + e0);
-            v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = e0 + k < per ? src[e0 + k] : 0.f;
-        }
-        unsigned f = e0 % d;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float2 ms = stats[f];
-            v[k] = __fdiv_rn(__fsub_rn(v[k], ms.x), ms.y);
-            f = f + 1 == d ? 0 : f + 1;
-        }
-        if (vec) {
-            *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (e0 + k < per) dst[e0 + k] = v[k];
-        }
-    }
-}
-
-// one (nodes x d_forcing * window) row of windowed forcing, standardised: window_batch_kernel's (window x d_forcing) ->
-// (d_forcing x window) transpose per node.  slot(w) is the (nodes x d_forcing) block that window slot w reads.
-template <typename SLOT>
-__device__ __forceinline__ void fc_forcing_row(float* __restrict__ dst, const float2* stats, unsigned nodes, unsigned df, unsigned W,
-                                               unsigned tid, unsigned nthr, SLOT slot) {
-    const unsigned fw = df * W;
-    const unsigned per_out = nodes * fw;
-    const bool vec = (per_out & 3u) == 0 && (reinterpret_cast<size_t>(dst) & 15) == 0;
-    for (unsigned q = tid; q < (per_out + 3) / 4; q += nthr) {
-        const unsigned e0 = 4 * q;
-        unsigned n = e0 / fw;
-        unsigned jj = e0 - n * fw;
-        unsigned fi = jj / W, w = jj - fi * W;
-        float v[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float x = 0.f;
-            if (e0 + c < per_out) {
-                const float2 ms = stats[fi];
-                x = __fdiv_rn(__fsub_rn(slot(w)[(long)n * df + fi], ms.x), ms.y);
-            }
-            v[c] = x;
-            if (++w == W) {
-                w = 0;
-                if (++fi == df) {
-                    fi = 0;
-                    ++n;
-                }
-            }
-        }
-        if (vec) {
-            *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (e0 + c < per_out) dst[e0 + c] = v[c];
-        }
-    }
-}
-
 // The strided source of nlam_forecast_init_strided / _head_strided: nlam_window_ens_t's addressing.  The flat sample index is
 // read on the device, clamped into [0, n_flat) and split into (sample, member) once per workgroup.
 struct ForecastSrcArgs {
@@ -137,86 +68,97 @@ __device__ __forceinline__ FcSample fc_sample(const ForecastSrcArgs& a, int b) {
 
 // the contiguous (nodes x d) block of row j of (sample, member): forecast data clamps the lead-time row into [0, steps), analysis
 // data the time index s + j into [0, n_times) (there stride_sample == stride_step)
-__device__ __forceinline__ const float* fc_src_block(const float* base, long stride_sample, long stride_step, long stride_member,
-                                                     const nlam_forecast_src_t& c, int steps, FcSample i, long j) {
+template <typename T>
+__device__ __forceinline__ const T* fc_src_block(const T* base, long stride_sample, long stride_step, long stride_member,
+                                                 const nlam_forecast_src_t& c, int steps, FcSample i, long j) {
     if (c.is_forecast) return base + i.s * stride_sample + fc_clamp_time(j, steps - 1) * stride_step + i.m * stride_member;
     return base + fc_clamp_time(i.s + j, c.n_times - 1) * stride_step + i.m * stride_member;
 }
 
+// a strided source with a packed series (nlam_forecast_init_q16 / _head_q16): the instantiations that decode take this one
+struct ForecastPackedArgs : ForecastSrcArgs {
+    nlam_q16_src_t q;
+};
+
 // blockIdx.z = forecast of the batch, blockIdx.y = 0: prev_prev (time t0 - 1), 1: prev (time t0); the counter starts at 0
 __global__ __launch_bounds__(256) void forecast_init_kernel(const nlam_forecast_t p) {
-    const float2* const stats = fc_stage_stats(p.state_mean, p.state_std, p.d_state);
+    const StatsLds stats{fc_stage_stats(p.state_mean, p.state_std, p.d_state)};
     const int b = blockIdx.z, r = blockIdx.y;
     const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
     const long t = fc_clamp_time(p.start[b] - 1 + r, p.n_times - 1);
-    fc_state_row(p.state + t * (long)per, (r == 0 ? p.prev_prev : p.prev) + (long)b * per, stats, per, p.d_state,
-                 blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    series_state_row(Series<float>{}, p.state + t * (long)per, (r == 0 ? p.prev_prev : p.prev) + (long)b * per, stats, per,
+                     (unsigned)p.d_state, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     if (blockIdx.x == 0 && r == 0 && b == 0 && threadIdx.x == 0) *p.lead = 0;
 }
 
 // blockIdx.z = forecast of the batch, blockIdx.y = 0: the boundary truth (state at t0 + k + 1), 1: the forcing window of that time
-// (window_batch_kernel's (window x d_forcing) -> (d_forcing x window) transpose per node)
 __global__ __launch_bounds__(256) void forecast_head_kernel(const nlam_forecast_t p) {
     const int k = *p.lead;
     if (k >= p.max_lead) return;   // the same in every thread of the grid, ahead of every barrier
     const bool forc = blockIdx.y == 1;
-    const float2* const stats = forc ? fc_stage_stats(p.forcing_mean, p.forcing_std, p.d_forcing)
-                                     : fc_stage_stats(p.state_mean, p.state_std, p.d_state);
+    const StatsLds stats{forc ? fc_stage_stats(p.forcing_mean, p.forcing_std, p.d_forcing)
+                              : fc_stage_stats(p.state_mean, p.state_std, p.d_state)};
     const int b = blockIdx.z;
     const long last = p.n_times - 1;
     const long tv = p.start[b] + k + 1;   // the valid time of this lead
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
     if (!forc) {
         const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
-        fc_state_row(p.state + fc_clamp_time(tv, last) * (long)per, p.truth + (long)b * per, stats, per, p.d_state, tid, nthr);
+        series_state_row(Series<float>{}, p.state + fc_clamp_time(tv, last) * (long)per, p.truth + (long)b * per, stats, per,
+                         (unsigned)p.d_state, tid, nthr);
         return;
     }
     const int past = p.num_past_forcing_steps;
     const unsigned W = past + p.num_future_forcing_steps + 1, df = p.d_forcing;
     const long per_in = (long)p.nodes * df;
     const long t0 = tv - past;   // time of window slot 0
-    fc_forcing_row(p.forcing_windowed + (long)b * p.nodes * (df * W), stats, p.nodes, df, W, tid, nthr,
-                   [&](unsigned w) { return p.forcing + fc_clamp_time(t0 + (long)w, last) * per_in; });
+    series_forcing_row(Series<float>{}, p.forcing_windowed + (long)b * p.nodes * (df * W), stats, (unsigned)p.nodes, df, W, tid, nthr,
+                       [&](unsigned w) { return p.forcing + fc_clamp_time(t0 + (long)w, last) * per_in; });
 }
 
-// forecast_init_kernel over a strided source: rows off - 2 and off - 1 of the sample
-__global__ __launch_bounds__(256) void forecast_init_strided_kernel(const ForecastSrcArgs a) {
-    const nlam_forecast_t& p = a.p;
-    const nlam_forecast_src_t& c = a.s;
-    const float2* const stats = fc_stage_stats(p.state_mean, p.state_std, p.d_state);
+// forecast_init_kernel over a strided source, fp32 (ST = float) or packed: rows off - 2 and off - 1 of the sample
+template <typename ST>
+__global__ __launch_bounds__(256) void forecast_init_strided_kernel(const SeriesArgs<ST, float, ForecastSrcArgs, ForecastPackedArgs> g) {
+    const nlam_forecast_t& p = g.p;
+    const nlam_forecast_src_t& c = g.s;
+    const StatsLds stats{fc_stage_stats(p.state_mean, p.state_std, p.d_state)};
     const int b = blockIdx.z, r = blockIdx.y;
     const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
     const long j = max(2, p.num_past_forcing_steps) - 2 + r;
-    const float* src = fc_src_block(c.state, c.state_stride_sample, c.state_stride_step, c.state_stride_member, c, c.state_steps,
-                                    fc_sample(a, b), j);
-    fc_state_row(src, (r == 0 ? p.prev_prev : p.prev) + (long)b * per, stats, per, p.d_state, blockIdx.x * blockDim.x + threadIdx.x,
-                 gridDim.x * blockDim.x);
+    const Series<ST> ser = state_series<ST>(c.state, g);
+    const ST* src = fc_src_block(ser.base, c.state_stride_sample, c.state_stride_step, c.state_stride_member, c, c.state_steps,
+                                 fc_sample(g, b), j);
+    series_state_row(ser, src, (r == 0 ? p.prev_prev : p.prev) + (long)b * per, stats, per, (unsigned)p.d_state,
+                     blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     if (blockIdx.x == 0 && r == 0 && b == 0 && threadIdx.x == 0) *p.lead = 0;
 }
 
 // forecast_head_kernel over a strided source: the truth is row off + k, window slot w of the forcing row off + k - past + w
-__global__ __launch_bounds__(256) void forecast_head_strided_kernel(const ForecastSrcArgs a) {
-    const nlam_forecast_t& p = a.p;
-    const nlam_forecast_src_t& c = a.s;
+template <typename ST, typename FT>
+__global__ __launch_bounds__(256) void forecast_head_strided_kernel(const SeriesArgs<ST, FT, ForecastSrcArgs, ForecastPackedArgs> g) {
+    const nlam_forecast_t& p = g.p;
+    const nlam_forecast_src_t& c = g.s;
     const int k = *p.lead;
     if (k >= p.max_lead) return;   // the same in every thread of the grid, ahead of every barrier
     const bool forc = blockIdx.y == 1;
-    const float2* const stats = forc ? fc_stage_stats(p.forcing_mean, p.forcing_std, p.d_forcing)
-                                     : fc_stage_stats(p.state_mean, p.state_std, p.d_state);
+    const StatsLds stats{forc ? fc_stage_stats(p.forcing_mean, p.forcing_std, p.d_forcing)
+                              : fc_stage_stats(p.state_mean, p.state_std, p.d_state)};
     const int b = blockIdx.z;
-    const FcSample i = fc_sample(a, b);
+    const FcSample i = fc_sample(g, b);
     const int past = p.num_past_forcing_steps;
     const long jv = max(2, past) + k;   // the row of this lead
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
     if (!forc) {
         const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
-        fc_state_row(fc_src_block(c.state, c.state_stride_sample, c.state_stride_step, c.state_stride_member, c, c.state_steps, i, jv),
-                     p.truth + (long)b * per, stats, per, p.d_state, tid, nthr);
+        const Series<ST> ser = state_series<ST>(c.state, g);
+        const ST* src = fc_src_block(ser.base, c.state_stride_sample, c.state_stride_step, c.state_stride_member, c, c.state_steps, i, jv);
+        series_state_row(ser, src, p.truth + (long)b * per, stats, per, (unsigned)p.d_state, tid, nthr);
         return;
     }
     const unsigned W = past + p.num_future_forcing_steps + 1, df = p.d_forcing;
-    fc_forcing_row(p.forcing_windowed + (long)b * p.nodes * (df * W), stats, p.nodes, df, W, tid, nthr, [&](unsigned w) {
-        return fc_src_block(c.forcing, c.forcing_stride_sample, c.forcing_stride_step, c.forcing_stride_member, c, c.forcing_steps, i,
+    const Series<FT> ser = forcing_series<FT>(c.forcing, g);
+    series_forcing_row(ser, p.forcing_windowed + (long)b * p.nodes * (df * W), stats, (unsigned)p.nodes, df, W, tid, nthr, [&](unsigned w) {
+        return fc_src_block(ser.base, c.forcing_stride_sample, c.forcing_stride_step, c.forcing_stride_member, c, c.forcing_steps, i,
                             jv - past + (long)w);
     });
 }
@@ -452,6 +394,58 @@ int fc_row_blocks(long elems) {
     return (int)(blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks));
 }
 
+// grid and dynamic LDS of an init / a head launch: two state rows, or the truth row and the forcing row, per forecast
+struct FcRowShape {
+    dim3 grid;
+    size_t lds;   // the (mean, std) table of the widest row
+};
+
+FcRowShape fc_init_shape(const nlam_forecast_t& p) {
+    return {dim3(fc_row_blocks((long)p.nodes * p.d_state), 2, p.batch), (size_t)p.d_state * sizeof(float2)};
+}
+
+FcRowShape fc_head_shape(const nlam_forecast_t& p) {
+    const long window = (long)p.num_past_forcing_steps + p.num_future_forcing_steps + 1;
+    const long e_state = (long)p.nodes * p.d_state, e_forc = (long)p.nodes * p.d_forcing * window;
+    const int wide = p.d_state > p.d_forcing ? p.d_state : p.d_forcing;
+    return {dim3(fc_row_blocks(e_state > e_forc ? e_state : e_forc), p.d_forcing > 0 ? 2 : 1, p.batch), (size_t)wide * sizeof(float2)};
+}
+
+// forecast_src_check with the packed source in place of the float series: a packed series stands in for the float pointer the
+// shared checks ask for (no kernel of the pair reads it through that pointer)
+int32_t forecast_q16_check(const nlam_forecast_t* p, const nlam_forecast_src_t* s, const nlam_q16_src_t* q, int which,
+                           ForecastPackedArgs* g) {
+    if (p == nullptr || s == nullptr || q == nullptr) return NLAM_EINVAL;
+    if (const int32_t rc = q16_src_check(q, s->state, s->forcing, p->d_forcing)) return rc;
+    nlam_forecast_src_t s2 = *s;
+    if (q->state != nullptr) s2.state = reinterpret_cast<const float*>(q->state);
+    if (p->d_forcing > 0 && q->forcing != nullptr) s2.forcing = reinterpret_cast<const float*>(q->forcing);
+    if (const int32_t rc = forecast_src_check(p, &s2, which, g)) return rc;
+    g->s = *s;
+    g->q = *q;
+    return 0;
+}
+
+// the strided launches, fp32 (g.q names no series: the float instantiations take the ForecastSrcArgs in front of it) or packed
+int32_t forecast_init_series(const ForecastPackedArgs& g, hipStream_t stream) {
+    const FcRowShape sh = fc_init_shape(g.p);
+    return pick_elem(g.q.state != nullptr, [&](auto st) {
+        using A = SeriesArgs<decltype(st), float, ForecastSrcArgs, ForecastPackedArgs>;
+        return launch<forecast_init_strided_kernel<decltype(st)>>(sh.grid, dim3(256), sh.lds, stream, static_cast<const A&>(g));
+    });
+}
+
+int32_t forecast_head_series(const ForecastPackedArgs& g, hipStream_t stream) {
+    const FcRowShape sh = fc_head_shape(g.p);
+    return pick_elem(g.q.state != nullptr, [&](auto st) {
+        return pick_elem(g.p.d_forcing > 0 && g.q.forcing != nullptr, [&](auto ft) {
+            using A = SeriesArgs<decltype(st), decltype(ft), ForecastSrcArgs, ForecastPackedArgs>;
+            return launch<forecast_head_strided_kernel<decltype(st), decltype(ft)>>(sh.grid, dim3(256), sh.lds, stream,
+                                                                                   static_cast<const A&>(g));
+        });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -459,37 +453,45 @@ extern "C" {
 int32_t nlam_forecast_init(const nlam_forecast_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_forecast_init");
     if (const int32_t rc = forecast_check(p, kFcInit)) return rc;
-    return launch<forecast_init_kernel>(dim3(fc_row_blocks((long)p->nodes * p->d_state), 2, p->batch), dim3(256),
-                                        (size_t)p->d_state * sizeof(float2), (hipStream_t)hip_stream, *p);
+    const FcRowShape sh = fc_init_shape(*p);
+    return launch<forecast_init_kernel>(sh.grid, dim3(256), sh.lds, (hipStream_t)hip_stream, *p);
 }
 
 int32_t nlam_forecast_head(const nlam_forecast_t* p, void* hip_stream) {
     NLAM_RANGE("nlam_forecast_head");
     if (const int32_t rc = forecast_check(p, kFcHead)) return rc;
-    const long window = (long)p->num_past_forcing_steps + p->num_future_forcing_steps + 1;
-    const long e_state = (long)p->nodes * p->d_state, e_forc = (long)p->nodes * p->d_forcing * window;
-    const int wide = p->d_state > p->d_forcing ? p->d_state : p->d_forcing;
-    return launch<forecast_head_kernel>(dim3(fc_row_blocks(e_state > e_forc ? e_state : e_forc), p->d_forcing > 0 ? 2 : 1, p->batch),
-                                        dim3(256), (size_t)wide * sizeof(float2), (hipStream_t)hip_stream, *p);
+    const FcRowShape sh = fc_head_shape(*p);
+    return launch<forecast_head_kernel>(sh.grid, dim3(256), sh.lds, (hipStream_t)hip_stream, *p);
 }
 
 int32_t nlam_forecast_init_strided(const nlam_forecast_t* p, const nlam_forecast_src_t* src, void* hip_stream) {
     NLAM_RANGE("nlam_forecast_init_strided");
-    ForecastSrcArgs a;
-    if (const int32_t rc = forecast_src_check(p, src, kFcInit, &a)) return rc;
-    return launch<forecast_init_strided_kernel>(dim3(fc_row_blocks((long)p->nodes * p->d_state), 2, p->batch), dim3(256),
-                                                (size_t)p->d_state * sizeof(float2), (hipStream_t)hip_stream, a);
+    ForecastPackedArgs g = {};
+    if (const int32_t rc = forecast_src_check(p, src, kFcInit, &g)) return rc;
+    return forecast_init_series(g, (hipStream_t)hip_stream);
 }
 
 int32_t nlam_forecast_head_strided(const nlam_forecast_t* p, const nlam_forecast_src_t* src, void* hip_stream) {
     NLAM_RANGE("nlam_forecast_head_strided");
-    ForecastSrcArgs a;
-    if (const int32_t rc = forecast_src_check(p, src, kFcHead, &a)) return rc;
-    const long window = (long)p->num_past_forcing_steps + p->num_future_forcing_steps + 1;
-    const long e_state = (long)p->nodes * p->d_state, e_forc = (long)p->nodes * p->d_forcing * window;
-    const int wide = p->d_state > p->d_forcing ? p->d_state : p->d_forcing;
-    return launch<forecast_head_strided_kernel>(dim3(fc_row_blocks(e_state > e_forc ? e_state : e_forc), p->d_forcing > 0 ? 2 : 1, p->batch),
-                                                dim3(256), (size_t)wide * sizeof(float2), (hipStream_t)hip_stream, a);
+    ForecastPackedArgs g = {};
+    if (const int32_t rc = forecast_src_check(p, src, kFcHead, &g)) return rc;
+    return forecast_head_series(g, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_forecast_init_q16(const nlam_forecast_t* p, const nlam_forecast_src_t* src, const nlam_q16_src_t* packed,
+                               void* hip_stream) {
+    NLAM_RANGE("nlam_forecast_init_q16");
+    ForecastPackedArgs g;
+    if (const int32_t rc = forecast_q16_check(p, src, packed, kFcInit, &g)) return rc;
+    return forecast_init_series(g, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_forecast_head_q16(const nlam_forecast_t* p, const nlam_forecast_src_t* src, const nlam_q16_src_t* packed,
+                               void* hip_stream) {
+    NLAM_RANGE("nlam_forecast_head_q16");
+    ForecastPackedArgs g;
+    if (const int32_t rc = forecast_q16_check(p, src, packed, kFcHead, &g)) return rc;
+    return forecast_head_series(g, (hipStream_t)hip_stream);
 }
 
 int32_t nlam_forecast_tail(const nlam_forecast_t* p, void* hip_stream) {

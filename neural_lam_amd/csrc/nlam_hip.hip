@@ -4171,205 +4171,6 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const nlam_eval_t p, i
 
 #endif
 
-#if NLAM_IN_TU(5)   // window_batch, window_batch_ens
-// nlam_window_batch: blockIdx.z = sample of the batch, blockIdx.y = row: 0 .. 1 + ar_steps -> one (nodes x d_state) block
-// of the state series (a contiguous copy), then ar_steps rows of windowed forcing (a (window x d_forcing) ->
-// (d_forcing x window) transpose per node: consecutive lanes write consecutive floats, their reads walk `window`
-// contiguous streams).  Four consecutive floats per thread and 32-bit index arithmetic: one division per four
-// elements, the feature / window counters advance incrementally (64-bit divisions per element made the first version
-// run at a tenth of the HBM rate).
-__global__ __launch_bounds__(256) void window_batch_kernel(const nlam_window_t p) {
-    const int b = blockIdx.z;
-    const long i = p.sample_idx[b];
-    const int past = p.num_past_forcing_steps, fut = p.num_future_forcing_steps;
-    const long last = p.n_times - 1;
-    const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
-    const int nstate_rows = 2 + p.ar_steps;
-    if ((int)blockIdx.y < nstate_rows) {
-        const int r = blockIdx.y;
-        const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
-        const long t = min(max(i + max(0, past - 2) + r, 0L), last);
-        const float* src = p.state + t * (long)per;
-        float* dst = r < 2 ? p.init_states + ((long)b * 2 + r) * per : p.target_states + ((long)b * p.ar_steps + (r - 2)) * per;
-        const bool stdz = p.state_mean != nullptr;
-        const unsigned d = p.d_state;
-        const bool vec = (per & 3u) == 0 && ((reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst)) & 15) == 0;
-        for (unsigned q = tid; q < (per + 3) / 4; q += nthr) {
-            const unsigned e0 = 4 * q;
-            float v[4];
-            if (vec) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(src + e0);
-                v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = e0 + k < per ? src[e0 + k] : 0.f;
-            }
-            if (stdz) {
-                unsigned f = e0 % d;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    v[k] = __fdiv_rn(__fsub_rn(v[k], p.state_mean[f]), p.state_std[f]);
-                    f = f + 1 == d ? 0 : f + 1;
-                }
-            }
-            if (vec) {
-                *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (e0 + k < per) dst[e0 + k] = v[k];
-            }
-        }
-        if (r == 2 && p.target_times != nullptr && blockIdx.x == 0 && (int)threadIdx.x < p.ar_steps) {
-            // without time stamps the (clamped, like the data) time INDEX of every target step is reported
-            const long tt = min(max(i + max(2, past) + (long)threadIdx.x, 0L), last);
-            p.target_times[(long)b * p.ar_steps + threadIdx.x] = p.times != nullptr ? p.times[tt] : tt;
-        }
-    } else {
-        if (p.d_forcing == 0) return;
-        const int step = (int)blockIdx.y - nstate_rows;
-        const unsigned W = past + fut + 1, df = p.d_forcing;
-        const unsigned fw = df * W;
-        const unsigned per_out = (unsigned)p.nodes * fw;
-        const long per_in = (long)p.nodes * df;
-        const long t0 = i + max(2, past) + step - past;   // time of window slot 0
-        float* dst = p.forcing_windowed + ((long)b * p.ar_steps + step) * per_out;
-        const bool stdz = p.forcing_mean != nullptr;
-        const bool vec = (per_out & 3u) == 0 && (reinterpret_cast<size_t>(dst) & 15) == 0;
-        for (unsigned q = tid; q < (per_out + 3) / 4; q += nthr) {
-            const unsigned e0 = 4 * q;
-            unsigned n = e0 / fw;
-            unsigned jj = e0 - n * fw;
-            unsigned fi = jj / W, w = jj - fi * W;
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float x = 0.f;
-                if (e0 + k < per_out) {
-                    const long t = min(max(t0 + (long)w, 0L), last);
-                    x = p.forcing[t * per_in + (long)n * df + fi];
-                    if (stdz) x = __fdiv_rn(__fsub_rn(x, p.forcing_mean[fi]), p.forcing_std[fi]);
-                }
-                v[k] = x;
-                if (++w == W) {
-                    w = 0;
-                    if (++fi == df) {
-                        fi = 0;
-                        ++n;
-                    }
-                }
-            }
-            if (vec) {
-                *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (e0 + k < per_out) dst[e0 + k] = v[k];
-            }
-        }
-    }
-}
-
-// nlam_window_batch_ens: window_batch_kernel's launch shape and row loops over strided series.  The flat index is
-// clamped and split into (sample, member) once per workgroup; every (sample, member, step) block is contiguous, so the
-// state rows keep the 16-byte copy and the forcing rows the per-node (window x d_forcing) transpose, the window slots
-// now stride_step floats apart.  n_flat = base_len * members (computed and checked by the entry point).
-__global__ __launch_bounds__(256) void window_batch_ens_kernel(const nlam_window_ens_t p, long n_flat) {
-    const int b = blockIdx.z;
-    const long idx = min(max(p.sample_idx[b], 0L), n_flat - 1);
-    const long s = idx / p.members, m = idx - s * p.members;
-    const int past = p.num_past_forcing_steps, fut = p.num_future_forcing_steps;
-    const int off = max(2, past);
-    const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
-    const int nstate_rows = 2 + p.ar_steps;
-    if ((int)blockIdx.y < nstate_rows) {
-        const int r = blockIdx.y;
-        const unsigned per = (unsigned)p.nodes * (unsigned)p.d_state;
-        const long j = max(0, past - 2) + r;
-        const float* src = p.state + s * p.state_stride_sample + j * p.state_stride_step + m * p.state_stride_member;
-        float* dst = r < 2 ? p.init_states + ((long)b * 2 + r) * per : p.target_states + ((long)b * p.ar_steps + (r - 2)) * per;
-        const bool stdz = p.state_mean != nullptr;
-        const unsigned d = p.d_state;
-        const bool vec = (per & 3u) == 0 && ((reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst)) & 15) == 0;
-        for (unsigned q = tid; q < (per + 3) / 4; q += nthr) {
-            const unsigned e0 = 4 * q;
-            float v[4];
-            if (vec) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(src + e0);
-                v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = e0 + k < per ? src[e0 + k] : 0.f;
-            }
-            if (stdz) {
-                unsigned f = e0 % d;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    v[k] = __fdiv_rn(__fsub_rn(v[k], p.state_mean[f]), p.state_std[f]);
-                    f = f + 1 == d ? 0 : f + 1;
-                }
-            }
-            if (vec) {
-                *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (e0 + k < per) dst[e0 + k] = v[k];
-            }
-        }
-        if (r == 2 && p.target_times != nullptr && blockIdx.x == 0 && (int)threadIdx.x < p.ar_steps) {
-            const long jt = off + (long)threadIdx.x;
-            long tt;
-            if (p.is_forecast) tt = p.times != nullptr ? p.times[s] + p.elapsed[jt] : jt;   // lead-time index without stamps
-            else tt = p.times != nullptr ? p.times[s + jt] : s + jt;                        // time index without stamps
-            p.target_times[(long)b * p.ar_steps + threadIdx.x] = tt;
-        }
-    } else {
-        if (p.d_forcing == 0) return;
-        const int step = (int)blockIdx.y - nstate_rows;
-        const unsigned W = past + fut + 1, df = p.d_forcing;
-        const unsigned fw = df * W;
-        const unsigned per_out = (unsigned)p.nodes * fw;
-        const long sw = p.forcing_stride_step;   // floats between window slots
-        const float* src0 = p.forcing + s * p.forcing_stride_sample + (long)(off + step - past) * sw + m * p.forcing_stride_member;
-        float* dst = p.forcing_windowed + ((long)b * p.ar_steps + step) * per_out;
-        const bool stdz = p.forcing_mean != nullptr;
-        const bool vec = (per_out & 3u) == 0 && (reinterpret_cast<size_t>(dst) & 15) == 0;
-        for (unsigned q = tid; q < (per_out + 3) / 4; q += nthr) {
-            const unsigned e0 = 4 * q;
-            unsigned n = e0 / fw;
-            unsigned jj = e0 - n * fw;
-            unsigned fi = jj / W, w = jj - fi * W;
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float x = 0.f;
-                if (e0 + k < per_out) {
-                    x = src0[(long)w * sw + (long)(n * df + fi)];
-                    if (stdz) x = __fdiv_rn(__fsub_rn(x, p.forcing_mean[fi]), p.forcing_std[fi]);
-                }
-                v[k] = x;
-                if (++w == W) {
-                    w = 0;
-                    if (++fi == df) {
-                        fi = 0;
-                        ++n;
-                    }
-                }
-            }
-            if (vec) {
-                *reinterpret_cast<f32x4*>(dst + e0) = f32x4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (e0 + k < per_out) dst[e0 + k] = v[k];
-            }
-        }
-    }
-}
-
-#endif
-
 // One element of the AdamW update, shared by every kernel that applies it (adamw_kernel here, adamw_ctl_body in
 // nlam_optctl.inc), with the roundings of the code the compiler made of adamw_kernel's plain expressions: it fused
 // 1 - lr * wd into one fma (hoisted by the callers as `decay`) and nothing else, so every other product and sum is rounded
@@ -6828,79 +6629,6 @@ int32_t nlam_detail::wgrad_dma_group(const nlam_wgrad_t* ps, int n, hipStream_t 
 #if NLAM_IN_TU(5)
 extern "C" {
 
-int64_t nlam_window_len(int64_t n_state_times, int64_t n_forcing_times, int32_t ar_steps, int32_t past, int32_t future) {
-    const int64_t window = (int64_t)(past > 2 ? past : 2) + ar_steps + future;
-    int64_t n = n_state_times - window + 1;
-    if (n_forcing_times >= 0 && n_forcing_times - window + 1 < n) n = n_forcing_times - window + 1;
-    return n > 0 ? n : 0;
-}
-
-int32_t nlam_window_batch(const nlam_window_t* p, void* hip_stream) {
-    NLAM_RANGE("nlam_window_batch");
-    if (p == nullptr || p->state == nullptr || p->sample_idx == nullptr || p->init_states == nullptr || p->target_states == nullptr)
-        return NLAM_EINVAL;
-    if (p->batch < 0 || p->nodes < 0 || p->d_state < 1 || p->d_forcing < 0 || p->ar_steps < 1 || p->ar_steps > 256 ||
-        p->num_past_forcing_steps < 0 || p->num_future_forcing_steps < 0 || p->n_times < 1)
-        return NLAM_EINVAL;
-    if (p->d_forcing > 0 && (p->forcing == nullptr || p->forcing_windowed == nullptr)) return NLAM_EINVAL;
-    if ((p->state_mean == nullptr) != (p->state_std == nullptr) || (p->forcing_mean == nullptr) != (p->forcing_std == nullptr)) return NLAM_EINVAL;
-    if (p->state_mean != nullptr && p->d_forcing > 0 && p->forcing_mean == nullptr) return NLAM_EINVAL;   // all or nothing, as the reference's hook
-    if (nlam_window_len(p->n_times, p->d_forcing > 0 ? p->n_times : -1, p->ar_steps, p->num_past_forcing_steps, p->num_future_forcing_steps) < 1)
-        return NLAM_EINVAL;   // the series is shorter than one sample
-    if (p->batch == 0 || p->nodes == 0) return 0;
-    const long window = p->num_past_forcing_steps + p->num_future_forcing_steps + 1;
-    const long e_state = (long)p->nodes * p->d_state;                       // one row of the launch (blockIdx.y)
-    const long e_forc = (long)p->nodes * p->d_forcing * window;
-    if (e_state >= (1L << 31) || e_forc >= (1L << 31) || p->batch > 65535) return NLAM_EUNSUP;   // 32-bit offsets inside a row
-    long blocks = ((e_state > e_forc ? e_state : e_forc) + 2047) / 2048;    // four elements per thread, two rounds
-    if (blocks < 1) blocks = 1;
-    if (blocks > 512) blocks = 512;
-    const int rows = 2 + p->ar_steps + (p->d_forcing > 0 ? p->ar_steps : 0);
-    hipLaunchKernelGGL(window_batch_kernel, dim3((int)blocks, rows, p->batch), dim3(256), 0, (hipStream_t)hip_stream, *p);
-    return (int32_t)hipGetLastError();
-}
-
-int32_t nlam_window_batch_ens(const nlam_window_ens_t* p, void* hip_stream) {
-    NLAM_RANGE("nlam_window_batch_ens");
-    if (p == nullptr || p->state == nullptr || p->sample_idx == nullptr || p->init_states == nullptr || p->target_states == nullptr)
-        return NLAM_EINVAL;
-    if (p->batch < 0 || p->nodes < 0 || p->d_state < 1 || p->d_forcing < 0 || p->ar_steps < 1 || p->ar_steps > 256 ||
-        p->num_past_forcing_steps < 0 || p->num_future_forcing_steps < 0 || p->n_times < 1 || p->members < 1 ||
-        (p->is_forecast != 0 && p->is_forecast != 1))
-        return NLAM_EINVAL;
-    if (p->state_stride_sample < 0 || p->state_stride_step < 0 || p->state_stride_member < 0 || p->forcing_stride_sample < 0 ||
-        p->forcing_stride_step < 0 || p->forcing_stride_member < 0)
-        return NLAM_EINVAL;
-    if (p->d_forcing > 0 && (p->forcing == nullptr || p->forcing_windowed == nullptr)) return NLAM_EINVAL;
-    if ((p->state_mean == nullptr) != (p->state_std == nullptr) || (p->forcing_mean == nullptr) != (p->forcing_std == nullptr)) return NLAM_EINVAL;
-    if (p->state_mean != nullptr && p->d_forcing > 0 && p->forcing_mean == nullptr) return NLAM_EINVAL;   // all or nothing, as the reference's hook
-    const int32_t past = p->num_past_forcing_steps, fut = p->num_future_forcing_steps;
-    const int64_t off = past > 2 ? past : 2;
-    int64_t base_len;
-    if (p->is_forecast) {
-        if ((p->times == nullptr) != (p->elapsed == nullptr)) return NLAM_EINVAL;   // a valid time needs both stamps
-        if (p->state_steps < off + p->ar_steps) return NLAM_EINVAL;                 // lead-time axis too short (weather_dataset.py:147-160)
-        if (p->d_forcing > 0 && p->forcing_steps < off + p->ar_steps + fut) return NLAM_EINVAL;   // (:162-180)
-        base_len = p->n_times;
-    } else {
-        if (p->elapsed != nullptr) return NLAM_EINVAL;
-        base_len = nlam_window_len(p->n_times, p->d_forcing > 0 ? p->n_times : -1, p->ar_steps, past, fut);
-        if (base_len < 1) return NLAM_EINVAL;   // the series is shorter than one sample
-    }
-    if (p->batch == 0 || p->nodes == 0) return 0;
-    const long window = past + fut + 1;
-    const long e_state = (long)p->nodes * p->d_state;
-    const long e_forc = (long)p->nodes * p->d_forcing * window;
-    if (e_state >= (1L << 31) || e_forc >= (1L << 31) || p->batch > 65535) return NLAM_EUNSUP;   // 32-bit offsets inside a row
-    long blocks = ((e_state > e_forc ? e_state : e_forc) + 2047) / 2048;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 512) blocks = 512;
-    const int rows = 2 + p->ar_steps + (p->d_forcing > 0 ? p->ar_steps : 0);
-    hipLaunchKernelGGL(window_batch_ens_kernel, dim3((int)blocks, rows, p->batch), dim3(256), 0, (hipStream_t)hip_stream, *p,
-                       (long)(base_len * p->members));
-    return (int32_t)hipGetLastError();
-}
-
 int32_t nlam_pre_add_supported(const nlam_mlp_fwd_t* p) {
     /* would nlam_mlp_fwd (and the matching nlam_mlp_bwd) run this NLAM_F_PRE_ADD problem on a factorised kernel?
        Only shapes, flags, ntiles and batch are read. */
@@ -7589,6 +7317,13 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 }  // extern "C"
 #endif
 
+// The resident series: packing (nlam_packed.inc), then the row loops every data kernel reads them through and the window batches
+// (nlam_series.inc: helpers for slices 1 and 5, the window kernels in 5); the forecast kernels and the moments build on those.
+#include "nlam_packed.inc"
+#if NLAM_IN_TU(1) || NLAM_IN_TU(5)
+#include "nlam_series.inc"
+#endif
+
 #if NLAM_IN_TU(1)
 #include "nlam_forecast.inc"   // beside the step-tail kernels: the forecast tail shares step_tail_pred and StepTailTables
 #include "nlam_ensemble.inc"   // the sampled-ensemble launches of the same recorded step
@@ -7605,6 +7340,3 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 #if NLAM_IN_TU(6)
 #include "nlam_gemm.inc"
 #endif
-
-// packed int16 series: its sections pick their own slices (5 beside the window and moments kernels, 1 beside the forecast pair)
-#include "nlam_packed.inc"

@@ -10,6 +10,8 @@
 // data's offset, where fp32 lanes would lose digits on 70 M-element samples with a large mean.  The lanes' sums meet in
 // LDS in a fixed order, the spans' partial sums go to the workspace, and moments_finish_kernel adds them in a fixed order.
 // The split depends on nodes and nvars only: a sample's row is bit-identical whichever [first, first + count) covers it.
+// nlam_window_moments_q16 is the same kernel over a packed int16 series (Series<int16_t>, mom_load of nlam_series.inc): the
+// quads are decoded on load and everything behind the load is shared, so its rows are those of the decoded series.
 // Included from nlam_hip.hip inside NLAM_IN_TU(5).
 
 namespace {
@@ -34,19 +36,11 @@ __host__ __device__ inline MomSplit mom_split(int nodes, int nvars) {
     return MomSplit{per_row, span, (int)((per_row + span - 1) / span)};
 }
 
-// quad e .. e + 3 of a row (entries at or beyond e1 read as 0 and are not counted by the caller)
-__device__ __forceinline__ f32x4 mom_load(const float* row, long e, long e1, bool vec) {
-    if (vec && e + 3 < e1) return *reinterpret_cast<const f32x4*>(row + e);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (e + k < e1) v[k] = row[e + k];
-    return v;
-}
-
-// workspace[(o * nslot + slot) * 2 * nvars + j]: j < nvars the sum of feature j, then the sums of squares
-template <bool DIFF>
-__global__ __launch_bounds__(kMomThreads) void moments_partials_kernel(const nlam_moments_t p, long n_flat, long span, int nslot) {
+// workspace[(o * nslot + slot) * 2 * nvars + j]: j < nvars the sum of feature j, then the sums of squares.  T: the element type
+// of the series (mom_load): a packed row is decoded with the lane's four (scale, offset) pairs, kept in registers.
+template <bool DIFF, typename T>
+__global__ __launch_bounds__(kMomThreads) void moments_partials_kernel(const nlam_moments_t p, const Series<T> ser, long n_flat,
+                                                                       long span, int nslot) {
     __shared__ double red[2 * 4 * kMomThreads];   // [2][W] the lanes' sums and sums of squares
     __shared__ double seg[2 * kMomThreads];       // [G][2 * nvars] segment sums (G * 2 * nvars <= 512)
     const int F = p.nvars;
@@ -61,18 +55,27 @@ __global__ __launch_bounds__(kMomThreads) void moments_partials_kernel(const nla
     const long per_row = (long)p.nodes * F;
     const long e0 = slot * span, e1 = min(per_row, e0 + span);
     const int tid = threadIdx.x;
-    const float* base = p.series + s * p.stride_sample + m * p.stride_member;
+    const T* base = ser.base + s * p.stride_sample + m * p.stride_member;
     double sum[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
     if (tid < lanes) {
+        float sc[4], of[4];   // the lane's decode pairs; T = float: never set and never read (mom_load<float> ignores them)
+        if constexpr (!std::is_same_v<T, float>) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int f = (4 * tid + kk) % F;
+                sc[kk] = ser.scale[f];
+                of[kk] = ser.offset[f];
+            }
+        }
         if constexpr (!DIFF) {
             for (long c = e0; c < e1; c += (long)W * kMomQuads) {
 #pragma unroll 2
                 for (int r = 0; r < p.nrows; ++r) {
-                    const float* row = base + (long)(p.row_begin + r) * p.stride_step;
-                    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+                    const T* row = base + (long)(p.row_begin + r) * p.stride_step;
+                    const bool vec = (reinterpret_cast<uintptr_t>(row) & kQuadAlign<T>) == 0;
                     f32x4 v[kMomQuads];
 #pragma unroll
-                    for (int q = 0; q < kMomQuads; ++q) v[q] = mom_load(row, c + (long)q * W + 4 * tid, e1, vec);
+                    for (int q = 0; q < kMomQuads; ++q) v[q] = mom_load(row, c + (long)q * W + 4 * tid, e1, vec, sc, of);
 #pragma unroll
                     for (int q = 0; q < kMomQuads; ++q) {
                         const long e = c + (long)q * W + 4 * tid;
@@ -100,11 +103,11 @@ __global__ __launch_bounds__(kMomThreads) void moments_partials_kernel(const nla
                 float zp[kMomQuads][4] = {};
 #pragma unroll 2
                 for (int r = 0; r < nsub; ++r) {
-                    const float* row = base + (long)(p.row_begin + k + r * S) * p.stride_step;
-                    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+                    const T* row = base + (long)(p.row_begin + k + r * S) * p.stride_step;
+                    const bool vec = (reinterpret_cast<uintptr_t>(row) & kQuadAlign<T>) == 0;
                     f32x4 v[kMomQuads];
 #pragma unroll
-                    for (int q = 0; q < kMomQuads; ++q) v[q] = mom_load(row, c + (long)q * W + 4 * tid, e1, vec);
+                    for (int q = 0; q < kMomQuads; ++q) v[q] = mom_load(row, c + (long)q * W + 4 * tid, e1, vec, sc, of);
 #pragma unroll
                     for (int q = 0; q < kMomQuads; ++q) {
                         const long e = c + (long)q * W + 4 * tid;
@@ -172,19 +175,10 @@ __global__ __launch_bounds__(kMomThreads) void moments_finish_kernel(const nlam_
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t nlam_moments_workspace_doubles(int32_t nodes, int32_t nvars, int64_t count, int32_t step) {
-    if (nodes < 1 || nvars < 1 || nvars > NLAM_MOMENTS_MAX_VARS || count < 1 || step < 0) return NLAM_EINVAL;
-    const MomSplit sp = mom_split(nodes, nvars);
-    return count * (step > 0 ? step : 1) * sp.nslot * 2L * nvars;
-}
-
-int32_t nlam_window_moments(const nlam_moments_t* p, void* hip_stream) {
-    NLAM_RANGE("nlam_window_moments");
-    if (p == nullptr || p->series == nullptr || p->workspace == nullptr || p->out_mean == nullptr || p->out_sq == nullptr)
+// nlam_window_moments and nlam_window_moments_q16: every check, then the partial sums over `ser` and the finish
+template <typename T>
+int32_t moments_launch(const nlam_moments_t* p, const Series<T>& ser, hipStream_t stream) {
+    if (p == nullptr || ser.base == nullptr || p->workspace == nullptr || p->out_mean == nullptr || p->out_sq == nullptr)
         return NLAM_EINVAL;
     if (p->nodes < 1 || p->nvars < 1 || p->members < 1 || p->n_times < 1 || p->nrows < 1 || p->row_begin < 0 || p->step < 0 ||
         p->first < 0 || p->count < 1 || (p->is_forecast != 0 && p->is_forecast != 1))
@@ -214,16 +208,37 @@ int32_t nlam_window_moments(const nlam_moments_t* p, void* hip_stream) {
     const int64_t blocks = n_out * sp.nslot;
     if (n_out > 0x7fffffffL || blocks > 0x7fffffffL) return NLAM_EUNSUP;
     if (p->workspace_doubles < blocks * 2L * p->nvars) return NLAM_EINVAL;
-    const hipStream_t stream = (hipStream_t)hip_stream;
     const double count = (double)(p->step > 0 ? p->nrows / p->step - 1 : p->nrows) * p->nodes;
     if (p->step > 0)
-        hipLaunchKernelGGL(moments_partials_kernel<true>, dim3((unsigned)blocks), dim3(kMomThreads), 0, stream, *p, (long)n_flat,
-                           sp.span, sp.nslot);
+        hipLaunchKernelGGL((moments_partials_kernel<true, T>), dim3((unsigned)blocks), dim3(kMomThreads), 0, stream, *p, ser,
+                           (long)n_flat, sp.span, sp.nslot);
     else
-        hipLaunchKernelGGL(moments_partials_kernel<false>, dim3((unsigned)blocks), dim3(kMomThreads), 0, stream, *p, (long)n_flat,
-                           sp.span, sp.nslot);
+        hipLaunchKernelGGL((moments_partials_kernel<false, T>), dim3((unsigned)blocks), dim3(kMomThreads), 0, stream, *p, ser,
+                           (long)n_flat, sp.span, sp.nslot);
     hipLaunchKernelGGL(moments_finish_kernel, dim3((unsigned)n_out), dim3(kMomThreads), 0, stream, *p, sp.nslot, count);
     return (int32_t)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nlam_moments_workspace_doubles(int32_t nodes, int32_t nvars, int64_t count, int32_t step) {
+    if (nodes < 1 || nvars < 1 || nvars > NLAM_MOMENTS_MAX_VARS || count < 1 || step < 0) return NLAM_EINVAL;
+    const MomSplit sp = mom_split(nodes, nvars);
+    return count * (step > 0 ? step : 1) * sp.nslot * 2L * nvars;
+}
+
+int32_t nlam_window_moments(const nlam_moments_t* p, void* hip_stream) {
+    NLAM_RANGE("nlam_window_moments");
+    return moments_launch(p, Series<float>{p != nullptr ? p->series : nullptr, nullptr, nullptr}, (hipStream_t)hip_stream);
+}
+
+int32_t nlam_window_moments_q16(const nlam_moments_t* p, const int16_t* series, const float* scale, const float* offset,
+                                void* hip_stream) {
+    NLAM_RANGE("nlam_window_moments_q16");
+    if (scale == nullptr || offset == nullptr) return NLAM_EINVAL;
+    return moments_launch(p, Series<int16_t>{series, scale, offset}, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"
