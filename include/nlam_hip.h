@@ -65,6 +65,9 @@
  *   nlam_ens_products, nlam_ens_products_workspace_floats
  *       what the ensemble is made for, per lead of that step: exceedance probabilities of threshold events and quantile fields
  *       from the sorted members, with Brier score, reliability table, pinball loss and coverage counts.
+ *   nlam_ens_neighbourhood, nlam_ens_neighbourhood_workspace_floats
+ *       the same events on the grid as a lattice: the fraction of (member, cell) pairs in the event inside square windows of a
+ *       ladder of radii, and the two sums of the fractions skill score, from integer summed-area tables.
  *   nlam_latent_kl_fwd, nlam_latent_kl_bwd, nlam_latent_kl_workspace_floats
  *       the variational training objective of Graph-EFM: the reparameterised posterior draw from that generator and the KL
  *       divergence from the prior as one pass with a fixed-order reduction, and its elementwise backward.
@@ -1210,6 +1213,53 @@ int32_t nlam_ens_products(const nlam_ens_products_t* p, void* hip_stream);
  * NLAM_ENS_MAX_MEMBERS, nvars > NLAM_EVAL_MAX_VARS, events > NLAM_ENS_MAX_EVENTS or quantiles > NLAM_ENS_MAX_QUANTILES */
 int64_t nlam_ens_products_workspace_floats(int32_t starts, int32_t members, int32_t nodes, int32_t nvars, int32_t events,
                                            int32_t quantiles);
+
+/* Neighbourhood probabilities of the same events and the sums of the fractions skill score (FSS, Roberts and Lean 2008), for
+ * lead slot k = *lead (only read; nothing is written once k >= max_lead): after nlam_ens_products, before nlam_forecast_finish.
+ * prev / truth / row_weight / lead and the three event tables as in nlam_ens_products_t (the same device tables; truth may be
+ * NULL).  The grid is nx x ny, node n = i * ny + j; N = nx * ny, M = members, W = scales, w_n = row_weight[n], "live" =
+ * w_n != 0.  C(n) = the members of variable event_var[e] at node n in event e, O(n) = 1 when the truth is in it, else 0.
+ * radius is device memory, read by the launch: a replay sees new values.  With r = radius[w], the window W_r(n) is the nodes
+ * (i', j') of the grid with |i' - i| <= r and |j' - j| <= r: no wrap, no padding, a negative radius acts as 0 and one larger than
+ * the grid gives the whole grid.  Three integers per (event, scale, node):
+ *   A  = the live nodes of W_r(n),   SC = sum of C over them,   SO = sum of O over them
+ *   nprob[s][k][e][w][n] = (float)SC / (float)(M A), NaN where A = 0; written for every node, live or not
+ * and with truth given, of = (float)SO / (float)A:
+ *   fbs[s][k][e][w]      = sum over live n of w_n (nprob - of)^2
+ *   fbs_ref[s][k][e][w]  = sum over live n of w_n (nprob^2 + of^2)              FSS = 1 - sum_s fbs / sum_s fbs_ref
+ * members * nx * ny <= 2^24 is required: both conversions are then exact and nprob is one correctly rounded division; at r = 0
+ * nprob of a live node is prob of nlam_ens_products bit for bit.  The window sums come from int32 summed-area tables in the
+ * workspace (exact in any order; the cost does not depend on the radii); fbs and fbs_ref from per-workgroup partial sums in the
+ * workspace and one finishing launch that adds them in a fixed order: no floating-point atomics, bit-identical from run to run.
+ * Five launches with truth, four without, for every size.  The launch clamps event_var into [0, d_state) and treats any
+ * non-zero sense as 1.
+ * NLAM_EINVAL for null required pointers (prev, row_weight, lead, the three event tables, radius, nprob, workspace), sizes < 1,
+ * a short workspace, fbs or fbs_ref without truth, truth without both; NLAM_EUNSUP for members > NLAM_ENS_MAX_MEMBERS, d_state >
+ * NLAM_EVAL_MAX_VARS, events > NLAM_ENS_MAX_EVENTS, scales > NLAM_NBR_MAX_SCALES, starts > 65535, members * nx * ny > 2^24.
+ * Every check comes before any launch; no allocation, no host synchronisation. */
+#define NLAM_NBR_MAX_SCALES 8
+typedef struct {
+    const float* prev;            /* (starts * members, nx * ny, d_state) standardised states of this lead */
+    const float* truth;           /* (starts * members, nx * ny, d_state) standardised analysis, or NULL: no scores */
+    const float* row_weight;      /* (nx * ny) */
+    const int32_t* lead;          /* device (1): k, only read */
+    const int32_t* event_var;     /* device (events) */
+    const int32_t* event_sense;   /* device (events): 0 above, 1 below */
+    const float* event_thr;       /* device (events): standardised units */
+    const int32_t* radius;        /* device (scales): cells */
+    float* nprob;                 /* (starts, max_lead, events, scales, nx * ny) */
+    float* fbs;                   /* (starts, max_lead, events, scales) */
+    float* fbs_ref;               /* (starts, max_lead, events, scales) */
+    float* workspace;             /* nlam_ens_neighbourhood_workspace_floats(starts, members, nx, ny, d_state, events, scales) floats */
+    int64_t workspace_floats;
+    int32_t starts, members, nx, ny;
+    int32_t d_state, max_lead, events, scales;
+} nlam_ens_neighbourhood_t;
+int32_t nlam_ens_neighbourhood(const nlam_ens_neighbourhood_t* p, void* hip_stream);
+/* floats of nlam_ens_neighbourhood_t.workspace: nx ny (1 + 2 starts events) table words and 2 starts events scales words per 256
+ * nodes; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP as nlam_ens_neighbourhood */
+int64_t nlam_ens_neighbourhood_workspace_floats(int32_t starts, int32_t members, int32_t nx, int32_t ny, int32_t nvars, int32_t events,
+                                                int32_t scales);
 
 /* The posterior draw and the KL term of the Graph-EFM training objective (Oskarsson et al. 2024, section 3; models.EFMForecaster)
  * inside the recorded training step.  With D = latent_dim, u = 1e-4, pq (batch, rows, 2 D) the encoder's parameters (always

@@ -103,6 +103,7 @@ EVAL_MAX_VARS = 256   # NLAM_EVAL_MAX_VARS
 ENS_MAX_MEMBERS = 64  # NLAM_ENS_MAX_MEMBERS: members of one nlam_ens_scores call
 ENS_MAX_EVENTS = 32   # NLAM_ENS_MAX_EVENTS: threshold events of one nlam_ens_products call
 ENS_MAX_QUANTILES = 16   # NLAM_ENS_MAX_QUANTILES: quantile levels of one nlam_ens_products call
+NBR_MAX_SCALES = 8    # NLAM_NBR_MAX_SCALES: window radii of one nlam_ens_neighbourhood call
 MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
 # learning-rate schedules of nlam_adamw_step_controlled (NLAM_SCHED_*) and the words of its control block
 SCHED_KINDS = {"constant": 1, "warmup_cosine": 2, "warmup_linear": 3}
@@ -207,6 +208,8 @@ EXPORTS = [
     "nlam_ens_scores_workspace_floats",
     "nlam_ens_products",
     "nlam_ens_products_workspace_floats",
+    "nlam_ens_neighbourhood",
+    "nlam_ens_neighbourhood_workspace_floats",
     "nlam_latent_kl_fwd",
     "nlam_latent_kl_bwd",
     "nlam_latent_kl_workspace_floats",
@@ -551,6 +554,34 @@ class EnsProducts(C.Structure):
         ("events", C.c_int32),
         ("quantiles", C.c_int32),
         ("_pad", C.c_int32),
+    ]
+
+
+class EnsNeighbourhood(C.Structure):
+    """nlam_ens_neighbourhood_t: neighbourhood probabilities and the sums of the fractions skill score of one lead."""
+
+    _fields_ = [
+        ("prev", C.c_void_p),
+        ("truth", C.c_void_p),
+        ("row_weight", C.c_void_p),
+        ("lead", C.c_void_p),
+        ("event_var", C.c_void_p),
+        ("event_sense", C.c_void_p),
+        ("event_thr", C.c_void_p),
+        ("radius", C.c_void_p),
+        ("nprob", C.c_void_p),
+        ("fbs", C.c_void_p),
+        ("fbs_ref", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("starts", C.c_int32),
+        ("members", C.c_int32),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("d_state", C.c_int32),
+        ("max_lead", C.c_int32),
+        ("events", C.c_int32),
+        ("scales", C.c_int32),
     ]
 
 
@@ -1012,6 +1043,10 @@ def load():
     lib.nlam_ens_products.restype = i32
     lib.nlam_ens_products_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
     lib.nlam_ens_products_workspace_floats.restype = i64
+    lib.nlam_ens_neighbourhood.argtypes = [C.POINTER(EnsNeighbourhood), vp]
+    lib.nlam_ens_neighbourhood.restype = i32
+    lib.nlam_ens_neighbourhood_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+    lib.nlam_ens_neighbourhood_workspace_floats.restype = i64
     lib.nlam_latent_kl_fwd.argtypes = [C.POINTER(LatentKl), vp]
     lib.nlam_latent_kl_fwd.restype = i32
     lib.nlam_latent_kl_bwd.argtypes = [C.POINTER(LatentKl), vp]

@@ -32,6 +32,13 @@ threshold and quantile fields, from the members sorted in registers, with their 
     ens = EnsembleForecast(step, dataset, 40, members=16, events=[("t2m", "<", 273.15)], quantiles=[0.1, 0.5, 0.9])
     pr = ens.run([0]).products      # EnsembleProducts: pr.prob (S, L, E, N), pr.quantile (S, L, Q, N, F)
     pr.brier_score(), pr.reliability(), pr.pinball_loss(step.state_std), pr.coverage()
+
+``neighbourhoods`` (with ``events`` and the ``grid_shape`` of the lattice) adds ``nlam_ens_neighbourhood``: per event and window
+radius the fraction of (member, cell) pairs in the event around every cell, and with ``verify`` the fractions skill score.
+
+    ens = EnsembleForecast(step, dataset, 40, members=16, events=[("tp", ">", 1e-3)], neighbourhoods=[0, 1, 2, 5, 10],
+                           grid_shape=(nx, ny))
+    pr = ens.run([0]).products      # pr.nprob (S, L, E, W, N);  pr.fss() (L, E, W)
 """
 from __future__ import annotations
 
@@ -439,6 +446,10 @@ class EnsembleProducts(NamedTuple):
     levels: tuple                       # the quantile levels
     n_members: int
     n_live: int                         # nodes with a non-zero weight
+    nprob: Optional[torch.Tensor] = None     # (S, leads, E, W, N) fraction of the (member, live cell) pairs of the window in the event
+    fbs: Optional[torch.Tensor] = None       # (S, leads, E, W) sum_n w_n (nprob - observed fraction)^2
+    fbs_ref: Optional[torch.Tensor] = None   # (S, leads, E, W) sum_n w_n (nprob^2 + observed fraction^2)
+    radii: tuple = ()                        # the window radii in cells (``neighbourhoods``)
 
     def _scores(self, t, what):
         if t is None:
@@ -465,6 +476,12 @@ class EnsembleProducts(NamedTuple):
         """(leads, Q, F) fraction of the live nodes, over all starts, whose truth lies below the quantile: ``q`` when calibrated."""
         below = self._scores(self.below, "coverage")
         return below.sum(0).to(torch.float32) / float(below.shape[0] * self.n_live)
+
+    def fss(self):
+        """(leads, E, W) fractions skill score of every event and window radius over all starts: ``1 - sum_s fbs / sum_s fbs_ref``,
+        in [0, 1], NaN where no live window holds a member or a truth in the event."""
+        ref = self._scores(self.fbs_ref, "fss").sum(0)
+        return 1.0 - self.fbs.sum(0) / ref
 
 
 def quantile_tables(levels, members):
@@ -513,6 +530,39 @@ def parse_products(events, quantiles, var_names, n_vars):
     if len(levels) > L.ENS_MAX_QUANTILES:
         raise ValueError(f"EnsembleForecast: at most {L.ENS_MAX_QUANTILES} quantile levels, got {len(levels)}")
     return ev, levels
+
+
+def parse_neighbourhoods(neighbourhoods, grid_shape, n_events, members, nodes=None):
+    """The host checks of ``EnsembleForecast(neighbourhoods=..., grid_shape=...)``: ``(radii, (nx, ny))``, or ``([], None)`` without
+    ``neighbourhoods``.  ValueError for radii without events, a missing grid shape or one that does not hold ``nodes`` nodes (when
+    they are known), a radius that is negative or no integer, more than ``NLAM_NBR_MAX_SCALES`` radii, and ``members * nodes`` above
+    2^24 (the window sums must stay integers a float holds).  No GPU."""
+    if neighbourhoods is None:
+        return [], None
+    radii = []
+    for r in neighbourhoods:
+        try:
+            ri = int(r)
+        except (TypeError, ValueError):
+            ri = -1
+        if isinstance(r, bool) or ri != r or ri < 0:
+            raise ValueError(f"EnsembleForecast: a neighbourhood radius is a non-negative integer number of cells, got {r!r}")
+        radii.append(min(ri, 2 ** 31 - 1))
+    if not radii:
+        raise ValueError("EnsembleForecast: neighbourhoods is empty")
+    if not n_events:
+        raise ValueError("EnsembleForecast: neighbourhoods are those of the events: give events=[...] too")
+    if len(radii) > L.NBR_MAX_SCALES:
+        raise ValueError(f"EnsembleForecast: at most {L.NBR_MAX_SCALES} neighbourhood radii, got {len(radii)}")
+    try:
+        nx, ny = (int(v) for v in grid_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"EnsembleForecast: neighbourhoods need grid_shape=(nx, ny), got {grid_shape!r}") from None
+    if nx < 1 or ny < 1 or (nodes is not None and nx * ny != nodes):
+        raise ValueError(f"EnsembleForecast: grid_shape {(nx, ny)} does not hold the {nodes} grid nodes")
+    if members * nx * ny > 2 ** 24:
+        raise ValueError(f"EnsembleForecast: neighbourhoods need members * nodes <= 2^24, got {members} * {nx * ny}")
+    return radii, (nx, ny)
 
 
 class EnsembleResult(NamedTuple):
@@ -586,7 +636,8 @@ class EnsembleResult(NamedTuple):
 class EnsembleForecast(Forecast):
     """``members`` forecasts from each of ``n_starts`` initial times, as ONE recorded step over the batch ``n_starts * members``:
 
-        head -> embed + prior parameters -> nlam_latent_sample -> decoder -> tail -> nlam_ens_scores [-> nlam_ens_products] -> finish
+        head -> embed + prior parameters -> nlam_latent_sample -> decoder -> tail -> nlam_ens_scores [-> nlam_ens_products
+             [-> nlam_ens_neighbourhood]] -> finish
 
     replayed per lead.  The predictor is a Graph-EFM (``GraphEFM``, ``GraphEFMMultiScale``; ``can_return_raw_delta()``): every
     lead draws a new latent sample per member from Philox4x32-10 keyed by ``seed`` and counted by (lead, member, start time),
@@ -603,12 +654,17 @@ class EnsembleForecast(Forecast):
     index, ``">"`` or ``"<"`` (equality never counts), a threshold in physical units -- and ``quantiles``: levels in [0, 1].  Either
     adds ``nlam_ens_products`` after ``nlam_ens_scores`` in the recorded step (``EnsembleResult.products``: ``4 S L N (E + Q F)``
     bytes of fields; their scores with ``verify``).  Thresholds live in a device table in standardised units, ``(thr - mean) / std``
-    computed in float64: ``set_thresholds`` rewrites it without a new recording.  With neither, nothing is allocated or launched."""
+    computed in float64: ``set_thresholds`` rewrites it without a new recording.  With neither, nothing is allocated or launched.
+    ``neighbourhoods``: window radii in cells (at most 8) on the ``grid_shape = (nx, ny)`` lattice, node ``n = i * ny + j`` as
+    ``graph.py`` numbers it; it needs ``events`` and ``members * nodes <= 2^24``.  It adds ``nlam_ens_neighbourhood`` behind
+    ``nlam_ens_products`` (5 launches per lead with ``verify``, 4 without, for every size): ``products.nprob`` takes ``4 S L E W N``
+    bytes, ``fbs`` / ``fbs_ref`` / ``fss()`` come with ``verify``.  The radii live in a device table (``set_radii``), and the event
+    tables are shared, so ``set_thresholds`` moves both launches.  With ``neighbourhoods=None`` nothing is allocated or launched."""
 
     _serves_latent = True
 
     def __init__(self, step, dataset, max_lead, members, n_starts=1, seed=0, verify=True, use_graph=True, autocast_dtype=None,
-                 record_noise=False, events=None, quantiles=None):
+                 record_noise=False, events=None, quantiles=None, neighbourhoods=None, grid_shape=None):
         members, n_starts = int(members), int(n_starts)
         if not 1 <= members <= L.ENS_MAX_MEMBERS:
             raise ValueError(f"EnsembleForecast: members {members} outside [1, {L.ENS_MAX_MEMBERS}]")
@@ -616,6 +672,9 @@ class EnsembleForecast(Forecast):
             raise ValueError(f"EnsembleForecast: n_starts {n_starts} must be >= 1")
         self._events, self._levels = parse_products(events, quantiles, getattr(step, "state_var_names", None),
                                                     int(getattr(step, "state_mean", torch.empty(0)).numel()))
+        weight = getattr(step, "interior_weight", None)
+        self._radii, self._grid = parse_neighbourhoods(neighbourhoods, grid_shape, len(self._events), members,
+                                                       None if weight is None else int(weight.numel()))
         super().__init__(step, dataset, max_lead, batch_size=n_starts * members, verify=verify, use_graph=use_graph,
                          autocast_dtype=autocast_dtype)
         S, M, B, Lm = n_starts, members, n_starts * members, self.max_lead
@@ -658,6 +717,10 @@ class EnsembleForecast(Forecast):
         self._pr = None
         if self._events or self._levels:
             self._init_products()
+        self._nb = None
+        if self._radii:
+            parse_neighbourhoods(self._radii, self._grid, len(self._events), M, N)
+            self._init_neighbourhoods()
 
     def _init_products(self):
         """The tables, outputs and argument struct of ``nlam_ens_products`` (only with ``events`` or ``quantiles``)."""
@@ -698,6 +761,42 @@ class EnsembleForecast(Forecast):
         p.workspace, p.workspace_floats = _ptr(self.products_workspace), self.products_workspace.numel()
         p.starts, p.members, p.nodes, p.d_state, p.max_lead, p.events, p.quantiles = S, M, N, F, Lm, E, Q
         self._pr = p
+
+    def _init_neighbourhoods(self):
+        """The radius table, outputs and argument struct of ``nlam_ens_neighbourhood`` (only with ``neighbourhoods``)."""
+        pr = self._pr
+        S, M, F, Lm, E, W = pr.starts, pr.members, pr.d_state, pr.max_lead, pr.events, len(self._radii)
+        (nx, ny), N = self._grid, pr.nodes
+        dev = self.start.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.radius = torch.zeros((W,), device=dev, dtype=torch.int32)
+        self.set_radii(self._radii)
+        self.nprob = torch.empty((S, Lm, E, W, N), **f32)
+        self.fbs = self.fbs_ref = None
+        nb = L.EnsNeighbourhood()
+        nb.prev, nb.truth, nb.row_weight, nb.lead = pr.prev, pr.truth, pr.row_weight, pr.lead
+        nb.event_var, nb.event_sense, nb.event_thr = pr.event_var, pr.event_sense, pr.event_thr
+        nb.radius, nb.nprob = _ptr(self.radius), _ptr(self.nprob)
+        if self.verify:
+            self.fbs, self.fbs_ref = torch.zeros((S, Lm, E, W), **f32), torch.zeros((S, Lm, E, W), **f32)
+            nb.fbs, nb.fbs_ref = _ptr(self.fbs), _ptr(self.fbs_ref)
+        nws = int(self._lib.nlam_ens_neighbourhood_workspace_floats(S, M, nx, ny, F, E, W))
+        if nws < 0:
+            raise ValueError(f"EnsembleForecast: nlam_ens_neighbourhood does not serve these sizes ({nws})")
+        self.neighbourhood_workspace = torch.empty((nws,), **f32)
+        nb.workspace, nb.workspace_floats = _ptr(self.neighbourhood_workspace), nws
+        nb.starts, nb.members, nb.nx, nb.ny, nb.d_state, nb.max_lead, nb.events, nb.scales = S, M, nx, ny, F, Lm, E, W
+        self._nb = nb
+
+    def set_radii(self, values):
+        """New window radii (cells, one per entry of ``neighbourhoods``) for the following runs: the device table is rewritten in
+        place.  No new recording, like ``set_thresholds``."""
+        values = list(values)
+        if len(values) != len(self._radii) or not values:
+            raise ValueError(f"EnsembleForecast.set_radii: {len(values)} radii for {len(self._radii)} neighbourhoods")
+        radii, _ = parse_neighbourhoods(values, self._grid, len(self._events), self.members)
+        self.radius.copy_(torch.tensor(radii, dtype=torch.int32))
+        self._radii = radii
 
     def set_thresholds(self, values):
         """New thresholds (physical units, one per event, in the order of ``events``) for the following runs: the device table
@@ -740,6 +839,8 @@ class EnsembleForecast(Forecast):
         L.check(self._lib.nlam_ens_scores(C.byref(self._e), _stream()), "nlam_ens_scores")
         if self._pr is not None:
             L.check(self._lib.nlam_ens_products(C.byref(self._pr), _stream()), "nlam_ens_products")
+        if self._nb is not None:
+            L.check(self._lib.nlam_ens_neighbourhood(C.byref(self._nb), _stream()), "nlam_ens_neighbourhood")
 
     def _install(self, given):
         """Install the recording that draws the noise (``given`` False) or reads it from ``self.noise`` (True)."""
@@ -788,5 +889,7 @@ class EnsembleForecast(Forecast):
             fields = (self.prob, self.quantile, self.brier, self.rel_count, self.rel_obs, self.pinball, self.below)
             products = EnsembleProducts(*(cut(t) for t in fields), tuple((v, "<" if sn else ">", t) for v, sn, t in self._events),
                                         tuple(self._levels), self.members, self.n_live)
+            if self._nb is not None:
+                products = products._replace(nprob=cut(self.nprob), fbs=cut(self.fbs), fbs_ref=cut(self.fbs_ref), radii=tuple(self._radii))
         return EnsembleResult(cut(self.out_state), cut(self.out_std), cut(self.valid_times), cut(self.sq), cut(self.ab),
                               cut(self.mean), cut(self.spread), *(cut(t) for t in scores), cut(noise, 0), self.members, products)

@@ -4,6 +4,7 @@
     python tools/ensemble_bench.py [--config cfg2] [--members 4 16] [--leads 40] [--rounds 3] [--out profiles/ensemble/bench.json]
     python tools/ensemble_bench.py --kernels-only      # under rocprofv3 --kernel-trace --stats: the two launches alone
     python tools/ensemble_bench.py --products [--kernels-only] [--out profiles/ensemble_products/bench.json]
+    python tools/ensemble_bench.py --neighbourhoods [0 1 2 5 10] [--out profiles/ensemble_neighbourhood/bench.json]
 
 Route "forecast": ``Forecast(step, data, L, batch_size=M, verify=True).run([start] * M)`` with the configuration's GraphLAM.
 Route "ensemble": ``EnsembleForecast(step, data, L, members=M).run([start])`` with the same predictor: the same batch, the same
@@ -16,6 +17,9 @@ The two new launches alone: 50 of them recorded into one graph and replayed betw
 ``--products`` adds the route "ensemble_products": the "ensemble" engine with 4 events and 3 quantile levels (nlam_ens_products and
 its finishing pass per lead), alternating with the others, and times that launch pair alone against its minimum bytes
 (4 S N F (M + 1) + 4 S N (E + Q F)).  Without the option the run is what it was.
+``--neighbourhoods [radii]`` (default 0 1 2 5 10; it implies ``--products``) adds the route "ensemble_neighbourhood": the
+"ensemble_products" engine with those window radii on the configuration's grid (nlam_ens_neighbourhood, five more launches per
+lead), alternating with the others, and times that launch alone beside nlam_ens_products.
 """
 import argparse
 import ctypes as C
@@ -38,8 +42,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=2, help="forecasts per timed window")
     ap.add_argument("--kernels-only", action="store_true", help="launch nlam_ens_scores and nlam_latent_sample alone (for a kernel trace)")
     ap.add_argument("--products", action="store_true", help="add the route with 4 events and 3 quantiles, and time nlam_ens_products alone")
+    ap.add_argument("--neighbourhoods", type=int, nargs="*", default=None, metavar="RADIUS",
+                    help="add the route with neighbourhood probabilities and the FSS at these radii (default 0 1 2 5 10) on top of --products")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.neighbourhoods is not None:
+        args.products = True
+        args.neighbourhoods = args.neighbourhoods or [0, 1, 2, 5, 10]
 
     import torch
 
@@ -80,6 +89,10 @@ def main():
             events = [(0, ">", 0.0), (0, "<", -1.0), (F // 2, ">", 1.5), (F - 1, "<", 0.5)]
             routes.append(("ensemble_products", lambda: EnsembleForecast(step, data, args.leads, members=M, events=events,
                                                                          quantiles=[0.1, 0.5, 0.9])))
+        if args.neighbourhoods:
+            routes.append(("ensemble_neighbourhood", lambda: EnsembleForecast(step, data, args.leads, members=M, events=events,
+                                                                              quantiles=[0.1, 0.5, 0.9], neighbourhoods=args.neighbourhoods,
+                                                                              grid_shape=(ds.nx, ds.ny))))
         for name, make in routes:
             torch.cuda.synchronize()
             before = torch.cuda.memory_allocated()
@@ -127,6 +140,18 @@ def main():
             if not args.kernels_only:
                 row["products_minus_ensemble_ms"] = row["ensemble_products"]["ms_per_lead"] - row["ensemble"]["ms_per_lead"]
             del pe
+        if args.neighbourhoods:
+            ne = engines["ensemble_neighbourhood"][0]
+            ne.run([0], leads=1)
+            ne.lead.zero_()
+            nbr_ms = kernel_ms(lambda: L.check(ne._lib.nlam_ens_neighbourhood(C.byref(ne._nb), stream()), "nlam_ens_neighbourhood"))
+            nbr_bytes = 4 * N * F * (M + 1) + 4 * N * ne._nb.events * ne._nb.scales
+            row["kernels"]["ens_neighbourhood"] = {"ms": nbr_ms, "min_bytes": nbr_bytes, "gb_per_s": nbr_bytes / nbr_ms / 1e6,
+                                                   "events": ne._nb.events, "radii": list(args.neighbourhoods),
+                                                   "grid": [ds.nx, ds.ny]}
+            if not args.kernels_only:
+                row["neighbourhood_minus_products_ms"] = row["ensemble_neighbourhood"]["ms_per_lead"] - row["ensemble_products"]["ms_per_lead"]
+            del ne
         out["members"][str(M)] = row
         del engines, ens, efm_eng
         torch.cuda.empty_cache()
