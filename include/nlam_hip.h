@@ -1429,7 +1429,8 @@ int32_t nlam_window_batch_ens(const nlam_window_ens_t* p, void* hip_stream);
  * neural_lam/datastore/npyfilesmeps/compute_standardization_stats.py; no batch is materialised).  Addressing as
  * nlam_window_ens_t: element (sample s, member m, row j) is the contiguous (nodes x nvars) block at
  *   series + s * stride_sample + j * stride_step + m * stride_member      (floats, 64-bit)
- * for the flat samples idx = first ... first + count - 1, (s, m) = divmod(idx, members), clamped to [0, base_len * members)
+ * for the flat samples idx = first ... first + count - 1, (s, m) = divmod(idx, members), all inside [0, base_len * members):
+ * a range that leaves it is refused, no index is clamped
  * (base_len: n_times - (row_begin + nrows) + 1 for analysis data -- nlam_window_len with past = future = 0 when
  * row_begin + nrows = 2 + ar_steps, sample s reading time steps s + j -- and n_times for forecast data).  The
  * rows of a sample are j = row_begin ... row_begin + nrows - 1 (the state: 0 ... ar_steps + 1; the forcing with no past /
@@ -1441,7 +1442,8 @@ int32_t nlam_window_batch_ens(const nlam_window_ens_t* p, void* hip_stream);
  *     d = (x[b] - mean) / std - (x[a] - mean) / std in fp32 (IEEE sub, div, sub, in this order); out_mean / out_sq are the
  *     means of d and d^2 over pairs and nodes.  Output row i * step + k (sample-major); count * step rows.  Needs at least
  *     one pair (nrows / step >= 2).
- * Accumulation is fp64 from the first element: a workgroup owns a fixed node range of one output row; its partial sums
+ * Accumulation is fp64 from the first element: a workgroup owns a fixed span of the elements of one output row's
+ * (nodes x nvars) blocks (whole chunks of 8 * lanes elements, lanes = (256 / nvars) * nvars; not whole nodes); its partial sums
  * go to `workspace` and a second launch adds them in a fixed order (bit-identical run to run; the split depends on nodes
  * and nvars only, so a sample's row does not depend on first / count).  No atomics, no allocation, no host
  * synchronisation.  NLAM_EINVAL (before any launch) for null pointers, sizes < 1, negative strides, samples outside
