@@ -40,6 +40,8 @@ C_Z, C_GRAW, C_G = 13, 11, 8
 # the launcher's cap is the KL's (csrc/nlam_crps_ens.inc launches latent_kl_blocks(nodes * nvars) workgroups per item): MAX_BLOCKS = 64
 # workgroups of 256 threads, a quad of 4 elements per thread -- one pass of the capped grid covers PASS_ELEMENTS = 65536 elements
 CRPS_SHAPES = [(1, 2, 5, 3), (3, 3, 7, 8), (2, 4, 1, 17), (2, 8, 33, 5), (1, 5, 9, 4), (1, 16, 9, 4), (2, 2, 3900, 17), (1, 2, 4100, 16)]
+# 66 300 elements per item, past the 64-block cap, for the instantiations M = 3, 4, 8 and the generic one (M = 5, 16)
+CRPS_SHAPES += [(1, M, 3900, 17) for M in (3, 4, 8, 5, 16)]
 DRAW_SHAPES = [(1, 5, 3), (3, 7, 8), (2, 1031, 65), (1, 1100, 64)]
 
 

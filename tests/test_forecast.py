@@ -250,11 +250,11 @@ def _stream():
 N_TIMES, NODES, NVARS, BATCH, LEAD = 16, 37, 5, 3, 4
 
 
-def _series(dev, d_forcing, nodes=NODES, seed=0):
+def _series(dev, d_forcing, nodes=NODES, seed=0, nvars=NVARS):
     g = torch.Generator().manual_seed(seed)
-    state = (torch.randn(N_TIMES, nodes, NVARS, generator=g) * 2.0 + 0.5).to(dev)
+    state = (torch.randn(N_TIMES, nodes, nvars, generator=g) * 2.0 + 0.5).to(dev)
     forcing = (torch.randn(N_TIMES, nodes, d_forcing, generator=g) * 3.0 - 1.0).to(dev) if d_forcing else None
-    stats = {"state_mean": torch.randn(NVARS, generator=g).to(dev), "state_std": (torch.rand(NVARS, generator=g) + 0.5).to(dev)}
+    stats = {"state_mean": torch.randn(nvars, generator=g).to(dev), "state_std": (torch.rand(nvars, generator=g) + 0.5).to(dev)}
     if d_forcing:
         stats.update(forcing_mean=torch.randn(d_forcing, generator=g).to(dev), forcing_std=(torch.rand(d_forcing, generator=g) + 0.5).to(dev))
     times = (torch.arange(N_TIMES, dtype=torch.int64) * 3_600_000_000_000 + 1_700_000_000_000_000_000).to(dev)
@@ -321,45 +321,47 @@ def test_head_and_init_give_the_bits_of_the_data_path(dev, past, fut, d_forcing,
         assert rel_err(fw.cpu().to(torch.float64), fw64) <= 2 * EPS32
 
 
-def _tail_case(dev, nodes, clamp, std_head, misalign, with_times, seed=1):
-    """Inputs of one tail launch at lead K of LEAD, every output NaN / -1 filled."""
+def _tail_case(dev, nodes, clamp, std_head, misalign, with_times, seed=1, nvars=NVARS, batch=BATCH):
+    """Inputs of one tail launch at lead K of LEAD, every output NaN / -1 filled; `nvars` variables, `batch` forecasts."""
     from neural_lam_amd.ops import ClampTables
 
     put = _misaligned if misalign else (lambda t: t)
     g = torch.Generator().manual_seed(seed)
-    state, _, times, stats = _series(dev, 0, nodes=nodes)
-    ld = 2 * NVARS if std_head else NVARS
-    c = types.SimpleNamespace(nodes=nodes, ld=ld, stats=stats, state=state, times=times if with_times else None)
-    c.delta = put(torch.randn(BATCH * nodes, ld, generator=g).to(dev))
-    c.prev0 = (torch.randn(BATCH, nodes, NVARS, generator=g) * 0.7).to(dev)
-    c.pprev0 = torch.randn(BATCH, nodes, NVARS, generator=g).to(dev)
-    c.truth = put((torch.randn(BATCH, nodes, NVARS, generator=g) * 0.7).to(dev))
-    c.dstd = (torch.rand(NVARS, generator=g) * 0.5 + 0.1).to(dev)
-    c.dmean = (torch.randn(NVARS, generator=g) * 0.1).to(dev)
+    state, _, times, stats = _series(dev, 0, nodes=nodes, nvars=nvars)
+    ld = 2 * nvars if std_head else nvars
+    c = types.SimpleNamespace(nodes=nodes, ld=ld, stats=stats, state=state, times=times if with_times else None, nvars=nvars, batch=batch)
+    c.delta = put(torch.randn(batch * nodes, ld, generator=g).to(dev))
+    c.prev0 = (torch.randn(batch, nodes, nvars, generator=g) * 0.7).to(dev)
+    c.pprev0 = torch.randn(batch, nodes, nvars, generator=g).to(dev)
+    c.truth = put((torch.randn(batch, nodes, nvars, generator=g) * 0.7).to(dev))
+    c.dstd = (torch.rand(nvars, generator=g) * 0.5 + 0.1).to(dev)
+    c.dmean = (torch.randn(nvars, generator=g) * 0.1).to(dev)
     c.bmask = (torch.rand(nodes, generator=g) < 0.3).to(torch.float32).to(dev)
     interior = 1.0 - c.bmask
     c.row_weight = interior / interior.sum()
     c.clamp = None
-    if clamp:   # NONE, BOTH, LOWER and UPPER on different variables
-        lo = torch.tensor([0.0, -1.5, -1.2, 0.0, 0.0]).to(dev)
-        hi = torch.tensor([0.0, 1.5, 0.0, 1.3, 0.0]).to(dev)
-        c.clamp = ClampTables([L.CLAMP_NONE, L.CLAMP_BOTH, L.CLAMP_LOWER, L.CLAMP_UPPER, L.CLAMP_NONE], lo, hi)
-    c.start = torch.tensor([1, 6, 9], dtype=torch.int64, device=dev)
+    if clamp:   # NONE, BOTH, LOWER and UPPER on different variables: the five-variable table, repeated over the variables
+        cyc = lambda v: (v * (nvars // 5 + 1))[:nvars]   # noqa: E731
+        lo = torch.tensor(cyc([0.0, -1.5, -1.2, 0.0, 0.0])).to(dev)
+        hi = torch.tensor(cyc([0.0, 1.5, 0.0, 1.3, 0.0])).to(dev)
+        c.clamp = ClampTables(cyc([L.CLAMP_NONE, L.CLAMP_BOTH, L.CLAMP_LOWER, L.CLAMP_UPPER, L.CLAMP_NONE]), lo, hi)
+    c.start = torch.tensor([1, 6, 9, 4, 7, 2][:batch], dtype=torch.int64, device=dev)
     c.lead = torch.zeros(1, dtype=torch.int32, device=dev)
     return c, put
 
 
 def _tail_buffers(c, put, slots, verify):
     dev = c.delta.device
+    B, F = c.batch, c.nvars
     nan = lambda *shape: put(torch.full(shape, float("nan"), device=dev))   # noqa: E731
     b = types.SimpleNamespace()
     b.prev, b.pprev = put(c.prev0.clone()), put(c.pprev0.clone())
-    b.out_state = nan(BATCH, slots, c.nodes, NVARS)
-    b.out_std = nan(BATCH, slots, c.nodes, NVARS) if c.ld == 2 * NVARS else None
-    b.valid_times = torch.full((BATCH, slots), -1, dtype=torch.int64, device=dev)
-    b.sq = nan(BATCH, slots, NVARS) if verify else None
-    b.ab = nan(BATCH, slots, NVARS) if verify else None
-    b.workspace = torch.full((int(L.load().nlam_forecast_workspace_floats(BATCH, c.nodes, NVARS)),), float("nan"), device=dev) if verify else None
+    b.out_state = nan(B, slots, c.nodes, F)
+    b.out_std = nan(B, slots, c.nodes, F) if c.ld == 2 * F else None
+    b.valid_times = torch.full((B, slots), -1, dtype=torch.int64, device=dev)
+    b.sq = nan(B, slots, F) if verify else None
+    b.ab = nan(B, slots, F) if verify else None
+    b.workspace = torch.full((int(L.load().nlam_forecast_workspace_floats(B, c.nodes, F)),), float("nan"), device=dev) if verify else None
     return b
 
 
