@@ -68,6 +68,9 @@
  *   nlam_ens_neighbourhood, nlam_ens_neighbourhood_workspace_floats
  *       the same events on the grid as a lattice: the fraction of (member, cell) pairs in the event inside square windows of a
  *       ladder of radii, and the two sums of the fractions skill score, from integer summed-area tables.
+ *   nlam_dct_spectra, nlam_dct_spectra_workspace_floats
+ *       at which scales a forecast holds variance, per lead of that step: binned variance spectra of lattice fields from a 2-D
+ *       orthonormal DCT, as two fp32 matrix products on the matrix cores and a fixed-order sum per bin.
  *   nlam_latent_kl_fwd, nlam_latent_kl_bwd, nlam_latent_kl_workspace_floats
  *       the variational training objective of Graph-EFM: the reparameterised posterior draw from that generator and the KL
  *       divergence from the prior as one pass with a fixed-order reduction, and its elementwise backward.
@@ -1260,6 +1263,64 @@ int32_t nlam_ens_neighbourhood(const nlam_ens_neighbourhood_t* p, void* hip_stre
  * nodes; NLAM_EINVAL for sizes < 1, NLAM_EUNSUP as nlam_ens_neighbourhood */
 int64_t nlam_ens_neighbourhood_workspace_floats(int32_t starts, int32_t members, int32_t nx, int32_t ny, int32_t nvars, int32_t events,
                                                 int32_t scales);
+
+/* Variance spectra of lattice fields from a 2-D discrete cosine transform (Denis, Cote and Laprise 2002), for lead slot
+ * k = *lead (only read; nothing is written once k >= max_lead): inside the recorded forecast step, before nlam_forecast_finish.
+ * Grid and window: the grid is nx x ny, node n = i * ny + j; the window i0 <= i < i0 + cx, j0 <= j < j0 + cy has cx >= 2 and
+ *   cy >= 2 (they size the launches) and its origin (i0, j0) = origin[0 .. 1] in device memory, read by the launch and clamped
+ *   into [0, nx - cx] x [0, ny - cy]: a replay sees a moved window, and nothing outside the grid is ever read.  One field (item b
+ *   of a source, variable v with f = var[v]) is g(i, j) = x[b][(i0 + i) * ny + (j0 + j)][f].
+ * Basis: C_n[k][i] = beta_k cos(pi k (2 i + 1) / (2 n)), beta_0 = sqrt(1 / n), beta_k = sqrt(2 / n): the orthonormal DCT-II,
+ *   computed by the host in float64 and rounded once to fp32; basis_x = C_cx (cx, cx), basis_y = C_cy (cy, cy), row-major [k][i].
+ * Coefficients: G(m, n) = sum_i sum_j basis_x[m][i] g(i, j) basis_y[n][j], as two passes of fp32 dot products in ascending index
+ *   order, first along j, then along i, on v_mfma_f32_16x16x4_f32 (bitwise an fp32 fmaf chain).
+ * Variance array: s2(m, n) = G(m, n)^2 / (cx cy); by Parseval the sum over (m, n) != (0, 0) is the population variance of g.
+ * Bins: the launch knows no binning convention.  The host passes the coefficients of every bin as a CSR list: bin b owns
+ *   bin_idx[bin_ptr[b] .. bin_ptr[b + 1]), each entry a coefficient m * cy + n; a coefficient that is in no list is dropped (the
+ *   host leaves (0, 0), the mean, out).  bin_ptr has bins + 1 words inside [0, bin_entries] (clamped as they are read), bin_idx
+ *   has bin_entries <= cx cy words (clamped into [0, cx cy)).
+ * Output: spec[b][k][v][bin] = scale_v / (cx cy) * sum over the bin's list, in list order, of G^2; scale_v = state_std[f]^2 for
+ *   a standardised source (physical units squared), 1 for a source with physical = 1; 0 for an empty bin.  The sum is added in
+ *   a fixed order, without floating-point atomics: two runs give the same bits.
+ * Sources: up to NLAM_SPEC_MAX_SOURCES per call, each (batch, nx * ny, d_state) floats with its own batch stride and a lead
+ *   stride multiplied by *lead (0 for the state of the step; nx * ny * d_state for per-lead slots such as out_mean of
+ *   nlam_ens_scores).  var, the bases, the bin lists and state_std are device memory, read by the launches: a replay sees new values.
+ *   var is clamped into [0, d_state).
+ * Three launches for every size.  Indices inside one item are 32-bit, offsets between items, sources and leads 64-bit.
+ * NLAM_EINVAL for null required pointers (lead, origin, both bases, var, bin_ptr, bin_idx, workspace, every source's x and spec,
+ * state_std with a standardised source), sizes < 1, sources outside [1, NLAM_SPEC_MAX_SOURCES], a source batch < 1 or a negative
+ * stride, a window larger than the grid or with cx or cy < 2, bin_entries outside [0, cx cy], a short workspace; NLAM_EUNSUP for
+ * d_state > NLAM_EVAL_MAX_VARS, vars > d_state, a source batch above 65535, nx * ny * d_state >= 2^31 or cx * cy * vars >= 2^31.
+ * Every check comes before any launch; no allocation, no host synchronisation. */
+#define NLAM_SPEC_MAX_SOURCES 3
+typedef struct {
+    const float* x;               /* (batch, nx * ny, d_state) */
+    float* spec;                  /* (batch, max_lead, vars, bins) */
+    int64_t batch_stride;         /* floats between two items */
+    int64_t lead_stride;          /* floats, multiplied by *lead */
+    int32_t batch;
+    int32_t physical;             /* 0: standardised, scale_v = state_std[f]^2; 1: scale_v = 1 */
+} nlam_dct_spectra_src_t;
+typedef struct {
+    nlam_dct_spectra_src_t src[NLAM_SPEC_MAX_SOURCES];
+    const int32_t* origin;        /* device (2): i0, j0 */
+    const float* basis_x;         /* device (cx, cx) */
+    const float* basis_y;         /* device (cy, cy) */
+    const int32_t* var;           /* device (vars) */
+    const int32_t* bin_ptr;       /* device (bins + 1) */
+    const int32_t* bin_idx;       /* device (bin_entries): m * cy + n, ascending inside a bin */
+    const float* state_std;       /* device (d_state) */
+    const int32_t* lead;          /* device (1): k, only read */
+    float* workspace;             /* nlam_dct_spectra_workspace_floats(items, cx, cy, vars) floats, items = the sum of the batches */
+    int64_t workspace_floats;
+    int32_t sources, nx, ny, d_state;
+    int32_t vars, bins, bin_entries, max_lead;
+    int32_t cx, cy;
+} nlam_dct_spectra_t;
+int32_t nlam_dct_spectra(const nlam_dct_spectra_t* p, void* hip_stream);
+/* floats of nlam_dct_spectra_t.workspace: the pass along j and the coefficients, 2 items cx cy vars; NLAM_EINVAL for items or
+ * vars < 1 and cx or cy < 2, NLAM_EUNSUP for items > 3 * 65535, vars > NLAM_EVAL_MAX_VARS or cx * cy * vars >= 2^31 */
+int64_t nlam_dct_spectra_workspace_floats(int32_t items, int32_t cx, int32_t cy, int32_t vars);
 
 /* The posterior draw and the KL term of the Graph-EFM training objective (Oskarsson et al. 2024, section 3; models.EFMForecaster)
  * inside the recorded training step.  With D = latent_dim, u = 1e-4, pq (batch, rows, 2 D) the encoder's parameters (always

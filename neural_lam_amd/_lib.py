@@ -104,6 +104,7 @@ ENS_MAX_MEMBERS = 64  # NLAM_ENS_MAX_MEMBERS: members of one nlam_ens_scores cal
 ENS_MAX_EVENTS = 32   # NLAM_ENS_MAX_EVENTS: threshold events of one nlam_ens_products call
 ENS_MAX_QUANTILES = 16   # NLAM_ENS_MAX_QUANTILES: quantile levels of one nlam_ens_products call
 NBR_MAX_SCALES = 8    # NLAM_NBR_MAX_SCALES: window radii of one nlam_ens_neighbourhood call
+SPEC_MAX_SOURCES = 3  # NLAM_SPEC_MAX_SOURCES: sources of one nlam_dct_spectra call
 MOMENTS_MAX_VARS = 256   # NLAM_MOMENTS_MAX_VARS: features of one nlam_window_moments call
 # learning-rate schedules of nlam_adamw_step_controlled (NLAM_SCHED_*) and the words of its control block
 SCHED_KINDS = {"constant": 1, "warmup_cosine": 2, "warmup_linear": 3}
@@ -210,6 +211,8 @@ EXPORTS = [
     "nlam_ens_products_workspace_floats",
     "nlam_ens_neighbourhood",
     "nlam_ens_neighbourhood_workspace_floats",
+    "nlam_dct_spectra",
+    "nlam_dct_spectra_workspace_floats",
     "nlam_latent_kl_fwd",
     "nlam_latent_kl_bwd",
     "nlam_latent_kl_workspace_floats",
@@ -582,6 +585,47 @@ class EnsNeighbourhood(C.Structure):
         ("max_lead", C.c_int32),
         ("events", C.c_int32),
         ("scales", C.c_int32),
+    ]
+
+
+class DctSpectraSrc(C.Structure):
+    """nlam_dct_spectra_src_t: one source of nlam_dct_spectra."""
+
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("spec", C.c_void_p),
+        ("batch_stride", C.c_int64),
+        ("lead_stride", C.c_int64),
+        ("batch", C.c_int32),
+        ("physical", C.c_int32),
+    ]
+
+
+class DctSpectra(C.Structure):
+    """nlam_dct_spectra_t: binned DCT variance spectra of up to SPEC_MAX_SOURCES sources of one lead."""
+
+    _fields_ = [
+        ("src", DctSpectraSrc * SPEC_MAX_SOURCES),
+        ("origin", C.c_void_p),
+        ("basis_x", C.c_void_p),
+        ("basis_y", C.c_void_p),
+        ("var", C.c_void_p),
+        ("bin_ptr", C.c_void_p),
+        ("bin_idx", C.c_void_p),
+        ("state_std", C.c_void_p),
+        ("lead", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_floats", C.c_int64),
+        ("sources", C.c_int32),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("d_state", C.c_int32),
+        ("vars", C.c_int32),
+        ("bins", C.c_int32),
+        ("bin_entries", C.c_int32),
+        ("max_lead", C.c_int32),
+        ("cx", C.c_int32),
+        ("cy", C.c_int32),
     ]
 
 
@@ -1047,6 +1091,10 @@ def load():
     lib.nlam_ens_neighbourhood.restype = i32
     lib.nlam_ens_neighbourhood_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32, i32]
     lib.nlam_ens_neighbourhood_workspace_floats.restype = i64
+    lib.nlam_dct_spectra.argtypes = [C.POINTER(DctSpectra), vp]
+    lib.nlam_dct_spectra.restype = i32
+    lib.nlam_dct_spectra_workspace_floats.argtypes = [i32, i32, i32, i32]
+    lib.nlam_dct_spectra_workspace_floats.restype = i64
     lib.nlam_latent_kl_fwd.argtypes = [C.POINTER(LatentKl), vp]
     lib.nlam_latent_kl_fwd.restype = i32
     lib.nlam_latent_kl_bwd.argtypes = [C.POINTER(LatentKl), vp]

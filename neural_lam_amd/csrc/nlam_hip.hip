@@ -7329,6 +7329,7 @@ int64_t nlam_eval_workspace_floats(int32_t batch, int32_t steps, int32_t nodes, 
 #include "nlam_ensemble.inc"   // the sampled-ensemble launches of the same recorded step
 #include "nlam_ens_products.inc"   // exceedance probabilities, quantile fields and their scores, one more pass of the same shape
 #include "nlam_ens_neighbourhood.inc"   // neighbourhood probabilities and the FSS sums of the same events, from summed-area tables
+#include "nlam_spectra.inc"    // DCT variance spectra of the same step's fields: two fp32 GEMMs on the matrix cores and a bin sum
 #include "nlam_latent_kl.inc"  // the posterior draw and the KL term of the Graph-EFM training step (the same generator)
 #include "nlam_crps_ens.inc"   // the prior draw with a gradient and the ensemble CRPS term of its fine-tuning stage
 #endif

@@ -39,6 +39,12 @@ radius the fraction of (member, cell) pairs in the event around every cell, and 
     ens = EnsembleForecast(step, dataset, 40, members=16, events=[("tp", ">", 1e-3)], neighbourhoods=[0, 1, 2, 5, 10],
                            grid_shape=(nx, ny))
     pr = ens.run([0]).products      # pr.nprob (S, L, E, W, N);  pr.fss() (L, E, W)
+
+``spectra`` (with ``grid_shape``, on either engine) adds ``nlam_dct_spectra``: per lead the variance spectrum of the forecast (every
+member), the analysis and the ensemble mean from a 2-D discrete cosine transform, binned by total wavenumber.
+
+    fc = Forecast(step, dataset, 40, spectra=["t2m", "u10"], grid_shape=(nx, ny), spectra_window=(10, nx - 10, 10, ny - 10))
+    sp = fc.run([0]).spectra        # Spectra: sp.forecast, sp.analysis (B, L, V, nb);  sp.wavenumber, sp.wavelength(2.5)
 """
 from __future__ import annotations
 
@@ -118,6 +124,123 @@ def check_starts(starts, n_starts):
     return host
 
 
+def dct_basis(n):
+    """The orthonormal DCT-II basis ``C[k][i] = beta_k cos(pi k (2 i + 1) / (2 n))``, ``beta_0 = sqrt(1 / n)``, ``beta_k = sqrt(2 / n)``
+    (``scipy.fft.dct(norm="ortho")`` of the identity), a float64 ``(n, n)`` tensor.  ``nlam_dct_spectra`` takes it rounded once to
+    fp32.  No GPU."""
+    import math
+
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"dct_basis: n {n} must be >= 1")
+    k = torch.arange(n, dtype=torch.int64)[:, None]
+    i = torch.arange(n, dtype=torch.int64)[None, :]
+    turn = (k * (2 * i + 1)) % (4 * n)   # the angle in units of pi / (2 n), reduced in integers: the cosine's argument stays below 2 pi
+    basis = torch.cos(turn.to(torch.float64) * (math.pi / (2.0 * n))) * math.sqrt(2.0 / n)
+    basis[0] = math.sqrt(1.0 / n)
+    return basis
+
+
+def dct_bins(cx, cy):
+    """``(bin_of, bin_ptr, bin_idx, nb)``: the binning of Denis, Cote and Laprise (2002) of the ``cx x cy`` DCT coefficients by total
+    normalised wavenumber, ``nb = Nmin = min(cx, cy)`` bins.  With ``k = floor(Nmin sqrt(m^2 / cx^2 + n^2 / cy^2))`` decided in
+    integers (``k`` is the largest integer with ``k^2 cx^2 cy^2 <= (m^2 cy^2 + n^2 cx^2) Nmin^2``; no float tie decides a bin),
+    coefficient ``(m, n)`` goes to bin ``max(k, 1) - 1`` when ``k <= Nmin - 1`` and to the last bin -- the corner beyond the
+    inscribed quarter ellipse -- otherwise; ``(0, 0)``, the mean, goes to -1 (dropped), so the bins of a field add up to its
+    variance.  ``bin_of`` (cx * cy) int32 at ``m * cy + n``; ``bin_ptr`` (nb + 1) / ``bin_idx`` int32 the same as a CSR list,
+    ascending in ``m * cy + n`` inside a bin: the order ``nlam_dct_spectra`` adds in.  No GPU."""
+    import math
+
+    cx, cy = int(cx), int(cy)
+    if cx < 2 or cy < 2:
+        raise ValueError(f"dct_bins: a window of {cx} x {cy} cells; both sides must be >= 2")
+    nmin = min(cx, cy)
+    den = cx * cx * cy * cy
+    bin_of = []
+    for m in range(cx):
+        for n in range(cy):
+            if m == 0 and n == 0:
+                bin_of.append(-1)
+                continue
+            k = math.isqrt((m * m * cy * cy + n * n * cx * cx) * nmin * nmin // den)
+            bin_of.append(max(k, 1) - 1 if k <= nmin - 1 else nmin - 1)
+    lists = [[] for _ in range(nmin)]
+    for idx, b in enumerate(bin_of):
+        if b >= 0:
+            lists[b].append(idx)
+    ptr = [0]
+    for lst in lists:
+        ptr.append(ptr[-1] + len(lst))
+    i32 = torch.int32
+    return (torch.tensor(bin_of, dtype=i32), torch.tensor(ptr, dtype=i32),
+            torch.tensor([i for lst in lists for i in lst], dtype=i32), nmin)
+
+
+def parse_spectra(spectra, grid_shape, window, var_names, n_vars, nodes=None):
+    """The host checks of ``Forecast(spectra=..., grid_shape=..., spectra_window=...)``: ``(variables, (nx, ny), (i0, i1, j0, j1))``
+    with every variable as its index, or ``([], None, None)`` without ``spectra``.  ``window`` None is the whole grid.  ValueError
+    for an unknown variable name or an index out of range, a duplicate, an empty list, a missing grid shape or one that does not
+    hold ``nodes`` nodes (when they are known), and a window that is not four integers with ``0 <= i0 < i1 <= nx``,
+    ``i1 - i0 >= 2`` and the same in j.  No GPU."""
+    if spectra is None:
+        return [], None, None
+    if isinstance(spectra, (str, bytes)):
+        spectra = [spectra]
+    variables = []
+    for var in spectra:
+        if isinstance(var, str):
+            if var_names is None or var not in var_names:
+                raise ValueError(f"Forecast: unknown state variable {var!r} in spectra (known: {var_names})")
+            idx = list(var_names).index(var)
+        else:
+            try:
+                idx = int(var)
+            except (TypeError, ValueError):
+                idx = -1
+            if isinstance(var, bool) or idx != var or not 0 <= idx < n_vars:
+                raise ValueError(f"Forecast: spectra variable index {var!r} outside [0, {n_vars})")
+        if idx in variables:
+            raise ValueError(f"Forecast: state variable {var!r} is listed twice in spectra")
+        variables.append(idx)
+    if not variables:
+        raise ValueError("Forecast: spectra is empty")
+    try:
+        nx, ny = (int(v) for v in grid_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"Forecast: spectra need grid_shape=(nx, ny), got {grid_shape!r}") from None
+    if nx < 1 or ny < 1 or (nodes is not None and nx * ny != nodes):
+        raise ValueError(f"Forecast: grid_shape {(nx, ny)} does not hold the {nodes} grid nodes")
+    if window is None:
+        window = (0, nx, 0, ny)
+    try:
+        win = tuple(int(v) for v in window)
+        exact = len(win) == 4 and all(not isinstance(v, bool) and w == v for v, w in zip(window, win))
+    except (TypeError, ValueError):
+        exact = False
+    if not exact:
+        raise ValueError(f"Forecast: spectra_window is four integers (i0, i1, j0, j1), got {window!r}")
+    i0, i1, j0, j1 = win
+    if not (0 <= i0 < i1 <= nx and 0 <= j0 < j1 <= ny) or i1 - i0 < 2 or j1 - j0 < 2:
+        raise ValueError(f"Forecast: spectra_window {win} needs 0 <= i0 < i1 <= {nx}, 0 <= j0 < j1 <= {ny} and at least 2 cells "
+                         "along each side")
+    return variables, (nx, ny), win
+
+
+class Spectra(NamedTuple):
+    """Device tensors of ``nlam_dct_spectra`` for one run, cut to the ``leads`` that ran: the variance of every selected variable
+    per wavenumber bin, in physical units squared; the bins of one field add up to its population variance over the window."""
+    forecast: torch.Tensor             # (B, leads, V, nb): every batch item (every member, b = s * M + m, of an ensemble)
+    analysis: torch.Tensor             # (B, leads, V, nb) (Forecast) or (S, leads, V, nb) (EnsembleForecast)
+    mean: Optional[torch.Tensor]       # (S, leads, V, nb) of the ensemble mean, or None
+    variables: tuple                   # the state variable index of every v
+    wavenumber: torch.Tensor           # (nb) float64, host: k / Nmin of bin k - 1; NaN for the last bin, the corner
+    window: tuple                      # (i0, i1, j0, j1)
+
+    def wavelength(self, spacing):
+        """(nb) wavelength of every bin in the units of the grid ``spacing``: ``2 * spacing / wavenumber`` (NaN for the corner bin)."""
+        return 2.0 * float(spacing) / self.wavenumber
+
+
 class ForecastResult(NamedTuple):
     """Device tensors of one ``Forecast.run``: ``state`` (B, L, N, F) in physical units, ``std`` (B, L, N, F) the predicted std
     in physical units or None, ``valid_times`` (B, L) int64 (time stamps, or time indices for a dataset without them), ``sq`` /
@@ -128,6 +251,7 @@ class ForecastResult(NamedTuple):
     valid_times: torch.Tensor
     sq: Optional[torch.Tensor]
     ab: Optional[torch.Tensor]
+    spectra: Optional[Spectra] = None   # Forecast(spectra=...): cut to the leads that ran
 
     def rmse(self, state_std):
         """(L, F) ``sqrt(mean_b sq) * state_std``: the rescaling of the reference's test epoch (models/module.py)."""
@@ -181,11 +305,25 @@ class Forecast:
     same launches eagerly.
     ``autocast_dtype``: the predictor call alone runs under ``torch.autocast`` with it.  Weights changed in place between two
     ``run`` calls (a training step, ``load_state_dict``, ``with tr.ema_weights():``) are honoured by the second call: the recorded
-    step reads the parameters where they live and the static embeddings are recomputed by every ``run``."""
+    step reads the parameters where they live and the static embeddings are recomputed by every ``run``.
+    ``spectra``: state variables (names of ``step.state_var_names`` or indices) whose variance spectrum is wanted per lead, on the
+    ``grid_shape = (nx, ny)`` lattice, node ``n = i * ny + j`` as ``graph.py`` numbers it, over ``spectra_window = (i0, i1, j0, j1)``
+    (default: the whole grid; pass the interior box so that the boundary rows, where forecast and analysis are the same by
+    construction, do not dilute the comparison).  It adds ``nlam_dct_spectra`` between the tail and the finish of the recorded step:
+    ``SPECTRA_LAUNCHES`` = 3 launches per lead for every size, ``ForecastResult.spectra`` with the spectra of the forecast and of the
+    analysis (``8 B L V nb`` bytes, ``nb = min(cx, cy)``) and ``8 B cx cy V`` bytes of workspace per source.  ``set_spectra_window``
+    moves the window without a new recording.  With ``spectra=None`` nothing is allocated or launched."""
 
     _serves_latent = False
+    _defers_spectra = False   # a subclass whose sources do not exist yet when this constructor ends sets the call up itself
+    SPECTRA_LAUNCHES = 3   # pass along j, pass along i, bins: for every size, window, variable list and source count
 
-    def __init__(self, step, dataset, max_lead, batch_size=1, verify=False, use_graph=True, autocast_dtype=None):
+    def __init__(self, step, dataset, max_lead, batch_size=1, verify=False, use_graph=True, autocast_dtype=None, spectra=None,
+                 grid_shape=None, spectra_window=None):
+        weight = getattr(step, "interior_weight", None)
+        self._spec_vars, self._spec_grid, self._spec_window = parse_spectra(
+            spectra, grid_shape, spectra_window, getattr(step, "state_var_names", None),
+            int(getattr(step, "state_mean", torch.empty(0)).numel()), None if weight is None else int(weight.numel()))
         from .models import ARForecaster
 
         forecaster = getattr(step, "forecaster", None)
@@ -288,6 +426,77 @@ class Forecast:
         self._graph = None
         self._delta = None      # the recorded step's network output (kept alive with the graph)
         self._launches = None
+        self._sp = None
+        if self._spec_vars and not self._defers_spectra:
+            parse_spectra(self._spec_vars, self._spec_grid, self._spec_window, None, F, N)
+            self._init_spectra(self._spectra_sources())
+
+    # ---- variance spectra ----
+    def _spectra_sources(self):
+        """``(name, tensor, batch, batch stride, lead stride, physical)`` of every source of the ``nlam_dct_spectra`` call."""
+        B, per = self.batch_size, self._p.nodes * self._p.d_state
+        return [("forecast", self.prev, B, per, 0, 0), ("analysis", self.truth, B, per, 0, 0)]
+
+    def _init_spectra(self, sources):
+        """The tables, outputs and argument struct of ``nlam_dct_spectra`` (only with ``spectra``)."""
+        (nx, ny), (i0, i1, j0, j1) = self._spec_grid, self._spec_window
+        cx, cy, V, Lm = i1 - i0, j1 - j0, len(self._spec_vars), self.max_lead
+        dev = self.start.device
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        _, bin_ptr, bin_idx, nb = dct_bins(cx, cy)
+        self.spec_basis_x, self.spec_basis_y = dct_basis(cx).to(**f32), dct_basis(cy).to(**f32)   # float64, rounded once
+        self.spec_bin_ptr, self.spec_bin_idx = bin_ptr.to(dev), bin_idx.to(dev)
+        self.spec_var = torch.tensor(self._spec_vars, **i32)
+        self.spec_origin = torch.tensor([i0, j0], **i32)
+        items = sum(src[2] for src in sources)
+        nws = int(self._lib.nlam_dct_spectra_workspace_floats(items, cx, cy, V))
+        if nws < 0 or len(sources) > L.SPEC_MAX_SOURCES:
+            raise ValueError(f"Forecast: nlam_dct_spectra does not serve these sizes ({nws})")
+        self.spectra_workspace = torch.empty((nws,), **f32)
+        self.spec_out = {}
+        sp = L.DctSpectra()
+        for k, (name, t, batch, batch_stride, lead_stride, physical) in enumerate(sources):
+            self.spec_out[name] = torch.zeros((batch, Lm, V, nb), **f32)
+            q = sp.src[k]
+            q.x, q.spec = t.data_ptr(), self.spec_out[name].data_ptr()
+            q.batch_stride, q.lead_stride, q.batch, q.physical = batch_stride, lead_stride, batch, physical
+        sp.origin, sp.basis_x, sp.basis_y = _ptr(self.spec_origin), _ptr(self.spec_basis_x), _ptr(self.spec_basis_y)
+        sp.var, sp.bin_ptr, sp.bin_idx = _ptr(self.spec_var), _ptr(self.spec_bin_ptr), _ptr(self.spec_bin_idx)
+        sp.state_std, sp.lead = _ptr(self.step.state_std), _ptr(self.lead)
+        sp.workspace, sp.workspace_floats = _ptr(self.spectra_workspace), nws
+        sp.sources, sp.nx, sp.ny, sp.d_state = len(sources), nx, ny, self._p.d_state
+        sp.vars, sp.bins, sp.bin_entries, sp.max_lead = V, nb, int(bin_idx.numel()), Lm
+        sp.cx, sp.cy = cx, cy
+        wn = torch.arange(1, nb + 1, dtype=torch.float64) / nb
+        wn[-1] = float("nan")
+        self._spec_wavenumber = wn
+        self._sp = sp
+
+    def set_spectra_window(self, window):
+        """A new window ``(i0, i1, j0, j1)`` of the same ``cx x cy`` cells for the following runs: the origin the launches read is
+        rewritten in device memory (the bases and the bins depend on ``cx`` and ``cy`` alone).  No new recording, like
+        ``set_thresholds``; a window that changes ``cx`` or ``cy`` is a ValueError (it would change the launches)."""
+        if self._sp is None:
+            raise ValueError("Forecast.set_spectra_window: the engine was built without spectra")
+        _, _, win = parse_spectra(self._spec_vars, self._spec_grid, window, None, self._p.d_state)
+        if (win[1] - win[0], win[3] - win[2]) != (self._sp.cx, self._sp.cy):
+            raise ValueError(f"Forecast.set_spectra_window: {win} is {win[1] - win[0]} x {win[3] - win[2]} cells, the recorded "
+                             f"step takes {self._sp.cx} x {self._sp.cy}")
+        self.spec_origin.copy_(torch.tensor([win[0], win[2]], dtype=torch.int32))
+        self._spec_window = win
+
+    def _launch_spectra(self):
+        from .ops import _stream
+
+        if self._sp is not None:
+            L.check(self._lib.nlam_dct_spectra(C.byref(self._sp), _stream()), "nlam_dct_spectra")
+
+    def _spectra_result(self, leads):
+        if self._sp is None:
+            return None
+        out = {name: t.narrow(1, 0, leads) for name, t in self.spec_out.items()}
+        return Spectra(out["forecast"], out["analysis"], out.get("mean"), tuple(self._spec_vars), self._spec_wavenumber,
+                       tuple(self._spec_window))
 
     # ---- one lead time ----
     def _entry(self, name):
@@ -314,7 +523,8 @@ class Forecast:
         return delta
 
     def _after_tail(self):
-        """Launches between the tail and the finish of a lead (none here)."""
+        """Launches between the tail and the finish of a lead: ``nlam_dct_spectra`` with ``spectra``, else none."""
+        self._launch_spectra()
 
     def _one_lead(self):
         """head -> predictor -> tail -> finish on the current stream; every launch reads the lead counter on the device."""
@@ -369,7 +579,8 @@ class Forecast:
 
     @property
     def launches_per_lead(self):
-        """Kernel nodes of the recorded step (it is recorded on first use); None with ``use_graph=False``."""
+        """Kernel nodes of the recorded step (it is recorded on first use); None with ``use_graph=False``.  ``spectra`` adds
+        ``SPECTRA_LAUNCHES`` = 3 to it, for every size."""
         if not self.use_graph:
             return None
         if self._graph is None:
@@ -394,7 +605,7 @@ class Forecast:
         if starts.numel() != self.batch_size:
             raise ValueError(f"Forecast.run: {starts.numel()} starts for batch_size {self.batch_size}")
         self._replay(starts, leads)
-        return ForecastResult(self.out_state, self.out_std, self.valid_times, self.sq, self.ab)
+        return ForecastResult(self.out_state, self.out_std, self.valid_times, self.sq, self.ab, self._spectra_result(leads))
 
     def _dataset_times(self, starts):
         """``valid_times`` of a strided dataset, the ``target_times`` of ``dataset.batch``: ``times[s + off + k]`` (analysis data),
@@ -584,6 +795,7 @@ class EnsembleResult(NamedTuple):
     noise: Optional[torch.Tensor]      # (leads, S * M, R, latent_dim) the standard-normal draws (record_noise / latent_noise)
     n_members: int
     products: Optional[EnsembleProducts] = None   # EnsembleForecast(events=..., quantiles=...)
+    spectra: Optional[Spectra] = None             # EnsembleForecast(spectra=...)
 
     def _per_member(self, t):
         return None if t is None else t.view(t.shape[0] // self.n_members, self.n_members, *t.shape[1:])
@@ -659,12 +871,18 @@ class EnsembleForecast(Forecast):
     ``graph.py`` numbers it; it needs ``events`` and ``members * nodes <= 2^24``.  It adds ``nlam_ens_neighbourhood`` behind
     ``nlam_ens_products`` (5 launches per lead with ``verify``, 4 without, for every size): ``products.nprob`` takes ``4 S L E W N``
     bytes, ``fbs`` / ``fbs_ref`` / ``fss()`` come with ``verify``.  The radii live in a device table (``set_radii``), and the event
-    tables are shared, so ``set_thresholds`` moves both launches.  With ``neighbourhoods=None`` nothing is allocated or launched."""
+    tables are shared, so ``set_thresholds`` moves both launches.  With ``neighbourhoods=None`` nothing is allocated or launched.
+    ``spectra`` / ``spectra_window``: as in ``Forecast`` (``grid_shape`` is the one ``neighbourhoods`` use).  ``nlam_dct_spectra`` goes
+    last before the finish, 3 launches per lead for every size, over three sources: every member, the analysis of every start and
+    the ensemble mean that ``nlam_ens_scores`` has just written (``EnsembleResult.spectra.forecast`` (S M, L, V, nb), ``.analysis``
+    and ``.mean`` (S, L, V, nb))."""
 
     _serves_latent = True
+    _defers_spectra = True    # the mean slots come after Forecast.__init__
 
     def __init__(self, step, dataset, max_lead, members, n_starts=1, seed=0, verify=True, use_graph=True, autocast_dtype=None,
-                 record_noise=False, events=None, quantiles=None, neighbourhoods=None, grid_shape=None):
+                 record_noise=False, events=None, quantiles=None, neighbourhoods=None, grid_shape=None, spectra=None,
+                 spectra_window=None):
         members, n_starts = int(members), int(n_starts)
         if not 1 <= members <= L.ENS_MAX_MEMBERS:
             raise ValueError(f"EnsembleForecast: members {members} outside [1, {L.ENS_MAX_MEMBERS}]")
@@ -676,7 +894,7 @@ class EnsembleForecast(Forecast):
         self._radii, self._grid = parse_neighbourhoods(neighbourhoods, grid_shape, len(self._events), members,
                                                        None if weight is None else int(weight.numel()))
         super().__init__(step, dataset, max_lead, batch_size=n_starts * members, verify=verify, use_graph=use_graph,
-                         autocast_dtype=autocast_dtype)
+                         autocast_dtype=autocast_dtype, spectra=spectra, grid_shape=grid_shape, spectra_window=spectra_window)
         S, M, B, Lm = n_starts, members, n_starts * members, self.max_lead
         N, F = self._p.nodes, self._p.d_state
         if F > L.EVAL_MAX_VARS:
@@ -721,6 +939,15 @@ class EnsembleForecast(Forecast):
         if self._radii:
             parse_neighbourhoods(self._radii, self._grid, len(self._events), M, N)
             self._init_neighbourhoods()
+        if self._spec_vars:
+            parse_spectra(self._spec_vars, self._spec_grid, self._spec_window, None, F, N)
+            self._init_spectra(self._spectra_sources())
+
+    def _spectra_sources(self):
+        """Every member, member 0's analysis row of every start, and this lead's slot of the ensemble mean (physical units)."""
+        S, M, Lm, per = self.starts_per_run, self.members, self.max_lead, self._p.nodes * self._p.d_state
+        return [("forecast", self.prev, S * M, per, 0, 0), ("analysis", self.truth, S, M * per, 0, 0),
+                ("mean", self.mean, S, Lm * per, per, 1)]
 
     def _init_products(self):
         """The tables, outputs and argument struct of ``nlam_ens_products`` (only with ``events`` or ``quantiles``)."""
@@ -841,6 +1068,7 @@ class EnsembleForecast(Forecast):
             L.check(self._lib.nlam_ens_products(C.byref(self._pr), _stream()), "nlam_ens_products")
         if self._nb is not None:
             L.check(self._lib.nlam_ens_neighbourhood(C.byref(self._nb), _stream()), "nlam_ens_neighbourhood")
+        self._launch_spectra()
 
     def _install(self, given):
         """Install the recording that draws the noise (``given`` False) or reads it from ``self.noise`` (True)."""
@@ -892,4 +1120,5 @@ class EnsembleForecast(Forecast):
             if self._nb is not None:
                 products = products._replace(nprob=cut(self.nprob), fbs=cut(self.fbs), fbs_ref=cut(self.fbs_ref), radii=tuple(self._radii))
         return EnsembleResult(cut(self.out_state), cut(self.out_std), cut(self.valid_times), cut(self.sq), cut(self.ab),
-                              cut(self.mean), cut(self.spread), *(cut(t) for t in scores), cut(noise, 0), self.members, products)
+                              cut(self.mean), cut(self.spread), *(cut(t) for t in scores), cut(noise, 0), self.members, products,
+                              self._spectra_result(leads))
